@@ -6,7 +6,7 @@ resident in HBM:   2B endpoint roots -> walk + per-root dedup + LP counts (walk_
 global unique LP rows -> SpG (segmented sort) -> Z_SF table -> SpJoin producing xz float32 [R,2,k] + indptr.
 Nothing is cached between steps; every step gets fresh pairs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cit2|collab|ppa] [--pairs B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cit2|collab|ppa] [--pairs B] [--dump-outputs DIR]
 
 N>1 is launched by the driver through torch.distributed.run (one rank per GPU); the graph is replicated, the
 pair batches are sharded (each rank its own: "weak"; --scaling strong splits one fixed batch), there is no data-path
@@ -236,6 +236,37 @@ def finish_step(xz, ind, sets):
     return xz, ind, sets
 
 
+# --dump-outputs DIR: what the last timed step handed its caller -- xz float32 [R,2,k] and its segment pointers -- so that two builds can
+# be compared output for output on the same seeded inputs.  Copied to the host right after the timed region (outside the clock, before a
+# later pass re-uses the step buffers) and written at the end of the run.
+DUMP_BYTES = 64 << 20
+_DUMPED = {}
+
+
+def step_outputs(xz, indptr):
+    """-> {name: float32 / float64 host array}: indptr (int64 [S+1] segment pointers) in full; xz for a fixed, seeded sample of the
+    S segments -- all of them when the whole fits DUMP_BYTES --, in segment order, and xz_segments, the segments that sample holds"""
+    ptr_ = indptr.cpu().numpy().astype(np.int64)
+    lens = np.diff(ptr_)
+    row_bytes = 4 * int(np.prod(xz.shape[1:]))
+    budget = DUMP_BYTES - 2 * 8 * ptr_.size             # (indptr and xz_segments, as float64)
+    order = np.random.default_rng(0).permutation(lens.size)
+    n = int(np.searchsorted(np.cumsum(lens[order]) * row_bytes, budget, side="right"))
+    segs = np.sort(order[:n])
+    lens_s = lens[segs]
+    rows = np.repeat(ptr_[segs] - np.cumsum(lens_s) + lens_s, lens_s) + np.arange(int(lens_s.sum()))
+    xz_s = xz[torch.from_numpy(rows).to(xz.device)].float().cpu().numpy()
+    return {"xz": xz_s, "indptr": ptr_.astype(np.float64), "xz_segments": segs.astype(np.float64)}
+
+
+def write_outputs(d, arrays):
+    if not arrays:
+        raise RuntimeError("--dump-outputs: the timed path kept no outputs")
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, f"{name}.npy"), a)
+
+
 def algorithmic_walk_bytes(csr, roots, sets, M, m):
     """SURVEY.md 8(d), per root: 4 (query) + 8 (indptr pair) + 4*min(deg,M) (first hop) + 12*M*(m-1) (later
     steps: 8 B indptr pair + 4 B neighbour) + 8*|S_r| (id + SFptr written) + 4 (nsize); int64 offsets: 8->16, 12->20."""
@@ -371,10 +402,11 @@ def literal_dropin(csr, M, k, n_cpu=32768, nthread_cpu=-1):
 _PPR_STORE = {}
 
 
-def bench_ppr(args, sp, sampler_mod, dev, rank, world, dist, desc, B, K, W, extra_regions=0, layout="aligned"):
+def bench_ppr(args, sp, sampler_mod, dev, rank, world, dist, desc, B, K, W, extra_regions=0, layout="aligned", dump_last=False):
     """SpJoin over a resident float-payload SpG (the citation2 PPR configuration): one step = B pairs -> xz [R,2,1].
     layout: "aligned" (round 6, the serving layout: SpG.aligned() -- rows on whole 128-byte lines at a fixed pitch, their lengths in
-    their first slots, no row pointers) or "packed" (the CSR the offline stage leaves, as rounds 1-5 joined it)."""
+    their first slots, no row pointers) or "packed" (the CSR the offline stage leaves, as rounds 1-5 joined it).
+    dump_last: keep the last timed step's (xz, indptr) for --dump-outputs (rank 0)."""
     from surel_plus_amd.graphs import ppr_like_spg, preset_graph
     key = (os.environ.get("SUBGACC_PPR_SYNTH", "0"), args.scale, str(dev))
     if key in _PPR_STORE:                                    # (the store of the pass before: the offline stage is not what is timed)
@@ -425,12 +457,16 @@ def bench_ppr(args, sp, sampler_mod, dev, rank, world, dist, desc, B, K, W, extr
                 return sp.gather(edges[s], z, dev, ptr=True, encode=None, out=bufs[s & 1], lazy=True)
         return pool.submit(edges[s], sync=False)          # (the batches were made before the region and synchronised)
 
+    last = []
+
     def resolve(q):
         if eager:
             import surel_plus_amd.spjoin as sj
             sj.lazy_join_status(q[1])
-            return int(q[1][-1].item())
-        return int(pool.finish(q)[0].shape[0])
+            last[:] = [q[0][: int(q[1][-1].item())], q[1]]
+        else:
+            last[:] = pool.finish(q)
+        return int(last[0].shape[0])
     for s in range(W):
         resolve(step(s))
     torch.cuda.synchronize()
@@ -452,6 +488,8 @@ def bench_ppr(args, sp, sampler_mod, dev, rank, world, dist, desc, B, K, W, extr
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     timer.enabled = False
+    if dump_last and rank == 0:
+        _DUMPED.update(step_outputs(*last))
     region_values = [world * B * K / elapsed]
     for r_ in range(extra_regions if (world == 1 and rank == 0) else 0):      # more regions of K steps, outside the clock
         torch.cuda.synchronize()
@@ -584,9 +622,10 @@ def median(v):
 
 def bench_lp(args, name, rng, B, K, W, sp, sampler_mod, dev, rank, world, dist, with_cpu_baseline, csr_variant=True,
              small_batches=False, two_stream_extra=True, dedup_extra=None, offline=False, extra_regions=(0, 0), value_is_median=False, captured=False,
-             cpu_kw={}, wake_s=0.0, host_fed=False, ref_flow=False):
+             cpu_kw={}, wake_s=0.0, host_fed=False, ref_flow=False, dump_last=False):
     """sample + SpJoin over one LP workload: W warm-up steps, K timed steps bracketed by barrier + synchronize, max over
     ranks.  Returns the JSON object (rank 0) or None.
+    dump_last: keep the last timed step's (xz, indptr) for --dump-outputs (rank 0; not with captured).
     extra_regions = (R, Kx): after the timed region, R more regions of Kx steps each in the same loop (rank 0, 1 GPU): their
     pairs/s as min / median / max -- the timed region of the driver's K steps is ~25 ms, one host hiccup away from any number;
     value_is_median: `value` is the median over the main region and the extras (the short passes over the other workloads).
@@ -640,12 +679,12 @@ def bench_lp(args, name, rng, B, K, W, sp, sampler_mod, dev, rank, world, dist, 
                 queued = hot_path_step(sp, csr, e, M, k, seed=s, rng=rng, slot=s & 1)
             if pending is not None:
                 xz, ind, sets = finish_step(*pending[1])
-                last = (pending[0], sets, xz)
+                last = (pending[0], sets, xz, ind)
             pending = (e, queued)
             step_marks.append(time.perf_counter())
         if pending is not None:
             xz, ind, sets = finish_step(*pending[1])
-            last = (pending[0], sets, xz)
+            last = (pending[0], sets, xz, ind)
 
     caps = None
     if captured:
@@ -702,6 +741,10 @@ def bench_lp(args, name, rng, B, K, W, sp, sampler_mod, dev, rank, world, dist, 
     elapsed = time.perf_counter() - t0
     timer.enabled = False
     timer.every = 1
+    if dump_last and rank == 0:
+        if captured:
+            raise ValueError("dump_last: the captured loop keeps no step outputs")
+        _DUMPED.update(step_outputs(last[2], last[3]))
     allocs_timed = torch.cuda.memory_stats().get("num_device_alloc", 0) - allocs0
     host_steps = [b - a for a, b in zip(step_marks, step_marks[1:])]
     elapsed_local = elapsed
@@ -797,7 +840,7 @@ def bench_lp(args, name, rng, B, K, W, sp, sampler_mod, dev, rank, world, dist, 
     if rank != 0:
         return None
 
-    edge, sets, xz = last
+    edge, sets, xz, _ = last
     walk_ms, launches = timer.mean_ms("walk_sets")
     join_ms, _ = timer.mean_ms("sjoin_fill")
     abytes = last_abytes
@@ -1327,6 +1370,9 @@ def main():
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: --pairs per step PER GPU (the driver's scaling runs); strong: --pairs per step in all, split over "
                          "the ranks as shard.shard_pairs splits a batch (contiguous shares)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned (rank 0) as DIR/<name>.npy: xz float32, indptr float64 and "
+                         "xz_segments float64 (the segments whose rows xz holds: all of them, or a fixed seeded sample within 64 MB)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -1377,7 +1423,7 @@ def main():
     t_start = time.perf_counter()
     if WORKLOADS[args.workload][0] is None:
         out = bench_ppr(args, sp, sampler_mod, dev, rank, world, dist, WORKLOADS[args.workload][3], B, K, W,
-                        layout=os.environ.get("SUBGACC_PPR_LAYOUT", "aligned"))
+                        layout=os.environ.get("SUBGACC_PPR_LAYOUT", "aligned"), dump_last=bool(args.dump_outputs))
     else:
         out = bench_lp(args, args.workload, args.rng, B, K, W, sp, sampler_mod, dev, rank, world, dist,
                        with_cpu_baseline=(world == 1 and not args.no_cpu_baseline),
@@ -1392,9 +1438,13 @@ def main():
                        ref_flow=(rank == 0 and world == 1 and not args.no_others and args.scale == 1.0 and not args.workload.startswith("twitter")),
                        host_fed=not args.no_others,
                        # the driver's K steps are the headline region; three regions of 100 steps follow, outside its clock
-                       extra_regions=((3, 100) if (world == 1 and not args.no_others) else (0, 0)))
+                       extra_regions=((3, 100) if (world == 1 and not args.no_others) else (0, 0)),
+                       dump_last=bool(args.dump_outputs))
     if rank == 0 and out is not None:
         note(f"{args.workload}: {out['value'] / 1e6:.2f} M pairs/s in the driver's region of {K} steps")
+    if rank == 0 and args.dump_outputs:
+        write_outputs(args.dump_outputs, _DUMPED)
+        note(f"outputs of the last timed step: {', '.join(f'{n}{list(a.shape)}' for n, a in _DUMPED.items())} -> {args.dump_outputs}")
     # BASELINE.json's other single-GPU configurations (and the reference-bit-exact rand_r stream on the headline one),
     # as short passes after the timed region: same code path, >= 5 timed steps each, their own roofline blocks
     # (configs[0], the reference's CPU-runnable collab case, rides on the collab entry as its cpu_baseline).

@@ -131,3 +131,33 @@ def test_traffic_json_cites_tracked_files():
         src = entry.get("source", "")
         assert src.startswith("profiles/") and os.path.exists(os.path.join(ROOT, src)), (key, src)
         assert entry.get("kernel_source_sha")
+
+
+@pytest.mark.parametrize("budget", [None, 24 * 1024])
+def test_dump_outputs_keep_whole_segments_of_a_fixed_sample(tmp_path, monkeypatch, budget):
+    """--dump-outputs: xz rows are those of whole segments (all of them when they fit, else a seeded sample within DUMP_BYTES), indptr
+    in full; the same outputs give the same files, float32 / float64 only"""
+    import numpy as np
+    import torch
+    import bench
+    if budget is not None:
+        monkeypatch.setattr(bench, "DUMP_BYTES", budget)
+    lens = np.random.default_rng(3).integers(0, 40, 257)
+    indptr = torch.from_numpy(np.concatenate([[0], np.cumsum(lens)]))
+    xz = torch.randn(int(lens.sum()), 2, 4)
+    got = bench.step_outputs(xz, indptr)
+    assert {a.dtype for a in got.values()} <= {np.dtype(np.float32), np.dtype(np.float64)}
+    assert np.array_equal(got["indptr"], indptr.numpy())
+    segs = got["xz_segments"].astype(np.int64)
+    assert np.all(np.diff(segs) > 0)
+    want = torch.cat([xz[indptr[s]:indptr[s + 1]] for s in segs]).numpy()
+    assert np.array_equal(got["xz"], want)
+    assert sum(a.nbytes for a in got.values()) <= bench.DUMP_BYTES
+    if budget is None:
+        assert np.array_equal(segs, np.arange(lens.size))
+    else:
+        assert 0 < segs.size < lens.size
+    bench.write_outputs(str(tmp_path / "d"), got)
+    again = bench.step_outputs(xz, indptr)
+    for name, a in again.items():
+        assert np.array_equal(np.load(tmp_path / "d" / f"{name}.npy"), a)

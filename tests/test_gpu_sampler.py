@@ -505,10 +505,11 @@ def test_batched_registration_regrows_a_small_table_and_numbers_transient_batche
     assert np.array_equal(s2.enc_int16().cpu().numpy(), oenc2)
 
 
-def test_shfl_fallback_of_the_wave_reductions_gives_the_same_rows():
+def test_shfl_fallback_of_the_wave_reductions_gives_the_same_rows(tmp_path):
     """csrc/waveops.hpp: the DPP wave reductions are internals of ROCm's device library; should an update rename them, the
     Makefile's probe builds the __shfl forms instead (-DSG_NO_OCKL_WAVE_OPS).  That build is made here (walk_rows.hip only,
-    into /tmp) and the key-rows / fused-row parity tests are run through it in a child process."""
+    into this test's own directory: a library left by another tree is never picked up) and the key-rows / fused-row parity
+    tests are run through it in a child process."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -517,7 +518,7 @@ def test_shfl_fallback_of_the_wave_reductions_gives_the_same_rows():
         from ab import build_variant
     finally:
         sys.path.pop(0)
-    lib = build_variant("-DSG_NO_OCKL_WAVE_OPS", ["walk_rows.hip"])
+    lib = build_variant("-DSG_NO_OCKL_WAVE_OPS", ["walk_rows.hip"], out_dir=str(tmp_path))
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_gpu_sampler.py"),
                         os.path.join(root, "tests", "test_gpu_join.py"), "-x", "-q", "-k",
                         "key_rows_join_like or specialised_fused_row or batched_registration_numbers"],

@@ -1,15 +1,20 @@
-"""CPU, build container only: randomized sweep of the oracle (oracle/subgacc_oracle.c) against the REFERENCE ITSELF
-(oracle/_ref = /root/reference/subg_acc/subg_acc.c compiled by `make -C oracle ref`), beyond the 46 committed
-fixtures: random graphs (isolated nodes, star hubs, K2 components), random M / m / bucket / seeds / query shapes.
+"""CPU: randomized sweep of the oracle (oracle/subgacc_oracle.c) against the REFERENCE ITSELF (subg_acc/subg_acc.c), beyond the
+46 committed fixtures: random graphs (isolated nodes, star hubs, K2 components), random M / m / bucket / seeds / query shapes.
 
     gset_sampler  nthread=1 (the only reproducible setting, subg_acc.c:731-732)        subg_acc.c:649-1034
     walk_sampler  nthread 1..8, both first-hop modes                                   subg_acc.c:316-389
     walk_join     over walk_sampler's own output                                       subg_acc.c:509-647
-    batch_sampler seeded with seed + getpid() by the reference (:421): same process, so the sum is known   subg_acc.c:391-507
+    batch_sampler seeded with seed + getpid() by the reference (:421)                   subg_acc.c:391-507
 
-Skips cleanly where oracle/_ref does not exist (the GPU box may or may not carry it; nothing here needs a GPU).
-Every case has its own seeded stream: a failing case number reproduces alone."""
+The reference's outputs of every case are committed as SHA-256 digests (tests/golden/ref_sweep.npz; batch_sampler's with the
+seed + getpid() sum they were made with), so the sweep runs wherever the oracle builds.  Where the compiled reference exists
+(oracle/_ref, `make -C oracle ref`) each case is also compared with it array by array, and
+`PYTHONPATH=. python tests/test_oracle_vs_ref.py` re-makes the digests from it.  Every case has its own seeded stream: a failing
+case number reproduces alone."""
 import ctypes
+import functools
+import hashlib
+import os
 
 import numpy as np
 import pytest
@@ -17,9 +22,32 @@ import pytest
 import oracle
 
 ref = oracle.ref_module()
-pytestmark = pytest.mark.skipif(ref is None, reason="oracle/_ref not built (needs /root/reference; `make -C oracle ref`)")
+SWEEP = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_sweep.npz")
 
 CASES = 240
+
+
+def digest(arrays):
+    """SHA-256 over the shapes and int64 values of a case's outputs: equal digests <=> np.array_equal on every array"""
+    h = hashlib.sha256()
+    for a in arrays:
+        a = np.ascontiguousarray(np.asarray(a), dtype=np.int64)
+        h.update(repr(a.shape).encode() + a.tobytes())
+    return h.hexdigest()
+
+
+def check(kind, case, o, r, what):
+    """the oracle's outputs `o` against the reference's: `r` itself where it was computed here, and the committed digest"""
+    if r is not None:
+        for a, b in zip(o, r, strict=True):
+            assert np.array_equal(a, b), what
+    assert digest(o) == str(stored()[kind][case]), f"{what}: not the reference's output (committed digest)"
+
+
+@functools.lru_cache(maxsize=None)
+def stored():
+    with np.load(SWEEP) as z:
+        return {k: z[k] for k in z.files}
 
 
 def rand_graph(rng):
@@ -71,24 +99,80 @@ def mask_isolated(ptr, query, nsize, remap):
     return remap
 
 
+def gset_case(case):
+    """-> (what, the oracle's outputs, the reference's -- None without oracle/_ref)"""
+    rng = np.random.default_rng(10_000 + case)
+    ptr, idx = rand_graph(rng)
+    q = rand_query(rng, len(ptr) - 1)
+    M, m = rand_walk_params(rng)
+    bucket = int(rng.integers(2, M * m + 2)) if rng.random() < 0.3 else -1
+    seed = int(rng.integers(0, 2**31 - 1))
+    r = None
+    if ref is not None:
+        nsize, remap, enc, raw = ref.gset_sampler(ptr, idx, q, num_walks=M, num_steps=m, bucket=bucket, nthread=1,
+                                                  seed=seed, debug=1)
+        r = [nsize, mask_isolated(ptr, q, nsize, remap), enc, raw]
+    o = oracle.gset_sampler(ptr, idx, q, num_walks=M, num_steps=m, bucket=bucket, seed=seed, debug=True)
+    return f"case {case}: N={len(ptr) - 1} n={len(q)} M={M} m={m} bucket={bucket} seed={seed}", list(o[:4]), r
+
+
+def walk_case(case):
+    """-> (what, [(kind, the oracle's outputs, the reference's -- None without oracle/_ref)] for "walk" and "walkjoin")"""
+    rng = np.random.default_rng(20_000 + case)
+    ptr, idx = rand_graph(rng)
+    q = rand_query(rng, len(ptr) - 1).astype(np.int32)
+    M, m = rand_walk_params(rng)
+    T = int(rng.integers(1, 9))
+    rep = bool(rng.integers(0, 2))
+    seed = int(rng.integers(0, 2**31 - 1))
+    r_walk = None
+    if ref is not None:
+        walks, obj = ref.walk_sampler(ptr, idx, q, num_walks=M, num_steps=m, nthread=T, seed=seed, replacement=rep)
+        r_walk = [walks, [len(obj[i, 0]) for i in range(len(q))], np.concatenate([obj[i, 0] for i in range(len(q))]),
+                  np.concatenate([obj[i, 1] for i in range(len(q))])]
+    o_walk = list(oracle.walk_sampler(ptr, idx, q, num_walks=M, num_steps=m, nthread=T, seed=seed, replacement=rep))
+    what = f"case {case}: N={len(ptr) - 1} n={len(q)} M={M} m={m} T={T} rep={rep} seed={seed}"
+    # the legacy join over these walks (pairs of sampled roots, (u, u) included).  Distinct roots only: with a root
+    # repeated in `walk` the reference adds duplicate keys to a uthash table (HASH_ADD_INT, subg_acc.c:563) --
+    # which of them HASH_FIND returns flips with every bucket expansion (expansion re-chains a bucket in reverse),
+    # i.e. depends on how many other roots there are.  The goldens' small `dup` case (no expansion: the last row
+    # wins) is what the oracle and the HIP path implement; the reference's callers pass unique nodes.
+    walks, nsize, ids = (r_walk or o_walk)[:3]
+    keys = np.split(ids, np.cumsum(nsize)[:-1])
+    first = np.sort(np.unique(q, return_index=True)[1])
+    uq, uw, ukeys = q[first], walks[first], [keys[i] for i in first]
+    Q = int(rng.integers(1, 40))
+    pairs = uq[rng.integers(0, len(uq), (Q, 2))]
+    pairs[0] = (uq[0], uq[0])
+    r_join = list(ref.walk_join(uw, ukeys, pairs, nthread=1, return_idx=True)) if ref is not None else None
+    o_join = list(oracle.walk_join(uw, ukeys, pairs, return_idx=True))
+    return what, [("walk", o_walk, r_walk), ("walkjoin", o_join, r_join)]
+
+
+def batch_case(case):
+    """-> (what, the oracle's output for a given seed + getpid() sum, (the reference's output, the sum it started from) or None)"""
+    rng = np.random.default_rng(30_000 + case)
+    ptr, idx = rand_graph(rng)
+    N = len(ptr) - 1
+    q = rand_query(rng, N).astype(np.int32)
+    M = int(rng.integers(1, 60))
+    S = int(rng.integers(1, 10))
+    thld = int(rng.integers(1, 4 * N))
+    seed = int(rng.integers(0, 2**30))
+
+    def run(seed_eff):
+        return [oracle.batch_sampler(ptr, idx, q, num_walks=M, num_steps=S, thld=thld, seed_eff=seed_eff)]
+    live = None
+    if ref is not None:          # (this process: the sum the reference starts from is known)
+        live = [ref.batch_sampler(ptr, idx, q, num_walks=M, num_steps=S, thld=thld, seed=seed)], seed + os.getpid()
+    return f"case {case}: N={N} n={len(q)} M={M} S={S} thld={thld} seed={seed}", run, live
+
+
 @pytest.mark.parametrize("block", range(8))
 def test_gset_sampler_random_sweep(block, capfd):
     for case in range(block * CASES // 8, (block + 1) * CASES // 8):
-        rng = np.random.default_rng(10_000 + case)
-        ptr, idx = rand_graph(rng)
-        q = rand_query(rng, len(ptr) - 1)
-        M, m = rand_walk_params(rng)
-        bucket = int(rng.integers(2, M * m + 2)) if rng.random() < 0.3 else -1
-        seed = int(rng.integers(0, 2**31 - 1))
-        nsize, remap, enc, raw = ref.gset_sampler(ptr, idx, q, num_walks=M, num_steps=m, bucket=bucket, nthread=1,
-                                                  seed=seed, debug=1)
-        remap = mask_isolated(ptr, q, nsize, remap)
-        o = oracle.gset_sampler(ptr, idx, q, num_walks=M, num_steps=m, bucket=bucket, seed=seed, debug=True)
-        what = f"case {case}: N={len(ptr) - 1} n={len(q)} M={M} m={m} bucket={bucket} seed={seed}"
-        assert np.array_equal(o[0], nsize), what
-        assert np.array_equal(o[1], remap), what
-        assert np.array_equal(o[2], enc), what
-        assert np.array_equal(o[3], raw), what
+        what, o, r = gset_case(case)
+        check("gset", case, o, r, what)
     ctypes.CDLL(None).fflush(None)
     capfd.readouterr()        # the reference printf()s statistics
 
@@ -96,50 +180,31 @@ def test_gset_sampler_random_sweep(block, capfd):
 @pytest.mark.parametrize("block", range(8))
 def test_walk_sampler_and_walk_join_random_sweep(block, capfd):
     for case in range(block * CASES // 8, (block + 1) * CASES // 8):
-        rng = np.random.default_rng(20_000 + case)
-        ptr, idx = rand_graph(rng)
-        q = rand_query(rng, len(ptr) - 1).astype(np.int32)
-        M, m = rand_walk_params(rng)
-        T = int(rng.integers(1, 9))
-        rep = bool(rng.integers(0, 2))
-        seed = int(rng.integers(0, 2**31 - 1))
-        walks, obj = ref.walk_sampler(ptr, idx, q, num_walks=M, num_steps=m, nthread=T, seed=seed, replacement=rep)
-        ow, onsize, oids, ocounts = oracle.walk_sampler(ptr, idx, q, num_walks=M, num_steps=m, nthread=T, seed=seed,
-                                                        replacement=rep)
-        what = f"case {case}: N={len(ptr) - 1} n={len(q)} M={M} m={m} T={T} rep={rep} seed={seed}"
-        assert np.array_equal(ow, walks), what
-        assert np.array_equal(onsize, [len(obj[i, 0]) for i in range(len(q))]), what
-        assert np.array_equal(oids, np.concatenate([obj[i, 0] for i in range(len(q))])), what
-        assert np.array_equal(ocounts, np.concatenate([obj[i, 1] for i in range(len(q))])), what
-        # the legacy join over these walks (pairs of sampled roots, (u, u) included).  Distinct roots only: with a root
-        # repeated in `walk` the reference adds duplicate keys to a uthash table (HASH_ADD_INT, subg_acc.c:563) --
-        # which of them HASH_FIND returns flips with every bucket expansion (expansion re-chains a bucket in reverse),
-        # i.e. depends on how many other roots there are.  The goldens' small `dup` case (no expansion: the last row
-        # wins) is what the oracle and the HIP path implement; the reference's callers pass unique nodes.
-        first = np.sort(np.unique(q, return_index=True)[1])
-        uq, uw, ukeys = q[first], walks[first], [obj[i, 0] for i in first]
-        Q = int(rng.integers(1, 40))
-        pairs = uq[rng.integers(0, len(uq), (Q, 2))]
-        pairs[0] = (uq[0], uq[0])
-        out, xrow = ref.walk_join(uw, ukeys, pairs, nthread=1, return_idx=True)
-        oout, oxrow = oracle.walk_join(uw, ukeys, pairs, return_idx=True)
-        assert np.array_equal(oout, out) and np.array_equal(oxrow, xrow), what
+        what, parts = walk_case(case)
+        for kind, o, r in parts:
+            check(kind, case, o, r, what)
     ctypes.CDLL(None).fflush(None)
     capfd.readouterr()
 
 
 @pytest.mark.parametrize("block", range(4))
 def test_batch_sampler_random_sweep(block):
-    import os
     for case in range(block * CASES // 4, (block + 1) * CASES // 4):
-        rng = np.random.default_rng(30_000 + case)
-        ptr, idx = rand_graph(rng)
-        N = len(ptr) - 1
-        q = rand_query(rng, N).astype(np.int32)
-        M = int(rng.integers(1, 60))
-        S = int(rng.integers(1, 10))
-        thld = int(rng.integers(1, 4 * N))
-        seed = int(rng.integers(0, 2**30))
-        r = ref.batch_sampler(ptr, idx, q, num_walks=M, num_steps=S, thld=thld, seed=seed)
-        o = oracle.batch_sampler(ptr, idx, q, num_walks=M, num_steps=S, thld=thld, seed_eff=seed + os.getpid())
-        assert np.array_equal(o, r), f"case {case}: N={N} n={len(q)} M={M} S={S} thld={thld} seed={seed}"
+        what, run, live = batch_case(case)
+        if live is not None:
+            assert np.array_equal(run(live[1])[0], live[0][0]), what
+        check("batch", case, run(int(stored()["batch_seed_eff"][case])), None, what)
+
+
+if __name__ == "__main__":     # re-make the committed digests from the compiled reference
+    assert ref is not None, "needs oracle/_ref (`make -C oracle ref`)"
+    digests = {"gset": [], "walk": [], "walkjoin": [], "batch": []}
+    seed_eff = []
+    for case in range(CASES):
+        digests["gset"].append(digest(gset_case(case)[2]))
+        for kind, _, r in walk_case(case)[1]:
+            digests[kind].append(digest(r))
+        r, s = batch_case(case)[2]
+        digests["batch"].append(digest(r))
+        seed_eff.append(s)
+    np.savez_compressed(SWEEP, batch_seed_eff=np.array(seed_eff, np.int64), **{k: np.array(v) for k, v in digests.items()})

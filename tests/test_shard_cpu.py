@@ -1,6 +1,8 @@
 """CPU, world_size 2 over gloo: the multi-GPU sharding logic (contiguous root / pair ranges, merge of the
 per-rank LP-row tables) reproduces the single-process result exactly.  The per-rank compute is an
-oracle-backed stand-in here (no GPU in this container); on GPUs the same code runs over RCCL."""
+oracle-backed stand-in here (no GPU in this container); on GPUs the same code runs over RCCL.
+The ranks never open the GPU, wherever they run: their barrier is gloo's monitored_barrier(), since dist.barrier() asks torch for
+the accelerator, which initialises HIP in every rank on a machine with a GPU (eight ranks are more processes than may hold it)."""
 import os
 import types
 
@@ -45,7 +47,7 @@ def _worker(rank, world, port, out_dir):
     sets, gkeys, (lo, hi) = shard.sample_sets_sharded(oracle_sampler(g, M, m, 9), g["query"], rank, world)
     np.savez(os.path.join(out_dir, f"r{rank}.npz"), nsize=sets.nsize.numpy(), ids=sets.ids.numpy(), sf=sets.sf.numpy(),
              gkeys=gkeys.numpy(), lo=lo, hi=hi)
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
@@ -77,7 +79,7 @@ def _spg_worker(rank, world, port, out_dir):
     store = sum(t.numel() * t.element_size() for t in (row_off, ids, data)) + (row_off.numel() - 1) * sets.nsize.element_size()
     assert sum(allocated) == store, (sum(allocated), store)          # exactly the returned arrays (+ the gathered nsize): 1x
     np.savez(os.path.join(out_dir, f"spg{rank}.npz"), row_off=row_off.numpy(), ids=ids.numpy(), data=data.numpy())
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
@@ -227,7 +229,7 @@ def _device_worker(rank, world, port, same_device, backend_label, out_dir):
         code = ex.code
     with open(os.path.join(out_dir, f"code_{rank}"), "w") as f:
         f.write(str(code))
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 

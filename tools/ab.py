@@ -17,9 +17,11 @@ CSRC = os.path.join(ROOT, "surel_plus_amd", "csrc")
 FLAGS = "-O3 -std=c++17 -fPIC --offload-arch=gfx950 -fhip-fp32-correctly-rounded-divide-sqrt -ffp-contract=off".split()
 
 
-def build_variant(flags, files):
+def build_variant(flags, files, out_dir="/tmp"):
+    """-> path of the variant library, built into out_dir unless it is there already (the name hashes the flags and files, not the
+    sources: a caller that must test THIS tree's sources passes an out_dir of its own)"""
     tag = hashlib.sha1((flags + "|" + ",".join(files)).encode()).hexdigest()[:10]
-    out = f"/tmp/libsubgacc_{tag}.so"
+    out = os.path.join(out_dir, f"libsubgacc_{tag}.so")
     if os.path.exists(out):
         return out
     objs = [os.path.join(CSRC, "build", f) for f in os.listdir(os.path.join(CSRC, "build"))
@@ -27,7 +29,7 @@ def build_variant(flags, files):
     procs = []
     hooks = ["-include", os.path.join(ROOT, "tools", "dev_hooks.hpp")] if any(k in flags for k in ("SG_EXPERIMENT", "SJ_EXPERIMENT", "SG_STOP_AFTER")) else []
     for f in files:
-        o = f"/tmp/{tag}_{f[:-4]}.o"
+        o = os.path.join(out_dir, f"{tag}_{f[:-4]}.o")
         procs.append((o, subprocess.Popen(["/opt/rocm/bin/hipcc"] + FLAGS + hooks + flags.split() + ["-c", os.path.join(CSRC, f), "-o", o])))
         objs.append(o)
     for o, p in procs:
