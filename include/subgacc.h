@@ -557,6 +557,32 @@ size_t subgacc_worklist_workspace_bytes(int64_t n);
 int subgacc_worklist_by_root(const int32_t *roots, int64_t n, int64_t num_nodes, int32_t *worklist, int64_t *n_work,
                              void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Graph-locality order (ABI 7, backward compatible additions).  The reference walks its roots in whatever order its loop takes
+ * them (subg_acc.c:742-745) and nothing observable depends on that order: Philox keys a walk by (seed, root id, walk, hop), the
+ * list-order walk entry points keep every row's rand_r stream position, and every row is written at its own index.  So the order
+ * is free to serve the L2: roots of the same community walked at the same time share their lines.  subgacc_worklist_by_root
+ * gets that only where ids carry locality; these two entry points build an order that does not rely on the ids.
+ *
+ * subgacc_locality_round: ONE round of a deterministic label propagation over the CSR, labels_in -> labels_out (int32 [num_nodes]
+ * each, distinct buffers; start from label[v] = v).  Node v updates in round `round` iff (mix32(v) & 1) == (round & 1), where
+ *     mix32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16   (uint32, mod 2^32);
+ * every other node copies its label.  An updating node with deg > 0 reads the labels of min(deg, cap) neighbours -- all of them if
+ * deg <= cap, else those at positions j*deg/cap (64-bit integer arithmetic), j < cap -- and its own label once more; the new label
+ * is the most frequent of these, ties to the smallest.  deg == 0: the label stays.  1 <= cap <= 64, round >= 0, num_nodes < 2^31;
+ * SUBGACC_ERR_BADARG otherwise (checked before anything is launched).  Sorting the nodes by (final label, id) gives the order
+ * (surel_plus_amd.sampler.locality_order; 8 rounds, cap = 64 by default).
+ *
+ * subgacc_worklist_by_rank: subgacc_worklist_by_root keyed by rank[root] instead of the root's id (rank: int32 [num_nodes] on the
+ * device, e.g. the position of the node in that order): 1,024 buckets of consecutive ranks, any order inside a bucket; rows whose
+ * root is SUBGACC_NO_ROOT are left out, a root outside [0, num_nodes) goes to the last bucket.  Same workspace contract as
+ * subgacc_worklist_by_root (zeroed once by its owner, left zeroed by every call).
+ * ------------------------------------------------------------------------------------------- */
+int subgacc_locality_round(const void *indptr, int32_t indptr64, const int32_t *indices, int64_t num_nodes,
+                           const int32_t *labels_in, int32_t *labels_out, int32_t round, int32_t cap, void *stream);
+int subgacc_worklist_by_rank(const int32_t *roots, int64_t n, const int32_t *rank, int64_t num_nodes, int32_t *worklist,
+                             int64_t *n_work, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,7 @@ SYMBOLS = (
     "subgacc_hop_records_format", "subgacc_hop_records_build", "subgacc_step_dedup_workspace_bytes",
     "subgacc_step_prologue_dedup", "subgacc_walk_spg_sparse",
     "subgacc_keyrows_register", "subgacc_keyrows_cand_capacity", "subgacc_walk_tags", "subgacc_keyrows_compact", "subgacc_keyrows_translate", "subgacc_rng_replay", "subgacc_walk_keyrows64", "subgacc_worklist_workspace_bytes", "subgacc_worklist_by_root", "subgacc_walk_spg_list",
+    "subgacc_locality_round", "subgacc_worklist_by_rank",
     "subgacc_sjoin_fill_v2", "subgacc_publish_words", "subgacc_rows_to_headed",
 )
 
@@ -149,6 +150,8 @@ def lib():
     sig["subgacc_rng_replay"] = (C.c_int, [cfgp, vp, vp, i64, vp, i64, i32, u64, vp, vp, vp, vp])
     sig["subgacc_worklist_workspace_bytes"] = (sz, [i64])
     sig["subgacc_worklist_by_root"] = (C.c_int, [vp, i64, i64, vp, vp, vp, sz, vp])
+    sig["subgacc_worklist_by_rank"] = (C.c_int, [vp, i64, vp, i64, vp, vp, vp, sz, vp])
+    sig["subgacc_locality_round"] = (C.c_int, [vp, i32, vp, i64, vp, vp, i32, i32, vp])
     sig["subgacc_walk_spg_list"] = (C.c_int, [cfgp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp])
     sig["subgacc_sjoin_fill_v2"] = (C.c_int, [C.POINTER(JoinDesc), vp])
     sig["subgacc_publish_words"] = (C.c_int, [vp, i64, vp, vp])

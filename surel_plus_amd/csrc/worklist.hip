@@ -18,6 +18,8 @@
 // The totals are zeroed again by the last block of `place` to finish (a completion counter), so a call leaves the workspace as it
 // found it: zeroed ONCE by its owner before the first call.  (The first form of this file kept per-block histograms in HBM and made
 // every block of the second launch sum 32 of them per bucket: 7 + 18 us for 131,072 rows; this one 4 + 5.)
+// subgacc_worklist_by_rank is the same pass keyed by rank[root] (a locality order of the nodes, csrc/locality.hip): the RANK
+// instantiation of both kernels; by_root keeps its own.
 #include "common.hpp"
 #include "blockscan.hpp"
 
@@ -32,7 +34,17 @@ __device__ __forceinline__ int wl_bucket(int32_t root, int shift) {
     return (int)(b < (uint32_t)kWlBuckets ? b : (uint32_t)kWlBuckets - 1u);
 }
 
+// the bucket of a row: by its root's id, or (RANK: subgacc_worklist_by_rank) by rank[root] -- a root outside [0, num_nodes) goes to the
+// last bucket either way, and so does a rank outside [0, 2^31)
+template <bool RANK>
+__device__ __forceinline__ int wl_key(int32_t root, const int32_t *__restrict__ rank, int64_t num_nodes, int shift) {
+    if (!RANK) return wl_bucket(root, shift);
+    return (uint32_t)root < (uint64_t)num_nodes ? wl_bucket(rank[root], shift) : kWlBuckets - 1;
+}
+
+template <bool RANK>
 __global__ __launch_bounds__(kWlThreads) void worklist_count_kernel(const int32_t *__restrict__ roots, int64_t n, int shift,
+                                                                    const int32_t *__restrict__ rank, int64_t num_nodes,
                                                                     int32_t *__restrict__ totals, int32_t *__restrict__ place) {
     __shared__ int32_t h[kWlBuckets];
     for (int b = threadIdx.x; b < kWlBuckets; b += kWlThreads) h[b] = 0;
@@ -46,7 +58,7 @@ __global__ __launch_bounds__(kWlThreads) void worklist_count_kernel(const int32_
         if (i < n) {
             const int32_t r = roots[i];
             if (r != SUBGACC_NO_ROOT) {      // a repeated endpoint's empty row is not listed
-                bk[k] = wl_bucket(r, shift);
+                bk[k] = wl_key<RANK>(r, rank, num_nodes, shift);
                 li[k] = atomicAdd(&h[bk[k]], 1);
             }
         }
@@ -69,7 +81,9 @@ __global__ __launch_bounds__(kWlThreads) void worklist_count_kernel(const int32_
     }
 }
 
+template <bool RANK>
 __global__ __launch_bounds__(kWlThreads) void worklist_place_kernel(const int32_t *__restrict__ roots, int64_t n, int shift,
+                                                                    const int32_t *__restrict__ rank, int64_t num_nodes,
                                                                     int32_t *__restrict__ totals, const int32_t *__restrict__ place,
                                                                     int32_t *__restrict__ done, int32_t *__restrict__ worklist,
                                                                     int64_t *__restrict__ n_work) {
@@ -103,7 +117,7 @@ __global__ __launch_bounds__(kWlThreads) void worklist_place_kernel(const int32_
 #pragma unroll
     for (int k = 0; k < kWlItems; ++k) {
         const int64_t i = base + (int64_t)k * kWlThreads + threadIdx.x;
-        if (rt[k] != SUBGACC_NO_ROOT) worklist[off[wl_bucket(rt[k], shift)] + pl[k]] = (int32_t)i;
+        if (rt[k] != SUBGACC_NO_ROOT) worklist[off[wl_key<RANK>(rt[k], rank, num_nodes, shift)] + pl[k]] = (int32_t)i;
     }
     // the last block to get here zeroes the totals for the next call (every block has READ them by then -- the scan above needed
     // their values -- and that is all the order this needs: no fence, which on this chip is an L2 write-back per block)
@@ -125,25 +139,44 @@ extern "C" size_t subgacc_worklist_workspace_bytes(int64_t n) {
     return (size_t)kWlHead + (size_t)kWlBuckets * 4 + (size_t)(n > 0 ? n : 1) * 4;
 }
 
-extern "C" int subgacc_worklist_by_root(const int32_t *roots, int64_t n, int64_t num_nodes, int32_t *worklist, int64_t *n_work,
-                                        void *workspace, size_t workspace_bytes, void *stream) {
-    SG_REQUIRE(n >= 0 && n < (1ll << 31) && num_nodes >= 0 && n_work, SUBGACC_ERR_BADARG, "worklist_by_root: bad arguments");
+static int worklist_launch(const int32_t *roots, int64_t n, const int32_t *rank, int64_t num_nodes, int32_t *worklist,
+                           int64_t *n_work, void *workspace, size_t workspace_bytes, void *stream, const char *name) {
+    SG_REQUIRE(n >= 0 && n < (1ll << 31) && num_nodes >= 0 && n_work, SUBGACC_ERR_BADARG, "%s: bad arguments", name);
     hipStream_t s = (hipStream_t)stream;
     if (n == 0) {
         SG_CHECK_HIP(hipMemsetAsync(n_work, 0, 8, s));
         return SUBGACC_OK;
     }
-    SG_REQUIRE(roots && worklist, SUBGACC_ERR_BADARG, "worklist_by_root: null argument");
-    SG_REQUIRE(workspace && workspace_bytes >= subgacc_worklist_workspace_bytes(n), SUBGACC_ERR_WORKSPACE, "worklist_by_root: workspace too small");
+    SG_REQUIRE(roots && worklist, SUBGACC_ERR_BADARG, "%s: null argument", name);
+    SG_REQUIRE(workspace && workspace_bytes >= subgacc_worklist_workspace_bytes(n), SUBGACC_ERR_WORKSPACE, "%s: workspace too small", name);
     const int nblk = (int)ceil_div(n, kWlTile);
     int shift = 0;
     while (((num_nodes > 0 ? num_nodes - 1 : 0) >> shift) >= kWlBuckets) ++shift;
     int32_t *done = (int32_t *)workspace;
     int32_t *totals = (int32_t *)((char *)workspace + kWlHead);
     int32_t *place = totals + kWlBuckets;
-    hipLaunchKernelGGL(worklist_count_kernel, dim3(nblk), dim3(kWlThreads), 0, s, roots, n, shift, totals, place);
-    hipLaunchKernelGGL(worklist_place_kernel, dim3(nblk), dim3(kWlThreads), 0, s, roots, n, shift, totals, (const int32_t *)place, done,
-                       worklist, n_work);
+    if (rank) {
+        hipLaunchKernelGGL(worklist_count_kernel<true>, dim3(nblk), dim3(kWlThreads), 0, s, roots, n, shift, rank, num_nodes, totals, place);
+        hipLaunchKernelGGL(worklist_place_kernel<true>, dim3(nblk), dim3(kWlThreads), 0, s, roots, n, shift, rank, num_nodes, totals,
+                           (const int32_t *)place, done, worklist, n_work);
+    } else {
+        hipLaunchKernelGGL(worklist_count_kernel<false>, dim3(nblk), dim3(kWlThreads), 0, s, roots, n, shift, rank, num_nodes, totals, place);
+        hipLaunchKernelGGL(worklist_place_kernel<false>, dim3(nblk), dim3(kWlThreads), 0, s, roots, n, shift, rank, num_nodes, totals,
+                           (const int32_t *)place, done, worklist, n_work);
+    }
     SG_LAUNCH_CHECK();
     return SUBGACC_OK;
+}
+
+extern "C" int subgacc_worklist_by_root(const int32_t *roots, int64_t n, int64_t num_nodes, int32_t *worklist, int64_t *n_work,
+                                        void *workspace, size_t workspace_bytes, void *stream) {
+    return worklist_launch(roots, n, nullptr, num_nodes, worklist, n_work, workspace, workspace_bytes, stream, "worklist_by_root");
+}
+
+extern "C" int subgacc_worklist_by_rank(const int32_t *roots, int64_t n, const int32_t *rank, int64_t num_nodes, int32_t *worklist,
+                                        int64_t *n_work, void *workspace, size_t workspace_bytes, void *stream) {
+    SG_REQUIRE(rank || num_nodes == 0, SUBGACC_ERR_BADARG, "worklist_by_rank: null rank");
+    SG_REQUIRE(num_nodes < (1ll << 31), SUBGACC_ERR_BADARG, "worklist_by_rank: num_nodes >= 2^31");
+    return worklist_launch(roots, n, rank ? rank : roots, num_nodes, worklist, n_work, workspace, workspace_bytes, stream,
+                           "worklist_by_rank");
 }

@@ -183,23 +183,34 @@ def symmetric_powerlaw_graph_big(N, avg_deg, seed=3, exponent=2.2, device="cuda"
     return DeviceCSR(indptr, indices, torch.device(device))
 
 
-def degree_ordered(csr):
-    """The same graph with its nodes renumbered by descending degree (dev experiment: does a hub-first placement of the
-    row pointers raise the walk's L2 hit rate?).  Returns (DeviceCSR, perm) with perm[new id] = old id; rows keep their
-    neighbour order (renumbered, not re-sorted)."""
+def relabeled(csr, perm):
+    """The same graph with node perm[i] renamed i (perm: a permutation of the node ids, perm[new id] = old id): row i of the result is
+    row perm[i] of `csr`, its neighbours renamed and kept in their order (not re-sorted).  Row offsets keep their dtype.  With a random
+    perm this takes the id locality out of a graph (tools/locality_ab.py: cit2loc with its communities scattered)."""
     ip = csr.indptr.long()
     N = csr.num_nodes
-    deg = ip[1:] - ip[:-1]
-    perm = torch.argsort(deg, descending=True, stable=True)
+    perm = torch.as_tensor(perm, device=ip.device).long()
+    if perm.shape != (N,):
+        raise ValueError(f"relabeled: perm must hold {N} ids")
     rank = torch.empty_like(perm)
     rank[perm] = torch.arange(N, device=perm.device)
+    deg = ip[1:] - ip[:-1]
     ndeg = deg[perm]
     nip = torch.zeros(N + 1, dtype=torch.int64, device=perm.device)
     nip[1:] = torch.cumsum(ndeg, 0)
     row = torch.repeat_interleave(torch.arange(N, device=perm.device), ndeg)
     old_e = ip[perm][row] + (torch.arange(csr.nnz, device=perm.device) - nip[row])
     nidx = rank[csr.indices[old_e].long()].to(torch.int32)
-    return DeviceCSR(nip.to(csr.indptr.dtype), nidx, csr.device), perm
+    return DeviceCSR(nip.to(csr.indptr.dtype), nidx, csr.device)
+
+
+def degree_ordered(csr):
+    """The same graph with its nodes renumbered by descending degree (dev experiment: does a hub-first placement of the
+    row pointers raise the walk's L2 hit rate?).  Returns (DeviceCSR, perm) with perm[new id] = old id; rows keep their
+    neighbour order (renumbered, not re-sorted)."""
+    ip = csr.indptr.long()
+    perm = torch.argsort(ip[1:] - ip[:-1], descending=True, stable=True)
+    return relabeled(csr, perm), perm
 
 
 def preset_graph(name, device="cuda", scale=1.0):

@@ -230,6 +230,8 @@ class SampledSets:
     _pending: tuple = None       # prefetch(): (pinned host copy of status, event, device source)
     extra: list = None           # values of prefetch(extra=...) once resolved
     _tail: torch.Tensor = None   # StepBuffers form: int64 [5] = [rows of the join (= members), status words x4], contiguous
+    walk_order: str = None       # the order the walk kernel took the rows in: "rank" (a locality order, subgacc_worklist_by_rank or
+                                 # the order itself), "id" (subgacc_worklist_by_root), "batch" (the order of the query); never observable
     #                              ([6] with root dedup: + the number of distinct roots = rows that were sampled)
     n_distinct: int = None       # StepBuffers(dedup_roots=True): so many rows (the first occurrences of the endpoints) hold sets
     keyrows: bool = False        # strided rows whose payload (`slot`) is the member's LP key: no table, no numbering
@@ -481,6 +483,67 @@ class SampledSets:
         return out
 
 
+@dataclass
+class LocalityOrder:
+    """An order of the nodes that puts the members of a graph community next to each other (locality_order()): rank[v] = position
+    of node v, order[k] = the node at position k (int32 [num_nodes] each, on the graph's device), labels = the final labels of the
+    label propagation (order sorts the nodes by (label, id)).  Passed as `order=` / `root_order=`, it changes the order in which the
+    walk kernel takes the rows and nothing else."""
+    rank: torch.Tensor
+    order: torch.Tensor
+    labels: torch.Tensor
+    num_nodes: int
+
+
+def locality_order(csr, rounds=8, cap=64):
+    """A locality order of the nodes of `csr`, built on the device: `rounds` rounds of label propagation (subgacc_locality_round,
+    csrc/locality.hip: half of the nodes update per round, each to the most frequent label among min(deg, cap) of its neighbours and
+    itself), then one stable sort by (label, id).  Deterministic: the same graph gives the same order, call after call."""
+    L, st = lib(), stream_ptr()
+    rounds, cap, N = int(rounds), int(cap), csr.num_nodes
+    if rounds < 0 or not 1 <= cap <= 64:
+        raise ValueError("locality_order: rounds >= 0 and 1 <= cap <= 64")
+    a = torch.arange(N, dtype=torch.int32, device=csr.device)
+    b = torch.empty_like(a)
+    for t in range(rounds):
+        check(L.subgacc_locality_round(ptr(csr.indptr), 1 if csr.indptr64 else 0, ptr(csr.indices), N, ptr(a), ptr(b), t, cap, st))
+        a, b = b, a
+    order = torch.sort(a, stable=True).indices.to(torch.int32)
+    rank = torch.empty_like(order)
+    rank[order.long()] = torch.arange(N, dtype=torch.int32, device=csr.device)
+    return LocalityOrder(rank, order, a, N)
+
+
+def as_rank(csr, order):
+    """`order=` as the walk paths take it: None, or a LocalityOrder (an int32 rank [num_nodes] on the graph's device is wrapped into
+    one without `order`/`labels`).  Anything else -- or an order of another graph size -- raises ValueError."""
+    if order is None:
+        return None
+    if isinstance(order, LocalityOrder):
+        rank = order.rank
+        if order.num_nodes != csr.num_nodes:
+            raise ValueError(f"order= was built for {order.num_nodes} nodes, the graph has {csr.num_nodes}")
+    elif torch.is_tensor(order):
+        rank = order
+    else:
+        raise ValueError("order= must be a LocalityOrder (locality_order()) or an int32 rank tensor")
+    if rank.dtype != torch.int32 or rank.dim() != 1 or rank.numel() != csr.num_nodes or rank.device != csr.device \
+            or not rank.is_contiguous():
+        raise ValueError(f"order=: the rank must be a contiguous int32 [{csr.num_nodes}] tensor on {csr.device}")
+    return order if isinstance(order, LocalityOrder) else LocalityOrder(rank, None, None, csr.num_nodes)
+
+
+def _is_all_nodes(query, num_nodes):
+    """is `query` -- as the caller handed it over -- every node in id order (the offline stage, main.py:172-178)?  Answered on the
+    host for host arrays; a device tensor is not read back for it (such a call takes subgacc_worklist_by_rank)."""
+    if torch.is_tensor(query):
+        if query.is_cuda or query.numel() != num_nodes:
+            return False
+        query = query.numpy()
+    q = np.asarray(query)
+    return q.ndim == 1 and q.size == num_nodes and bool(np.array_equal(q, np.arange(num_nodes)))
+
+
 def make_cfg(csr, num_walks, num_steps, bucket=-1, seed=111413, rng="rand_r", first_hop_wo=True,
              order=_lib.ORDER_WALK_MAJOR, cap_root_degree=True, emit_walks=False, records=True, row_pitch=0):
     """records=True: hand the graph's hop records (DeviceCSR.hop_records(), built on first use) to the kernel -- only the
@@ -593,7 +656,7 @@ def sample_sets(csr, query, num_walks=100, num_steps=3, bucket=-1, seed=111413, 
                 order=_lib.ORDER_WALK_MAJOR, cap_root_degree=True, emit_walks=False, rng_streams=1,
                 calls_before=0, dedup=True, keep_keys=None, staging_bytes=None, uniq_capacity=UNIQ_CAPACITY,
                 uniq_small_limit=0, fused_rows=False, lazy=False, strided=False, number_rows=True, key_rows=True,
-                walk_replay=False, batched_registration=True, sort_roots=True, rng_state=None):
+                walk_replay=False, batched_registration=True, sort_roots=True, rng_state=None, root_order=None):
     """Run the sampler for `query` (roots) on the GPU.  See SampledSets.
 
     rng_state=(rng_pos, rng_seed): the rand_r stream positions of the roots, already computed (a batch that is sampled a second
@@ -612,12 +675,21 @@ def sample_sets(csr, query, num_walks=100, num_steps=3, bucket=-1, seed=111413, 
     (spg.StridedSpG); no packed copy, no row offsets.  With fused_rows the walk kernel emits them itself
     (subgacc_walk_spg); without, the general walk kernel is followed by subgacc_finish_rows (the faster pair for short
     walks over a cache-resident graph, spg.prefers_fused).  number_rows=False (strided only): the distinct LP rows are not numbered either until somebody
-    asks (SampledSets.number()); the join by table slot needs no numbering."""
+    asks (SampledSets.number()); the join by table slot needs no numbering.
+
+    root_order = a LocalityOrder (locality_order()) or an int32 rank [num_nodes] on the device: the fused-row kernel takes the rows
+    in ascending rank of their root (subgacc_worklist_by_rank; the query over all nodes in id order walks the order itself) instead
+    of ascending id -- the rows, and everything computed from them, are the same.  (`order` is the reference's first-visit order.)
+    sets.walk_order says which order ran."""
+    root_order = as_rank(csr, root_order)
     p = types.SimpleNamespace(**locals())
     if not _plan_sets(p):              # shapes, kernel form, chunking, the rand_r stream positions, the table of distinct rows
         return None
     res = _launch_sets(p)              # per chunk: walk -> sizes -> (finish rows | register | number) -> packed copy
-    return _finish_sets(p) if res is _PACKED else res       # packed forms: global row offsets, numbering of the distinct LP rows
+    res = _finish_sets(p) if res is _PACKED else res        # packed forms: global row offsets, numbering of the distinct LP rows
+    if res is not None and res.walk_order is None:
+        res.walk_order = p.walk_order
+    return res
 
 
 _PACKED = object()      # _launch_sets: the chunks were packed, _finish_sets takes over (the strided forms return their sets themselves)
@@ -632,6 +704,7 @@ def _plan_sets(p):
     p.q = _as_query(p.query, p.dev)
     p.n = p.q.numel()
     p.walk_replay = bool(p.walk_replay and p.rng == "rand_r")
+    p.walk_order = "batch"
     p.records = bool(p.fused_rows) and p.bucket <= 0 and p.num_walks * p.num_steps + 1 <= FUSED_MAX_Q and 2 <= p.num_steps <= 4 and not p.walk_replay
     p.cfg = make_cfg(p.csr, p.num_walks, p.num_steps, p.bucket, p.seed, p.rng, p.first_hop_wo, p.order, p.cap_root_degree, p.emit_walks, p.records)
     check(p.L.subgacc_key_shift(p.cfg.num_walks, p.cfg.num_steps))   # AssertionError like subg_acc.c:911-915
@@ -716,22 +789,36 @@ def _launch_sets(p):
         # a BATCH sampled in one chunk walks its rows in ascending order of root id, like the buffered step (csrc/worklist.hip:
         # repeated and neighbouring roots share their lines in L2; the rows stay where they are).  Beyond a million roots the call
         # is the offline stage over a whole graph, whose nodes come in order already (listing them again cost it 1.5 %).
-        p.by_root = (p.fused_rows and p.chunk == p.n and SORT_ROOTS_MIN <= p.cn <= SORT_ROOTS_MAX and p.sort_roots and p.walk_pos is None and
-                   rows_kernel_takes(p.M, p.m, p.bucket))
-        if p.by_root:
+        # with a locality order (root_order) every single-chunk call the fused-row kernel serves takes the list, whatever its size: a
+        # batch in ascending rank of its roots (subgacc_worklist_by_rank), the offline stage over all nodes in id order walks the order
+        # itself.  A chunked call walks each chunk in query order (the list kernels take one chunk holding every row).
+        p.by_rank = (p.root_order is not None and p.fused_rows and p.chunk == p.n and p.walk_pos is None and
+                     rows_kernel_takes(p.M, p.m, p.bucket))
+        p.by_root = (not p.by_rank and p.fused_rows and p.chunk == p.n and SORT_ROOTS_MIN <= p.cn <= SORT_ROOTS_MAX and p.sort_roots and
+                   p.walk_pos is None and rows_kernel_takes(p.M, p.m, p.bucket))
+        p.walk_order = "rank" if p.by_rank else "id" if p.by_root else "batch"
+        if p.by_rank and p.root_order.order is not None and _is_all_nodes(p.query, p.csr.num_nodes):
+            p.wl = p.root_order.order
+            p.nwl = torch.full((1,), p.cn, dtype=torch.int64, device=p.dev)
+        elif p.by_root or p.by_rank:
             p.wl = torch.empty(p.cn, dtype=torch.int32, device=p.dev)
             p.nwl = torch.zeros(1, dtype=torch.int64, device=p.dev)
             p.wws = torch.zeros(p.L.subgacc_worklist_workspace_bytes(p.cn), dtype=torch.uint8, device=p.dev)
             p.nsize.zero_()           # (a row that is not listed -- a root equal to SUBGACC_NO_ROOT -- reads as an empty set)
-            check(p.L.subgacc_worklist_by_root(ptr(p.q), p.cn, p.csr.num_nodes, ptr(p.wl), ptr(p.nwl), ptr(p.wws), p.wws.numel(), p.st))
+            if p.by_rank:
+                check(p.L.subgacc_worklist_by_rank(ptr(p.q), p.cn, ptr(p.root_order.rank), p.csr.num_nodes, ptr(p.wl), ptr(p.nwl),
+                                                   ptr(p.wws), p.wws.numel(), p.st))
+            else:
+                check(p.L.subgacc_worklist_by_root(ptr(p.q), p.cn, p.csr.num_nodes, ptr(p.wl), ptr(p.nwl), ptr(p.wws), p.wws.numel(), p.st))
+        p.listed = p.by_root or p.by_rank
         with _timed("walk_sets"):
             if p.kform == 64:       # rows of 64-bit LP keys (4 hops, M >= 128): one chunk, optionally in work-list order
                 check(p.L.subgacc_walk_keyrows64(p.cfg, ptr(p.csr.indptr), ptr(p.csr.indices), p.csr.num_nodes, ptr(p.q), p.cn,
                                                ptr(p.rng_pos) if p.rng_pos is not None else None,
                                                ptr(p.rng_seed) if p.rng_seed is not None else None,
-                                               ptr(p.wl) if p.by_root else None, ptr(p.nwl) if p.by_root else None,
+                                               ptr(p.wl) if p.listed else None, ptr(p.nwl) if p.listed else None,
                                                ptr(p.st_ids), ptr(p.st_aux), ptr(p.nsize), ptr(p.flags), p.st))
-            elif p.by_root:
+            elif p.listed:
                 check(p.L.subgacc_walk_spg_list(p.cfg, ptr(p.csr.indptr), ptr(p.csr.indices), p.csr.num_nodes, ptr(p.q), p.cn,
                                               ptr(p.rng_pos) if p.rng_pos is not None else None,
                                               ptr(p.rng_seed) if p.rng_seed is not None else None, ptr(p.wl), ptr(p.nwl),
@@ -801,7 +888,7 @@ def _launch_sets(p):
                                        p.cap_root_degree, p.emit_walks, p.rng_streams, p.calls_before, p.dedup, p.keep_keys,
                                        p.staging_bytes, p.uniq_capacity * 4, p.uniq_small_limit, p.fused_rows, p.lazy, p.strided,
                                        p.number_rows, key_rows=p.key_rows_arg, walk_replay=p.walk_replay,
-                                       batched_registration=p.batched_registration, sort_roots=p.sort_roots, rng_state=p.rng_state)
+                                       batched_registration=p.batched_registration, sort_roots=p.sort_roots, rng_state=p.rng_state, root_order=p.root_order)
                 if p.st_host[4] > p.max_unique:       # more distinct rows than the direct ranking numbers: the caller
                     return None                   # (sample_spg) falls through to the packed forms
                 p.sets.resolve()
@@ -898,7 +985,7 @@ def _finish_sets(p):
         return sample_sets(p.csr, p.q, p.num_walks, p.num_steps, p.bucket, p.seed, p.rng, p.first_hop_wo, p.order, p.cap_root_degree,
                            p.emit_walks, p.rng_streams, p.calls_before, p.dedup, p.keep_keys, p.staging_bytes, p.uniq_capacity * 4,
                            p.uniq_small_limit, p.fused_rows, p.lazy, p.strided, p.number_rows, key_rows=p.key_rows_arg, walk_replay=p.walk_replay,
-                           batched_registration=p.batched_registration, sort_roots=p.sort_roots, rng_state=p.rng_state)
+                           batched_registration=p.batched_registration, sort_roots=p.sort_roots, rng_state=p.rng_state, root_order=p.root_order)
     p.sets.resolve()
     p.sets.ukeys = p.sets.ukeys.clone()
     return p.sets

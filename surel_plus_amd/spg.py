@@ -284,7 +284,7 @@ def prefers_fused(csr, hops):
 
 
 def sample_spg(csr, query, num_walks=200, num_steps=3, seed=111413, rng="rand_r", bucket=-1, fused=None, lazy=False,
-               strided=False, **kw):
+               strided=False, *, order=None, **kw):
     """sample -> SpG on the GPU: (SpG, SampledSets) -- the sets carry ukeys / nsize / feature_table().
 
     `num_steps` = walk hops (gset_sampler's meaning).  fused=True lets the walk kernel emit finished SpG rows
@@ -296,8 +296,12 @@ def sample_spg(csr, query, num_walks=200, num_steps=3, seed=111413, rng="rand_r"
     sampler.RANK_LIMIT distinct rows): resolve() raises SubgAccError then and the batch is sampled again with
     lazy=False, which regrows the table / takes the packed path on its own (a serving loop: catch, re-run that batch).
     strided=True: for a batch that is sampled, joined and dropped -- returns a StridedSpG (no packed copy of the rows):
-    the fused-row walk kernel's output, or the general walk kernel's sets finished in place (subgacc_finish_rows)."""
+    the fused-row walk kernel's output, or the general walk kernel's sets finished in place (subgacc_finish_rows).
+    order=LocalityOrder (sampler.locality_order) or an int32 rank: the walk kernel takes the roots in that order
+    (sample_sets(root_order=)); the result does not change."""
     sets = None
+    if order is not None:
+        kw["root_order"] = order
     if fused is None:
         fused = prefers_fused(csr, num_steps)
     if strided:     # transient batch: rows stay in the walk kernel's staging layout (falls through when it does not apply)
@@ -315,7 +319,7 @@ def sample_spg(csr, query, num_walks=200, num_steps=3, seed=111413, rng="rand_r"
     return SpG.from_sets(sets, n_cols=csr.num_nodes), sets
 
 
-def subg_matrix(G, train_idx, num_walks=200, num_steps=4, seed=111413, rng="rand_r", device=None, fused=None):
+def subg_matrix(G, train_idx, num_walks=200, num_steps=4, seed=111413, rng="rand_r", device=None, fused=None, *, order=None):
     """Drop-in for sampler/random_walks.py:74-82: returns (z, enc).
 
     z   -- SpG on the GPU (row i = sampled set of train_idx[i]); the reference indexes rows by node id and
@@ -323,11 +327,13 @@ def subg_matrix(G, train_idx, num_walks=200, num_steps=4, seed=111413, rng="rand
     enc -- numpy int16 [c+1, num_steps] with the all-zero row 0, exactly what the reference returns, so
            `torch.from_numpy(xpe).to(device).float() / num_walks` (main.py:174) keeps working.
     `num_steps` is the CLI value: the walks have num_steps-1 hops (random_walks.py:78).
+    order=LocalityOrder (sampler.locality_order): the walk kernel takes the roots in that order (over all nodes: the order itself
+    is the work list); z and enc do not change.
     """
     if _lib.VERBOSE:
         print(f'Start sampling for #{len(train_idx)} nodes with {num_walks} {num_steps}-step walks')
     csr = G if isinstance(G, DeviceCSR) else DeviceCSR(G.indptr, G.indices, device)
-    z, sets = sample_spg(csr, train_idx, num_walks=num_walks, num_steps=num_steps - 1, seed=seed, rng=rng, fused=fused)
+    z, sets = sample_spg(csr, train_idx, num_walks=num_walks, num_steps=num_steps - 1, seed=seed, rng=rng, fused=fused, order=order)
     enc = sets.enc_int16().cpu().numpy()
     enc = np.insert(enc, 0, np.zeros((1, num_steps), dtype=enc.dtype), axis=0)
     z.sets = sets

@@ -569,12 +569,19 @@ class StepBuffers:
     hash of the endpoints names every node's first occurrence, one more small launch; the walk kernel runs over the list of
     first occurrences) -- Philox keys a walk by its root's id, so (xz, indptr) do not change; the sets of the batch sit in the
     rows of the first occurrences (sets.n_distinct of them; bufs.roots == NO_ROOT elsewhere), the other rows are empty.
-    The hash is stamped with a per-step generation kept on the device: a captured step replays correctly."""
+    The hash is stamped with a per-step generation kept on the device: a captured step replays correctly.
+    order=LocalityOrder (sampler.locality_order) or an int32 rank [num_nodes]: every step the fused-row kernel serves walks its
+    rows (or, with dedup_roots, its first occurrences) in ascending rank of their root, whatever the batch size -- the rows are
+    the same; `walk_order` records after each step which order ran ("rank", "id" or "batch")."""
 
     def __init__(self, csr, pairs, num_walks=200, num_steps=3, uniq_capacity=1 << 17, out=None, dedup_roots=False, rng="philox",
-                 key_rows=True, sort_roots=True, batch=None, align_rows=True):
-        from .sampler import FUSED_MAX_Q
+                 key_rows=True, sort_roots=True, batch=None, align_rows=True, order=None):
+        from .sampler import FUSED_MAX_Q, as_rank
         L, dev = lib(), csr.device
+        # order=LocalityOrder / int32 rank: the walk kernel takes the rows in ascending rank of their root (subgacc_worklist_by_rank),
+        # the deduplicated step its first occurrences too; self.walk_order says which order the last step ran
+        self.order = as_rank(csr, order)
+        self.walk_order = None
         self.B, self.M, self.m = int(pairs), int(num_walks), int(num_steps)
         # batch=b: the `pairs` of a step are pairs/b reference-sized batches of b pairs each, handed over as [nb, 2, b] (rows
         # [u_0 | v_0 | u_1 | v_1 | ...]); the join pairs row j with its mirror inside ITS batch, and split_batches() cuts the
@@ -643,14 +650,19 @@ def _dedup_tick(bufs):
 
 
 def _sorted_list(bufs, csr, n, L, st):
-    """the rows of the step as a work list in ascending order of root id (csrc/worklist.hip); its buffers are made on first use"""
+    """the rows of the step as a work list in ascending order of root id (csrc/worklist.hip) -- of rank, with StepBuffers(order=);
+    rows whose root is SUBGACC_NO_ROOT are left out.  Its buffers are made on first use"""
     if not hasattr(bufs, "sorted_list"):
         dev = csr.device
         bufs.sorted_list = torch.empty(n, dtype=torch.int32, device=dev)
         bufs.n_all = torch.zeros(1, dtype=torch.int64, device=dev)
         bufs.sort_ws = torch.zeros(L.subgacc_worklist_workspace_bytes(n), dtype=torch.uint8, device=dev)      # (zeroed once: every call leaves it so)
-    check(L.subgacc_worklist_by_root(ptr(bufs.roots), n, csr.num_nodes, ptr(bufs.sorted_list), ptr(bufs.n_all), ptr(bufs.sort_ws),
-                                     bufs.sort_ws.numel(), st))
+    if bufs.order is not None:
+        check(L.subgacc_worklist_by_rank(ptr(bufs.roots), n, ptr(bufs.order.rank), csr.num_nodes, ptr(bufs.sorted_list), ptr(bufs.n_all),
+                                         ptr(bufs.sort_ws), bufs.sort_ws.numel(), st))
+    else:
+        check(L.subgacc_worklist_by_root(ptr(bufs.roots), n, csr.num_nodes, ptr(bufs.sorted_list), ptr(bufs.n_all), ptr(bufs.sort_ws),
+                                         bufs.sort_ws.numel(), st))
 
 
 def _buffered_step(csr, e, bufs, seed, out):
@@ -677,24 +689,31 @@ def _buffered_step(csr, e, bufs, seed, out):
         check(L.subgacc_step_prologue_dedup(ptr(bufs.table), 0 if kr else bufs.capacity, ptr(bufs.status), 4, ptr(e), ptr(bufs.roots),
                                             ptr(bufs.own), ptr(bufs.partner), ptr(bufs.worklist), ptr(bufs.nsize), n,
                                             ptr(bufs.dedup_ws), bufs.dedup_ws.numel(), ptr(bufs.n_distinct), st))
-        # (no sorted list here: what the order buys is mostly repeated endpoints standing next to each other, and those are gone --
-        # measured, cit2 walk kernel 0.647 ms either way, and the sort costs its 25 us)
+        # (no sorted list by id here: what that order buys is mostly repeated endpoints standing next to each other, and those are
+        # gone -- measured, cit2 walk kernel 0.647 ms either way, and the sort costs its 25 us.  A locality order groups distinct
+        # roots of one community: with order= the first occurrences are walked in ascending rank, subgacc_worklist_by_rank)
+        if bufs.order is not None:
+            _sorted_list(bufs, csr, n, L, st)
+            wl, nwl, bufs.walk_order = bufs.sorted_list, bufs.n_all, "rank"
+        else:
+            wl, nwl, bufs.walk_order = bufs.worklist, bufs.n_distinct, "batch"
         with _timed("walk_sets"):
             if bufs.key64:
                 check(L.subgacc_walk_keyrows64(cfg, ptr(csr.indptr), ptr(csr.indices), csr.num_nodes, ptr(bufs.roots), n, None, None,
-                                               ptr(bufs.worklist), ptr(bufs.n_distinct), ptr(bufs.ids), ptr(bufs.slot), ptr(bufs.nsize),
+                                               ptr(wl), ptr(nwl), ptr(bufs.ids), ptr(bufs.slot), ptr(bufs.nsize),
                                                ptr(flags), st))
             else:
                 check(L.subgacc_walk_spg_sparse(cfg, ptr(csr.indptr), ptr(csr.indices), csr.num_nodes, ptr(bufs.roots), n,
-                                                ptr(bufs.worklist), ptr(bufs.n_distinct), ptr(bufs.table), 0 if kr else bufs.capacity,
+                                                ptr(wl), ptr(nwl), ptr(bufs.table), 0 if kr else bufs.capacity,
                                                 ptr(bufs.ids), ptr(bufs.slot), ptr(bufs.nsize), ptr(flags), st))
         own, partner = bufs.own, bufs.partner
-    elif bufs.sort_roots and n >= SORT_ROOTS_MIN and walk_kernel_name(csr, M, m, True) == "walk_rows_kernel":
+    elif ((bufs.order is not None) or (bufs.sort_roots and n >= SORT_ROOTS_MIN)) and walk_kernel_name(csr, M, m, True) == "walk_rows_kernel":
         # the rows stay where the batch has them; the walk kernel takes them in ascending order of their root's id (a work list):
         # roots that are neighbours in id space -- the same community of a graph with id locality -- are walked at the same time on
         # the same XCD and share its L2
         check(L.subgacc_step_prologue(ptr(bufs.table), 0 if kr else bufs.capacity, ptr(bufs.status), 4, ptr(e), ptr(bufs.roots), n, st))
         _sorted_list(bufs, csr, n, L, st)
+        bufs.walk_order = "rank" if bufs.order is not None else "id"
         if rr:
             check(L.subgacc_rng_positions(cfg, ptr(csr.indptr), csr.num_nodes, ptr(bufs.roots), n, 1, 0, ptr(bufs.rng_pos),
                                           ptr(bufs.rng_seed), ptr(bufs.rng_ws), bufs.rng_ws.numel(), st))
@@ -710,6 +729,7 @@ def _buffered_step(csr, e, bufs, seed, out):
         own, partner = _arange_segments(B, dev, PB)
     else:
         check(L.subgacc_step_prologue(ptr(bufs.table), 0 if kr else bufs.capacity, ptr(bufs.status), 4, ptr(e), ptr(bufs.roots), n, st))
+        bufs.walk_order = "batch"
         if rr:
             check(L.subgacc_rng_positions(cfg, ptr(csr.indptr), csr.num_nodes, ptr(bufs.roots), n, 1, 0, ptr(bufs.rng_pos),
                                           ptr(bufs.rng_seed), ptr(bufs.rng_ws), bufs.rng_ws.numel(), st))
@@ -756,11 +776,12 @@ def _buffered_step(csr, e, bufs, seed, out):
     # from them on demand (the member count of a deduplicated step, X / nnz) is refused once they hold a later batch
     sets._fresh = lambda: getattr(bufs, "step_id", 0) == step_id
     sets.status, sets._tail = bufs.status, bufs.tail[n: n + (6 if bufs.dedup else 5)]
+    sets.walk_order = bufs.walk_order
     return xz, bufs.seg, sets
 
 
 def sample_and_gather(csr, edge, num_walks=200, num_steps=3, seed=111413, rng="philox", dedup_roots=False, out=None,
-                      lazy=False, strided=None, buffers=None, **kw):
+                      lazy=False, strided=None, buffers=None, order=None, **kw):
     """The on-demand form of the path in one call: sample the endpoints of `edge` [2, B] (node ids), build their SpG
     rows, join -> (xz, indptr, sets), the same (xz, indptr) as `gather(edge, subg_matrix(G, arange(N)))` would give for sets
     drawn with the same RNG (Philox keys every walk by (seed, root id, walk, step), so a root's set does not depend on
@@ -770,8 +791,12 @@ def sample_and_gather(csr, edge, num_walks=200, num_steps=3, seed=111413, rng="p
     against a thousand candidates (utils.py:92-95), so half of the endpoints of such a batch are duplicates.
     strided=None picks the joined-in-place form where the fused walk kernel is the faster one (spg.prefers_fused).
     buffers=StepBuffers(...): the same step without a single allocation or helper kernel (six launches; the result is
-    lazy: sets.prefetch() / sets.resolve() as with lazy=True, xz is a view of out= or of the buffers' own output)."""
+    lazy: sets.prefetch() / sets.resolve() as with lazy=True, xz is a view of out= or of the buffers' own output).
+    order=LocalityOrder (sampler.locality_order) or an int32 rank [num_nodes]: the walk kernel takes the endpoints in that order
+    (with buffers=, the StepBuffers' own order= is the one used); (xz, indptr) do not change, sets.walk_order says which ran."""
+    from .sampler import as_rank
     from .spg import sample_spg
+    order = as_rank(csr, order)
     e = _as_rows(edge, csr.device)
     if buffers is None and e.dim() != 2:
         raise ValueError("sample_and_gather: edge must be [2, B] (many batches at once: sample_and_gather_many)")
@@ -782,6 +807,8 @@ def sample_and_gather(csr, edge, num_walks=200, num_steps=3, seed=111413, rng="p
                 kw.get("uniq_capacity", buffers.capacity) != buffers.capacity:
             raise ValueError("buffers= serves the on-demand step (the StepBuffers' rng, fused strided rows; root dedup if the StepBuffers "
                              "were made with dedup_roots=True) of the shape the StepBuffers were made for")
+        if order is not None and (buffers.order is None or order.rank is not buffers.order.rank):
+            raise ValueError("buffers= walks in the order its StepBuffers were made with: pass order= to StepBuffers(...)")
         return _buffered_step(csr, e, buffers, seed, out)
     if dedup_roots:
         if rng != "philox":
@@ -796,7 +823,7 @@ def sample_and_gather(csr, edge, num_walks=200, num_steps=3, seed=111413, rng="p
     if strided:       # joined by table slot below: the distinct LP rows need no numbering (SampledSets.number() does it on demand)
         kw.setdefault("number_rows", False)
     z, sets = sample_spg(csr, roots.to(torch.int32), num_walks=num_walks, num_steps=num_steps, seed=seed, rng=rng, lazy=lazy,
-                         strided=strided, **kw)
+                         strided=strided, order=order, **kw)
     table = z.slot_table() if sets.strided else sets.feature_table()
     if rows is not None:
         xz, ind = gather(rows, z, e.device, ptr=True, encode=table, out=out, lazy=lazy)
@@ -808,12 +835,16 @@ def sample_and_gather(csr, edge, num_walks=200, num_steps=3, seed=111413, rng="p
     return xz, ind, sets
 
 
-def sample_and_gather_many(csr, edges, num_walks=200, num_steps=3, seed=111413, rng="philox", out=None, buffers=None, **kw):
+def sample_and_gather_many(csr, edges, num_walks=200, num_steps=3, seed=111413, rng="philox", out=None, buffers=None, order=None,
+                           **kw):
     """sample_and_gather() for MANY reference-sized batches at once (main.py:32: 1,024 pairs -- 2,048 roots cannot fill the
     chip): `edges` [nb, 2, B]; all nb*2B endpoints are sampled by ONE walk launch and joined by ONE join launch, and the result
     is cut into nb reference-shaped pieces -- [(xz_b, indptr_b)] * nb, bit for bit what sample_and_gather(csr, edges[b], ...)
     returns for every b with rng="philox" (a root's set is a function of (seed, root id)), plus the sets of the whole call.
-    buffers=StepBuffers(csr, nb*B, ..., batch=B): the allocation-free six-launch form; the sets are resolved here (one read)."""
+    buffers=StepBuffers(csr, nb*B, ..., batch=B): the allocation-free six-launch form; the sets are resolved here (one read).
+    order=: as for sample_and_gather -- the walk order of all nb*2B endpoints, nothing else."""
+    from .sampler import as_rank
+    order = as_rank(csr, order)
     e = _as_rows(edges, csr.device)
     if e.dim() != 3 or e.shape[1] != 2:
         raise ValueError("sample_and_gather_many: edges must be [nb, 2, B]")
@@ -824,7 +855,8 @@ def sample_and_gather_many(csr, edges, num_walks=200, num_steps=3, seed=111413, 
     if buffers is not None:
         if buffers.batch != B or buffers.B != nb * B or buffers.dedup:
             raise ValueError(f"buffers= must be StepBuffers(csr, {nb * B}, ..., batch={B})")
-        xz, seg, sets = sample_and_gather(csr, e, num_walks=num_walks, num_steps=num_steps, seed=seed, rng=rng, out=out, buffers=buffers, **kw)
+        xz, seg, sets = sample_and_gather(csr, e, num_walks=num_walks, num_steps=num_steps, seed=seed, rng=rng, out=out, buffers=buffers,
+                                          order=order, **kw)
         sets.resolve()
         views = split_batches(xz, seg, B)
         views._resolve()      # (the pointers live in the step buffers: read now, before the buffers take another step)
@@ -832,7 +864,7 @@ def sample_and_gather_many(csr, edges, num_walks=200, num_steps=3, seed=111413, 
     from .spg import sample_spg
     kw.setdefault("number_rows", False)
     z, sets = sample_spg(csr, e.reshape(-1).to(torch.int32), num_walks=num_walks, num_steps=num_steps, seed=seed, rng=rng,
-                         strided=True, **kw)
+                         strided=True, order=order, **kw)
     table = z.slot_table() if sets.strided else sets.feature_table()
     own = torch.arange(nb * 2 * B, device=e.device, dtype=torch.int64)
     xz, seg = _checked(*sjoin(_as_spg(z), own, None, table, ptr_mode=True, pair_block=B, out=out))
