@@ -248,9 +248,9 @@ int subgacc_sjoin_sizes(const int64_t *spg_indptr, int64_t n_rows, const int64_t
 int subgacc_sjoin_sizes_rows(const int32_t *row_len, int64_t n_rows, const int64_t *own, const int64_t *partner, int64_t S,
                              int64_t *out_seg, int32_t *flags, void *workspace, size_t workspace_bytes, void *stream);   /* strided rows */
 
-/* ABI 6 -- ONE entry point fills the R = out_seg[S] rows of every form of the join: the descriptor states what the store looks
+/* ONE entry point fills the R = out_seg[S] rows of every form of the join: the descriptor states what the store looks
  * like, what a member's payload is, which segments to join and which outputs are wanted; subgacc_sjoin_fill_v2 dispatches.
- * (ABI 7: it is the ONLY fill entry point -- the seven per-form entry points of ABI 1-5, forwards since ABI 6, are gone.)
+ * (Since ABI 7 it is the only fill entry point.)
  *
  *   store      exactly one of three row layouts.  PACKED rows: row_off [n_rows+1] (the SpG of random_walks.py:79).  STRIDED rows:
  *              row_len [n_rows] + row_stride (the form subgacc_walk_spg leaves a transient batch in -- row r = [r*row_stride,
@@ -270,7 +270,9 @@ int subgacc_sjoin_sizes_rows(const int32_t *row_len, int64_t n_rows, const int64
  *                                  itself, subgacc_unpack_lp(zero_row = 1)); feature rows are gathered from table f32 [table_rows, k]
  *                                  (Z_SF with the zero row; an SFptr outside it is never read: flags[3] |= 2)
  *              SUBGACC_JOIN_F64    double: the PPR encoder's score (train.py:39-43); xz is [R,2,1] = (float(own), float((partner or
- *                                  0.0) + 1.0 - 1.0)), the SciPy expression of train.py:33 in double
+ *                                  0.0) + 1.0 - 1.0)), the SciPy expression of train.py:33 in double.  Strided / headed rows: max_len is
+ *                                  not a bound here but the number of members a row is asked for before its length is known
+ *                                  (0 = min(row slot, 128))
  *              SUBGACC_JOIN_KEY32  int32 LP key (key = sum_j count_j << ((num_steps - j) * SHIFT), bit num_steps*SHIFT set on a root's
  *                                  own row, subg_acc.c:900-955): a feature row is the key's unpacked counts / num_walks -- what
  *                                  subgacc_unpack_lp writes into the feature table, computed on the fly (main.py:174's IEEE division);
@@ -453,7 +455,7 @@ int subgacc_step_prologue(void *uniq_table, int64_t capacity, int64_t *zero_word
  *               elsewhere -- rows of the batch's sets stay where the plain step has them, the rows of repeated endpoints
  *               stay empty (subgacc_walk_spg_sparse passes over them), and the distinct LP rows keep their numbering
  *   own, partner int64 [n]: gather()'s mirrored segment lists over those rows -- own[j] = row of endpoint j's first occurrence,
- *               partner[j] = that of the other end of its pair (j +- n/2); for subgacc_sjoin_sizes_rows / _fill_rows / _fill_keyrows
+ *               partner[j] = that of the other end of its pair (j +- n/2); for subgacc_sjoin_sizes_rows / subgacc_sjoin_fill_v2 (strided rows)
  *   worklist    int32 [n]: the first occurrences, worklist[0 .. *n_distinct), in order of arrival (not reproducible, and it does
  *               not matter: entry k names its row) -- what subgacc_walk_spg_sparse runs over
  *   row_len     int32 [n]: the rows' lengths (the sampler's nsize): set to 0 for the rows of repeated endpoints, which the

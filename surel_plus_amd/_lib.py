@@ -50,7 +50,7 @@ class WalkCfg(C.Structure):
 
 
 class JoinDesc(C.Structure):
-    """struct subgacc_join_desc (include/subgacc.h, ABI 6): what one call of subgacc_sjoin_fill_v2 joins"""
+    """struct subgacc_join_desc (include/subgacc.h, ABI 7): what one call of subgacc_sjoin_fill_v2 joins"""
     _fields_ = [("struct_bytes", C.c_int32), ("form", C.c_int32), ("payload_kind", C.c_int32), ("max_len", C.c_int32),
                 ("row_off", C.c_void_p), ("row_len", C.c_void_p), ("row_stride", C.c_int64), ("n_rows", C.c_int64),
                 ("ids", C.c_void_p), ("payload", C.c_void_p), ("uniq_table", C.c_void_p), ("uniq_capacity", C.c_int64),
@@ -197,16 +197,23 @@ def stream_ptr():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def join_fill(form=JOIN_ROWS, payload_kind=JOIN_SFPTR, **fields):
-    """One join through subgacc_sjoin_fill_v2 on the current stream: `fields` are the members of subgacc_join_desc by name --
-    torch tensors for the pointers (None = NULL), ints for the rest; what a form does not read stays zero."""
+def join_desc(form=JOIN_ROWS, payload_kind=JOIN_SFPTR, **fields):
+    """A subgacc_join_desc: `fields` are its members by name -- torch tensors for the pointers (None = NULL), ints for the rest;
+    what a form does not read stays zero."""
     d = JoinDesc()
     d.struct_bytes, d.form, d.payload_kind = C.sizeof(JoinDesc), int(form), int(payload_kind)
     for name, val in fields.items():
         if val is None:
             continue
         setattr(d, name, val.data_ptr() if hasattr(val, "data_ptr") else int(val))
-    return check(lib().subgacc_sjoin_fill_v2(C.byref(d), stream_ptr()))
+    return d
+
+
+def join_fill(form=JOIN_ROWS, payload_kind=JOIN_SFPTR, stream=None, **fields):
+    """One join through subgacc_sjoin_fill_v2 on `stream` (a stream_ptr(), if the caller has it at hand), else on the current stream
+    (fields: see join_desc)."""
+    return check(lib().subgacc_sjoin_fill_v2(C.byref(join_desc(form, payload_kind, **fields)),
+                                             stream if stream is not None else stream_ptr()))
 
 
 def publish(src, host):

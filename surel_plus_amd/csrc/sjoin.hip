@@ -14,7 +14,7 @@
 //   sjoin_fill_kernel                   any other list: one wave per segment, the partner row in LDS (or searched in place when it
 //                                       does not fit)
 //   sjoin_counts_kernel / sjoin_pairs_kernel   the count and pair forms of the join
-// One entry point, subgacc_sjoin_fill_v2(descriptor) (ABI 6); the entry points of ABI 1-5 forward to it (end of file).
+// One entry point, subgacc_sjoin_fill_v2(descriptor), at the end of the file.
 // The [R,2] index array of the reference never exists in memory unless asked for (out_idx).
 #include <cstdlib>
 #include "common.hpp"
@@ -260,7 +260,7 @@ struct JoinArgs {
     // indices / data, where `indices` points ONE WORD behind row_head -- slot 0 of a row's ids holds its length, its members follow
     const int32_t *row_head = nullptr;
     int32_t spec_len = 0;     // strided / headed float rows: members asked for before a row's length is known (sjoin_f64pair_kernel)
-    // key rows (subgacc_sjoin_fill_keyrows): the rows' payload is the member's 32-bit LP key; a feature row is its unpacked
+    // key rows (payload kinds KEY32 / KEY64): the rows' payload is the member's LP key; a feature row is its unpacked
     // counts / num_walks (lut[c] = float(c) / float(M), built per workgroup), 0xFFFFFFFF = partner absent -> the zero row
     int32_t key_M, key_m, key_shift;
     const int32_t *slot_id;   // slot -> SFptr (id plane of the numbered table of distinct LP rows); NULL with
@@ -1419,7 +1419,7 @@ static int launch_table_pairs(JoinArgs &a, int64_t S, int64_t pair_block, bool v
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// ONE entry point for every form of the join (ABI 6; since ABI 7 the only one -- the seven per-form entry points of ABI 1-5 are gone).
+// ONE entry point for every form of the join (since ABI 7 the only one).
 // A descriptor says what the store looks like (packed, strided or headed rows; which payload), which segments to join, what the
 // feature rows are made from and which outputs are wanted.  The kernels' arguments are built from it ONCE, here.
 // key payload (strided rows of a transient batch, or a packed store whose payload was re-keyed): shared launcher
@@ -1587,6 +1587,8 @@ extern "C" int subgacc_sjoin_fill_v2(const subgacc_join_desc *d, void *stream) {
             if (d->form == SUBGACC_JOIN_ROWS) SG_REQUIRE(d->out_xz || d->out_idx, SUBGACC_ERR_BADARG, "sjoin_fill_v2: no output requested");
         }
     }
+    // headed rows keep their lengths in `ids`: the size pass reads them too (the sizes-only call included)
+    SG_REQUIRE(!headed || S == 0 || d->ids, SUBGACC_ERR_BADARG, "sjoin_fill_v2: null argument (ids: the lengths of headed rows)");
     if (sized) {       // the whole join of a batch in one call: size pass, then the fill behind it
         const int rc = join_sizes_onepass(d, (hipStream_t)stream);
         if (rc != SUBGACC_OK || sizes_only) return rc;

@@ -42,7 +42,7 @@ HOP_RECORDS_MAX_FREE_FRACTION = 0.25    # of the free device memory, in "auto" m
 # the buffered step: StepBuffers(sort_roots=True)).  Nothing observable changes; cit2-like step +5.7 % pairs/s, twitter-like +5.6 %.
 SORT_ROOTS_MIN, SORT_ROOTS_MAX = 16384, 1 << 20
 
-# Key rows (csrc/walk_rows.hip KR form + subgacc_sjoin_fill_keyrows): a strided batch that will not be numbered carries its
+# Key rows (csrc/walk_rows.hip KR form, joined as KEY32 / KEY64 rows by subgacc_sjoin_fill_v2): a strided batch that will not be numbered carries its
 # members' 32-bit LP keys instead of slots of a table of distinct rows; the join unpacks a key into its feature row itself.
 # No table, no registration, no unpack pass: -14 % walk-kernel time on the cit2-like batch, -23 % on collab.  Asking such a
 # batch for its numbering afterwards (number(), c, enc_int16(), to_csr()) samples it again with the table form.
@@ -473,7 +473,7 @@ class SampledSets:
         """float32 [capacity+1, m+1]: row s+1 = enc/M of the LP row held in slot s of the table of distinct rows, row 0
         (and the rows of free slots, never indexed) zero -- Z_SF without the numbering, for joins over table slots."""
         if self.keyrows:
-            raise ValueError("key rows are joined by subgacc_sjoin_fill_keyrows: there is no table to index")
+            raise ValueError("key rows are joined by unpacking their keys: there is no table to index")
         if self.table is None:
             raise ValueError("no table of distinct LP rows (sample_sets(..., dedup=True))")
         keys = self.table[: self.capacity * 8].view(torch.int64)

@@ -94,7 +94,13 @@ class SpG:
         enc = blob.get("encode")
         return z, (enc.to(device) if enc is not None else None)
 
-    keyrows = False       # keyed(): the payload is the member's LP key, joined by subgacc_sjoin_fill_keys
+    keyrows = key64 = False       # keyed(): the payload is the member's 32-bit LP key, joined as KEY32 rows
+    payload_is_slot = False       # the payload is SFptr+1 itself (a StridedSpG's is a slot of its batch's table)
+
+    def join_rows(self):
+        """-> (size pass, row fields of subgacc_join_desc): packed rows, sized by subgacc_sjoin_sizes over the row offsets"""
+        return ("subgacc_sjoin_sizes", self.indptr), dict(row_off=self.indptr, ids=self.indices, payload=self.data, n_rows=self.n_rows,
+                                                          max_len=self.max_len)
 
     def keyed(self, enc, num_walks):
         """The same store with every member's 32-bit LP KEY as payload instead of SFptr+1 (shares indptr / indices): the join
@@ -165,6 +171,13 @@ class HeadedSpG:
         self.max_data, self.shape, self.device = max_data, shape, ids.device
         self.keyrows, self.key_M, self.key_m = False, 0, 0
 
+    key64 = payload_is_slot = False
+
+    def join_rows(self):
+        """-> (size pass, row fields of subgacc_join_desc): headed rows, no row pointer -- sized by the library's one-launch size pass
+        (subgacc_sjoin_fill_v2 with SUBGACC_JOIN_OPT_SIZES), named by None"""
+        return None, dict(row_stride=self.pitch, ids=self.ids, payload=self.data, n_rows=self.n_rows)
+
     @classmethod
     def from_spg(cls, z, pitch=None):
         if not isinstance(z, SpG):
@@ -224,12 +237,20 @@ class StridedSpG:
         self.sets = sets
         self.indices, self.slot, self.nsize = sets.ids, sets.slot, sets.nsize
         self.stride = self.max_len = int(sets.stride)
-        self.table, self.capacity = sets.table, sets.capacity
-        self.keyrows = bool(getattr(sets, "keyrows", False))      # payload = LP keys (subgacc_sjoin_fill_keyrows joins them)
+        self.table, self.capacity = sets.table, sets.capacity     # the batch's table of distinct LP rows: slot -> SFptr+1
+        self.keyrows = bool(getattr(sets, "keyrows", False))      # payload = LP keys (joined as KEY32 / KEY64 rows)
+        self.key64, self.key_M, self.key_m = bool(getattr(sets, "key64", False)), sets.num_walks, sets.num_steps
         self._slot_table = None
         self.n_rows = sets.nsize.numel()
         self.shape = (self.n_rows, n_cols)
         self.device = sets.ids.device
+
+    payload_is_slot = True
+
+    def join_rows(self):
+        """-> (size pass, row fields of subgacc_join_desc): strided rows, sized by subgacc_sjoin_sizes_rows over the row lengths"""
+        return ("subgacc_sjoin_sizes_rows", self.nsize), dict(row_len=self.nsize, row_stride=self.stride, ids=self.indices, payload=self.slot,
+                                                               n_rows=self.n_rows)
 
     def slot_table(self):
         """The feature table indexed by table slot (SampledSets.feature_table_by_slot): pass it as `encode` and the

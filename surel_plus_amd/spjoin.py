@@ -17,7 +17,7 @@ from ._lib import JOIN_COUNTS, JOIN_F64, JOIN_KEY32, JOIN_KEY64, JOIN_PAIRS, JOI
 
 NO_ROOT = -2 ** 31      # include/subgacc.h: SUBGACC_NO_ROOT
 from .sampler import _timed
-from .spg import HeadedSpG, SpG, StridedSpG
+from .spg import KEY_ROWS_ENCODE, HeadedSpG, SpG, StridedSpG
 
 _scipy_cache = weakref.WeakKeyDictionary()
 
@@ -52,248 +52,119 @@ def _as_rows(edge, device):
     return torch.from_numpy(np.ascontiguousarray(np.asarray(edge)).astype(np.int64)).to(device)
 
 
-def sjoin(spg, own, partner, encode=None, ptr_mode=True, return_index=False, pair_block=0, out=None, lazy=False):
-    """Generic segment join (include/subgacc.h: subgacc_sjoin_sizes + subgacc_sjoin_fill).
-
-    own/partner: int64 device tensors of SpG row numbers, one segment each.  pair_block = P > 0 promises that
-    the list is made of blocks of P segments with block 2t+1 the mirror of block 2t (see include/subgacc.h).
-    out: optional preallocated float32 buffer with room for the R output rows (a steady-state caller re-uses one
-    buffer instead of asking the allocator for a fresh GB-sized block per batch); the result is a view of it.
-    lazy=True (needs out=, segment pointers, an integer SpG): no host round trip at all -- the number of rows R stays
-    on the device as ind[-1] and xz is the whole buffer viewed as [capacity, 2, k], of which the first R rows are valid.
-    Returns (xz, ind): xz float32 [R,2,k] (or int32 [R,2] index pairs when return_index), ind = int64 [S+1]
-    segment pointers (ptr_mode) or int64 [R] segment ids.
-    """
-    L = lib()
-    dev = spg.device
-    st = stream_ptr()
-    S = own.numel()
-    own = own.contiguous()
-    if partner is None:
-        if pair_block <= 0 and S > 0:
-            raise ValueError("partner=None needs a mirrored segment list (pair_block > 0)")
-    else:
-        partner = partner.contiguous()
-    seg, flags = _seg_and_flags(S, dev)
-    ws = torch.empty(L.subgacc_sjoin_workspace_bytes(S), dtype=torch.uint8, device=dev)
-    if isinstance(spg, StridedSpG):
-        return _sjoin_strided(spg, own, partner, seg, flags, ws, encode, ptr_mode, return_index, pair_block, out, lazy)
-    if isinstance(spg, HeadedSpG):
-        return _sjoin_headed(spg, own, partner, seg, flags, encode, ptr_mode, return_index, pair_block, out, lazy)
-    check(L.subgacc_sjoin_sizes(ptr(spg.indptr), spg.n_rows, ptr(own), ptr(partner), S, ptr(seg), ptr(flags), ptr(ws),
-                                ws.numel(), st))
-    is_f64 = spg.data.dtype == torch.float64
-    if getattr(spg, "keyrows", False):       # SpG.keyed(): the payload is the LP key, the join unpacks it (no table)
-        from .spg import KEY_ROWS_ENCODE
-        if encode is not KEY_ROWS_ENCODE or return_index or (pair_block <= 0 and S > 0) or (lazy and not ptr_mode):
-            raise ValueError("a keyed() store is joined by gather / hgather(…, encode=zk.slot_table())")
-        k = spg.key_m + 1
-        R = None if lazy else _size_and_row_check(seg, S, flags, spg.n_rows)
-        if lazy:
-            if out is None or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev or \
-                    out.numel() < S * spg.max_len * 2 * k:
-                raise ValueError("lazy out= must hold S * SpG.max_len * 2 * k float32 on the SpG's device")
-            rows = out.numel() // (2 * k)
-            res = out.view(-1)[: rows * 2 * k].view(rows, 2, k)
-        elif out is not None:
-            if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < R * 2 * k or out.device != dev:
-                raise ValueError("out= must be a contiguous float32 buffer on the SpG's device with >= R*2*k elements")
-            res = out.view(-1)[: R * 2 * k].view(R, 2, k)
-        else:
-            res = torch.empty((R, 2, k), dtype=torch.float32, device=dev)
-        segid = None if ptr_mode else torch.empty(R, dtype=torch.int64, device=dev)
-        with _timed("sjoin_fill"):
-            join_fill(JOIN_ROWS, JOIN_KEY32, row_off=spg.indptr, n_rows=spg.n_rows, ids=spg.indices, payload=spg.data, max_len=spg.max_len,
-                      own=own, partner=partner, S=S, seg=seg, pair_block=pair_block, num_walks=spg.key_M, num_steps=spg.key_m,
-                      out_xz=res, out_segid=segid, flags=flags)
-        return res, (seg if ptr_mode else _with_pointers(segid, seg)), flags
-    if lazy and (out is None or not ptr_mode or return_index or (encode is None and not is_f64)):
-        raise ValueError("lazy=True needs out=, ptr=True and an integer SpG with its encode table (or a float-payload SpG)")
-    R = None if lazy else _size_and_row_check(seg, S, flags, spg.n_rows)     # the one host round trip
-    segid = None if ptr_mode else torch.empty(R, dtype=torch.int64, device=dev)
-    if is_f64:
+def join_payload(z, encode, return_index=False):
+    """What the members of store `z` carry, as the join needs it: (payload kind, k, the descriptor's payload fields -- table /
+    table_rows / k, num_walks / num_steps for keys, uniq_table / uniq_capacity for the slots of a StridedSpG).  Every payload check
+    of the join is made here.  A StridedSpG's slots become SFptr+1 through its batch's numbered table on their way in, unless
+    `encode` is the batch's own slot_table(): that one is indexed by slot and needs no bound check."""
+    if encode is None and z.payload_is_slot and not return_index:
+        raise NotImplementedError("a sampled batch is joined with an encode table (z.slot_table())")
+    if z.keyrows:           # LP keys (SpG.keyed(), key-rows batches): the join unpacks the feature rows itself, no table
+        if encode is not KEY_ROWS_ENCODE or return_index:
+            raise ValueError("a keyed store is joined by gather / hgather(…, encode=z.slot_table()); other tables and index pairs "
+                             "need the SFptr store (z.to_csr() of a key-rows batch)")
+        return (JOIN_KEY64 if z.key64 else JOIN_KEY32), z.key_m + 1, dict(num_walks=z.key_M, num_steps=z.key_m)
+    if not z.payload_is_slot and z.data.dtype == torch.float64:
         if encode is not None:
             raise TypeError("a float-payload SpG is joined without an encode table (train.py:39-43)")
-        if lazy:      # worst case: every segment as long as the longest SpG row
-            if out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev or out.numel() < S * spg.max_len * 2:
-                raise ValueError("lazy out= must hold S * SpG.max_len * 2 float32 on the SpG's device")
-            rows = out.numel() // 2
-            xz = out.view(-1)[: rows * 2].view(rows, 2, 1)
-        elif out is not None:
-            if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < R * 2 or out.device != dev:
-                raise ValueError("out= must be a contiguous float32 buffer on the SpG's device with >= R*2 elements")
-            xz = out.view(-1)[: R * 2].view(R, 2, 1)
-        else:
-            xz = torch.empty((R, 2, 1), dtype=torch.float32, device=dev)
-        with _timed("sjoin_fill"):
-            join_fill(JOIN_ROWS, JOIN_F64, row_off=spg.indptr, n_rows=spg.n_rows, ids=spg.indices, payload=spg.data, max_len=spg.max_len,
-                      own=own, partner=partner, S=S, seg=seg, pair_block=pair_block, out_xz=xz, out_segid=segid, flags=flags)
-        out = xz
-    elif return_index:
-        out = torch.empty((R, 2), dtype=torch.int32, device=dev)
-        join_fill(JOIN_ROWS, JOIN_SFPTR, row_off=spg.indptr, n_rows=spg.n_rows, ids=spg.indices, payload=spg.data, max_len=spg.max_len,
-                  own=own, partner=partner, S=S, seg=seg, pair_block=pair_block, out_idx=out, out_segid=segid, flags=flags)
-    else:
-        if encode is None:
-            raise NotImplementedError("an integer SpG needs the encode table")
-        enc = encode.to(device=dev, dtype=torch.float32).contiguous()
-        k = enc.shape[1]
-        if enc.shape[0] <= spg.max_data:       # host-side bound check: no device round trip on the hot path
-            raise IndexError(f"index {spg.max_data} is out of bounds for the encode table with {enc.shape[0]} rows")
-        if lazy:      # worst case: every segment as long as the longest SpG row
-            if out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev or \
-                    out.numel() < S * spg.max_len * 2 * k:
-                raise ValueError("lazy out= must hold S * SpG.max_len * 2 * k float32 on the SpG's device")
-            rows = out.numel() // (2 * k)
-            out = out.view(-1)[: rows * 2 * k].view(rows, 2, k)
-        elif out is not None:
-            if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < R * 2 * k or out.device != dev:
-                raise ValueError("out= must be a contiguous float32 buffer on the SpG's device with >= R*2*k elements")
-            out = out.view(-1)[: R * 2 * k].view(R, 2, k)
-        else:
-            out = torch.empty((R, 2, k), dtype=torch.float32, device=dev)
-        with _timed("sjoin_fill"):
-            join_fill(JOIN_ROWS, JOIN_SFPTR, row_off=spg.indptr, n_rows=spg.n_rows, ids=spg.indices, payload=spg.data, max_len=spg.max_len,
-                      own=own, partner=partner, S=S, seg=seg, pair_block=pair_block, table=enc, table_rows=enc.shape[0], k=k,
-                      out_xz=out, out_segid=segid, flags=flags)
-    return out, (seg if ptr_mode else _with_pointers(segid, seg)), flags
-
-
-def _sjoin_strided(spg, own, partner, seg, flags, ws, encode, ptr_mode, return_index, pair_block, out, lazy):
-    """sjoin over a StridedSpG (rows where the fused walk kernel left them): mirrored lists, segment pointers."""
-    L, dev, st, S = lib(), spg.device, stream_ptr(), own.numel()
-    if pair_block <= 0:
-        raise ValueError("a StridedSpG is joined by gather / hgather (mirrored segment lists); use .to_csr() for the other forms")
-    if lazy and not ptr_mode:
-        raise ValueError("lazy=True needs ptr=True")
-    check(L.subgacc_sjoin_sizes_rows(ptr(spg.nsize), spg.n_rows, ptr(own), ptr(partner), S, ptr(seg), ptr(flags), ptr(ws),
-                                     ws.numel(), st))
-    R = None if lazy else _size_and_row_check(seg, S, flags, spg.n_rows)
-    segid = None if ptr_mode else torch.empty(R, dtype=torch.int64, device=dev)
+        return JOIN_F64, 1, {}
+    by_slot = z.payload_is_slot and not return_index and encode is not None and encode is z._slot_table
+    fields = dict(uniq_table=z.table, uniq_capacity=z.capacity) if z.payload_is_slot and not by_slot else {}
     if return_index:
-        if lazy:
-            raise ValueError("lazy=True needs the encode table")
-        if getattr(spg, "keyrows", False):
-            raise ValueError("a key-rows batch has no row numbers to return: join z.to_csr() (gather_index does)")
-        spg.sets.number()               # the pairs are SFptr+1: a transient batch is numbered only now
-        res = torch.empty((R, 2), dtype=torch.int32, device=dev)
-        join_fill(JOIN_ROWS, JOIN_SFPTR, row_len=spg.nsize, n_rows=spg.n_rows, row_stride=spg.stride, ids=spg.indices, payload=spg.slot,
-                  uniq_table=spg.table, uniq_capacity=spg.capacity, own=own, partner=partner, S=S, seg=seg, pair_block=pair_block,
-                  out_idx=res, out_segid=segid, flags=flags)
-        return res, (seg if ptr_mode else _with_pointers(segid, seg)), flags
+        if z.payload_is_slot:
+            z.sets.number()         # the pairs are SFptr+1: a transient batch is numbered only now
+        return JOIN_SFPTR, 0, fields
     if encode is None:
         raise NotImplementedError("an integer SpG needs the encode table")
-    if getattr(spg, "keyrows", False):      # rows of LP keys: the feature rows are unpacked from the keys by the join itself
-        from .spg import KEY_ROWS_ENCODE
-        if encode is not KEY_ROWS_ENCODE:
-            raise ValueError("a key-rows batch is joined with encode=z.slot_table(); use z.to_csr() for another table")
-        M_, m_ = spg.sets.num_walks, spg.sets.num_steps
-        k = m_ + 1
-        if lazy:
-            if out is None or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev or \
-                    out.numel() < S * spg.max_len * 2 * k:
-                raise ValueError("lazy out= must hold S * SpG.max_len * 2 * k float32 on the SpG's device")
-            rows = out.numel() // (2 * k)
-            res = out.view(-1)[: rows * 2 * k].view(rows, 2, k)
-        elif out is not None:
-            if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < R * 2 * k or out.device != dev:
-                raise ValueError("out= must be a contiguous float32 buffer on the SpG's device with >= R*2*k elements")
-            res = out.view(-1)[: R * 2 * k].view(R, 2, k)
-        else:
-            res = torch.empty((R, 2, k), dtype=torch.float32, device=dev)
-        if not ptr_mode:
-            raise ValueError("a key-rows batch is joined with segment pointers (ptr=True); use z.to_csr() for segment ids")
-        with _timed("sjoin_fill"):
-            join_fill(JOIN_ROWS, JOIN_KEY64 if spg.sets.key64 else JOIN_KEY32, row_len=spg.nsize, n_rows=spg.n_rows, row_stride=spg.stride,
-                      ids=spg.indices, payload=spg.slot, own=own, partner=partner, S=S, seg=seg, pair_block=pair_block,
-                      num_walks=M_, num_steps=m_, out_xz=res, flags=flags)
-        return res, seg, flags
-    by_slot = encode is spg._slot_table and encode is not None      # StridedSpG.slot_table(): indexed by slot + 1
-    enc = encode if by_slot else encode.to(device=dev, dtype=torch.float32).contiguous()
-    k = enc.shape[1]
-    if not by_slot and enc.shape[0] <= spg.max_data:
-        raise IndexError(f"index {spg.max_data} is out of bounds for the encode table with {enc.shape[0]} rows")
-    tab, cap = (None, 0) if by_slot else (spg.table, spg.capacity)
-    if lazy:
-        if out is None or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev or \
-                out.numel() < S * spg.max_len * 2 * k:
-            raise ValueError("lazy out= must hold S * SpG.max_len * 2 * k float32 on the SpG's device")
-        rows = out.numel() // (2 * k)
-        res = out.view(-1)[: rows * 2 * k].view(rows, 2, k)
-    elif out is not None:
-        if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < R * 2 * k or out.device != dev:
-            raise ValueError("out= must be a contiguous float32 buffer on the SpG's device with >= R*2*k elements")
-        res = out.view(-1)[: R * 2 * k].view(R, 2, k)
-    else:
-        res = torch.empty((R, 2, k), dtype=torch.float32, device=dev)
-    with _timed("sjoin_fill"):
-        join_fill(JOIN_ROWS, JOIN_SFPTR, row_len=spg.nsize, n_rows=spg.n_rows, row_stride=spg.stride, ids=spg.indices, payload=spg.slot,
-                  uniq_table=tab, uniq_capacity=cap, own=own, partner=partner, S=S, seg=seg, pair_block=pair_block,
-                  table=enc, table_rows=enc.shape[0], k=k, out_xz=res, out_segid=segid, flags=flags)
-    return res, (seg if ptr_mode else _with_pointers(segid, seg)), flags
+    table = encode if by_slot else encode.to(device=z.device, dtype=torch.float32).contiguous()
+    if not by_slot and table.shape[0] <= z.max_data:       # host-side bound check: no device round trip on the hot path
+        raise IndexError(f"index {z.max_data} is out of bounds for the encode table with {table.shape[0]} rows")
+    fields.update(table=table, table_rows=table.shape[0], k=table.shape[1])
+    return JOIN_SFPTR, int(table.shape[1]), fields
 
 
-def _sjoin_headed(spg, own, partner, seg, flags, encode, ptr_mode, return_index, pair_block, out, lazy):
-    """sjoin over a HeadedSpG (a resident store on whole lines, include/subgacc.h: headed rows): mirrored lists.  The size pass is
-    the library's one-launch form (SUBGACC_JOIN_OPT_SIZES): lazily it and the fill are ONE call into a worst-case `out`; eagerly it
-    runs alone first (no output: the "count" call), the host reads [R, status] from pinned memory, and the fill follows into R rows."""
-    from .spg import KEY_ROWS_ENCODE
-    dev, S = spg.device, own.numel()
-    if pair_block <= 0 and S > 0:
-        raise ValueError("a HeadedSpG is joined by gather / hgather (mirrored segment lists); keep the packed store for the other forms")
-    if return_index:
+def _out_view(out, dev, k, R=None, worst=None):
+    """The join's float32 output [rows, 2, k]: a new tensor of R rows, or a view of the caller's buffer `out` -- its first R rows,
+    or, for a lazy join (R stays on the device), all of it, which must hold the worst case of `worst` rows."""
+    if out is None:
+        return torch.empty((R, 2, k), dtype=torch.float32, device=dev)
+    need = R if worst is None else worst
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev or out.numel() < need * 2 * k:
+        raise ValueError(f"out= must be a contiguous float32 buffer on the store's device with room for {need} rows of 2 x {k} "
+                         "(R rows; lazy=True: the worst case, S * max_len)")
+    rows = R if worst is None else out.numel() // (2 * k)
+    return out.view(-1)[: rows * 2 * k].view(rows, 2, k)
+
+
+def sjoin(spg, own, partner, encode=None, ptr_mode=True, return_index=False, pair_block=0, out=None, lazy=False):
+    """Generic segment join (include/subgacc.h: the layout's size pass + subgacc_sjoin_fill_v2) over any store: its rows are described
+    by spg.join_rows(), its payload by join_payload().
+
+    own/partner: int64 device tensors of SpG row numbers, one segment each.  pair_block = P > 0 promises that
+    the list is made of blocks of P segments with block 2t+1 the mirror of block 2t (see include/subgacc.h); strided and headed
+    rows and keyed stores join such lists only.
+    out: optional preallocated float32 buffer with room for the R output rows (a steady-state caller re-uses one
+    buffer instead of asking the allocator for a fresh GB-sized block per batch); the result is a view of it.
+    lazy=True (needs out=, segment pointers, an integer SpG with its encode table or a float one): no host round trip at all -- the
+    number of rows R stays on the device as ind[-1] and xz is the whole buffer viewed as [capacity, 2, k], of which the first R rows
+    are valid.  Headed rows: the size pass is the library's one-launch form (SUBGACC_JOIN_OPT_SIZES) -- lazily it and the fill are
+    ONE call; eagerly it runs alone first (no output), the host reads [R, status] from pinned memory, and the fill follows.
+    Returns (xz, ind, flags): xz float32 [R,2,k] (or int32 [R,2] index pairs when return_index), ind = int64 [S+1]
+    segment pointers (ptr_mode) or int64 [R] segment ids, flags the join's int32[4] status words.
+    """
+    L, dev, S = lib(), spg.device, own.numel()
+    own = own.contiguous()
+    if partner is not None:
+        partner = partner.contiguous()
+    elif pair_block <= 0 and S > 0:
+        raise ValueError("partner=None needs a mirrored segment list (pair_block > 0)")
+    size_pass, rows = spg.join_rows()
+    if lazy and (out is None or not ptr_mode or return_index or
+                 (encode is None and "row_off" in rows and rows["payload"].dtype != torch.float64)):
+        raise ValueError("lazy=True needs out=, ptr=True and feature rows (a packed integer store: with its encode table)")
+    if return_index and size_pass is None:
         raise ValueError("index pairs come from the packed store (gather_index)")
-    kw = dict(row_stride=spg.pitch, n_rows=spg.n_rows, ids=spg.ids, payload=spg.data, own=own, partner=partner, S=S, pair_block=pair_block,
-              flags=flags)
-    if spg.keyrows:
-        if encode is not KEY_ROWS_ENCODE:
-            raise ValueError("a keyed() store is joined by gather / hgather(…, encode=zk.slot_table())")
-        kind, k = JOIN_KEY32, spg.key_m + 1
-        kw.update(num_walks=spg.key_M, num_steps=spg.key_m)
-    elif spg.data.dtype == torch.float64:
-        if encode is not None:
-            raise TypeError("a float-payload SpG is joined without an encode table (train.py:39-43)")
-        kind, k = JOIN_F64, 1
+    kind, k, payload = join_payload(spg, encode, return_index)
+    # only a packed SFptr / float store joins a list that is not mirrored (a strided one not even an empty list)
+    if pair_block <= 0 and (kind in (JOIN_KEY32, JOIN_KEY64) or "row_off" not in rows) and (S > 0 or "row_len" in rows):
+        raise ValueError("this store is joined by gather / hgather (mirrored segment lists); use the packed store (to_csr() / "
+                         "to_spg()) for the other forms")
+    if kind in (JOIN_KEY32, JOIN_KEY64) and "row_len" in rows and not ptr_mode:
+        raise ValueError("a key-rows batch is joined with segment pointers (ptr=True); use z.to_csr() for segment ids")
+    seg, flags = _seg_and_flags(S, dev)
+    st, R = stream_ptr(), None              # (R stays on the device in a lazy join)
+    desc = dict(rows, **payload, own=own, partner=partner, S=S, pair_block=pair_block, flags=flags, seg=seg)
+    if size_pass is None:
+        state = torch.zeros(L.subgacc_sjoin_workspace_bytes(S), dtype=torch.uint8, device=dev)
+        host = torch.empty(2, dtype=torch.int64, pin_memory=True)
+        onepass = dict(options=_lib.JOIN_OPT_SIZES, seg=None, out_seg=seg, size_state=state, size_state_bytes=state.numel(), host_tail=host)
+        if lazy:
+            desc.update(onepass)
+        else:
+            join_fill(JOIN_ROWS, kind, st, **{**desc, **onepass})     # no output: the size pass alone
+            torch.cuda.current_stream(dev).synchronize()
+            R, status = (int(v) for v in host.tolist())
+            if status & 64:
+                raise _lib.SubgAccError("the join's size state was not clean")
+            if status & 16:
+                raise IndexError(f"row index out of range for an SpG with {spg.n_rows} rows")
     else:
-        if encode is None:
-            raise NotImplementedError("an integer SpG needs the encode table")
-        enc = encode.to(device=dev, dtype=torch.float32).contiguous()
-        if enc.shape[0] <= spg.max_data:
-            raise IndexError(f"index {spg.max_data} is out of bounds for the encode table with {enc.shape[0]} rows")
-        kind, k = JOIN_SFPTR, int(enc.shape[1])
-        kw.update(table=enc, table_rows=enc.shape[0], k=k)
-    if lazy and (out is None or not ptr_mode):
-        raise ValueError("lazy=True needs out= and ptr=True")
-    state = torch.zeros(lib().subgacc_sjoin_workspace_bytes(S), dtype=torch.uint8, device=dev)
-    host = torch.empty(2, dtype=torch.int64, pin_memory=True)
-    sized = dict(options=_lib.JOIN_OPT_SIZES, out_seg=seg, size_state=state, size_state_bytes=state.numel(), host_tail=host)
-    if lazy:
-        if out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev or out.numel() < S * spg.max_len * 2 * k:
-            raise ValueError("lazy out= must hold S * SpG.max_len * 2 * k float32 on the SpG's device")
-        rows = out.numel() // (2 * k)
-        res = out.view(-1)[: rows * 2 * k].view(rows, 2, k)
-        with _timed("sjoin_fill"):
-            join_fill(JOIN_ROWS, kind, out_xz=res, **kw, **sized)
+        fn, lens = size_pass
+        ws = torch.empty(L.subgacc_sjoin_workspace_bytes(S), dtype=torch.uint8, device=dev)
+        check(getattr(L, fn)(ptr(lens), spg.n_rows, ptr(own), ptr(partner), S, ptr(seg), ptr(flags), ptr(ws), ws.numel(), st))
+        if not lazy:
+            R = _size_and_row_check(seg, S, flags, spg.n_rows)     # the one host round trip
+    if return_index and kind == JOIN_SFPTR:          # (a float store answers with its xz, as bgather() wants it)
+        res = desc["out_idx"] = torch.empty((R, 2), dtype=torch.int32, device=dev)
+    else:
+        res = desc["out_xz"] = _out_view(out, dev, k, R, S * spg.max_len if lazy else None)
+    segid = desc["out_segid"] = None if ptr_mode else torch.empty(R, dtype=torch.int64, device=dev)
+    with _timed("sjoin_fill"):
+        join_fill(JOIN_ROWS, kind, st, **desc)
+    if lazy and size_pass is None:
         ev = torch.cuda.Event()
         ev.record()
         _lib.keep_until(ev, (host, state))          # the kernels write both after this function has returned
-        return res, seg, flags
-    join_fill(JOIN_ROWS, kind, **kw, **sized)        # no output: the size pass alone
-    torch.cuda.current_stream(dev).synchronize()
-    R, status = (int(v) for v in host.tolist())
-    if status & 64:
-        raise _lib.SubgAccError("the join's size state was not clean")
-    if status & 16:
-        raise IndexError(f"row index out of range for an SpG with {spg.n_rows} rows")
-    if out is not None:
-        if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < R * 2 * k or out.device != dev:
-            raise ValueError("out= must be a contiguous float32 buffer on the SpG's device with >= R*2*k elements")
-        res = out.view(-1)[: R * 2 * k].view(R, 2, k)
-    else:
-        res = torch.empty((R, 2, k), dtype=torch.float32, device=dev)
-    segid = None if ptr_mode else torch.empty(R, dtype=torch.int64, device=dev)
-    with _timed("sjoin_fill"):
-        join_fill(JOIN_ROWS, kind, seg=seg, out_xz=res, out_segid=segid, **kw)
     return res, (seg if ptr_mode else _with_pointers(segid, seg)), flags
 
 
@@ -634,10 +505,9 @@ class StepBuffers:
             self.dedup_steps = 0
         self.ws = torch.empty(max(L.subgacc_sjoin_workspace_bytes(n), 8), dtype=torch.uint8, device=dev)
         self.feat = None if self.keyrows else torch.empty((self.capacity + 1, self.k), dtype=torch.float32, device=dev)
-        need = n * self.Q * 2 * self.k
-        if out is not None and (out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev or out.numel() < need):
-            raise ValueError("StepBuffers: out= must hold 2B * (M*m+1) * 2 * (m+1) float32 on the graph's device")
-        self.out = out if out is not None else torch.empty(need, dtype=torch.float32, device=dev)
+        if out is not None:         # room for the worst case: 2B rows of M*m+1 members
+            _out_view(out, dev, self.k, worst=n * self.Q)
+        self.out = out if out is not None else torch.empty(n * self.Q * 2 * self.k, dtype=torch.float32, device=dev)
 
 
 def _dedup_tick(bufs):
@@ -683,84 +553,56 @@ def _buffered_step(csr, e, bufs, seed, out):
     check(L.subgacc_key_shift(cfg.num_walks, cfg.num_steps))
     kr = bufs.keyrows
     bufs.step_id = step_id = getattr(bufs, "step_id", 0) + 1
+    tab = (ptr(bufs.table), 0 if kr else bufs.capacity)
     if bufs.dedup:      # first occurrences only: the other rows stay empty, the segment lists point at the first occurrence
         if not torch.cuda.is_current_stream_capturing():
             _dedup_tick(bufs)
-        check(L.subgacc_step_prologue_dedup(ptr(bufs.table), 0 if kr else bufs.capacity, ptr(bufs.status), 4, ptr(e), ptr(bufs.roots),
-                                            ptr(bufs.own), ptr(bufs.partner), ptr(bufs.worklist), ptr(bufs.nsize), n,
-                                            ptr(bufs.dedup_ws), bufs.dedup_ws.numel(), ptr(bufs.n_distinct), st))
-        # (no sorted list by id here: what that order buys is mostly repeated endpoints standing next to each other, and those are
-        # gone -- measured, cit2 walk kernel 0.647 ms either way, and the sort costs its 25 us.  A locality order groups distinct
-        # roots of one community: with order= the first occurrences are walked in ascending rank, subgacc_worklist_by_rank)
-        if bufs.order is not None:
-            _sorted_list(bufs, csr, n, L, st)
-            wl, nwl, bufs.walk_order = bufs.sorted_list, bufs.n_all, "rank"
-        else:
-            wl, nwl, bufs.walk_order = bufs.worklist, bufs.n_distinct, "batch"
-        with _timed("walk_sets"):
-            if bufs.key64:
-                check(L.subgacc_walk_keyrows64(cfg, ptr(csr.indptr), ptr(csr.indices), csr.num_nodes, ptr(bufs.roots), n, None, None,
-                                               ptr(wl), ptr(nwl), ptr(bufs.ids), ptr(bufs.slot), ptr(bufs.nsize),
-                                               ptr(flags), st))
-            else:
-                check(L.subgacc_walk_spg_sparse(cfg, ptr(csr.indptr), ptr(csr.indices), csr.num_nodes, ptr(bufs.roots), n,
-                                                ptr(wl), ptr(nwl), ptr(bufs.table), 0 if kr else bufs.capacity,
-                                                ptr(bufs.ids), ptr(bufs.slot), ptr(bufs.nsize), ptr(flags), st))
-        own, partner = bufs.own, bufs.partner
-    elif ((bufs.order is not None) or (bufs.sort_roots and n >= SORT_ROOTS_MIN)) and walk_kernel_name(csr, M, m, True) == "walk_rows_kernel":
-        # the rows stay where the batch has them; the walk kernel takes them in ascending order of their root's id (a work list):
-        # roots that are neighbours in id space -- the same community of a graph with id locality -- are walked at the same time on
-        # the same XCD and share its L2
-        check(L.subgacc_step_prologue(ptr(bufs.table), 0 if kr else bufs.capacity, ptr(bufs.status), 4, ptr(e), ptr(bufs.roots), n, st))
-        _sorted_list(bufs, csr, n, L, st)
-        bufs.walk_order = "rank" if bufs.order is not None else "id"
-        if rr:
-            check(L.subgacc_rng_positions(cfg, ptr(csr.indptr), csr.num_nodes, ptr(bufs.roots), n, 1, 0, ptr(bufs.rng_pos),
-                                          ptr(bufs.rng_seed), ptr(bufs.rng_ws), bufs.rng_ws.numel(), st))
-        with _timed("walk_sets"):
-            if bufs.key64:
-                check(L.subgacc_walk_keyrows64(cfg, ptr(csr.indptr), ptr(csr.indices), csr.num_nodes, ptr(bufs.roots), n, rp, rs,
-                                               ptr(bufs.sorted_list), ptr(bufs.n_all), ptr(bufs.ids), ptr(bufs.slot), ptr(bufs.nsize),
-                                               ptr(flags), st))
-            else:
-                check(L.subgacc_walk_spg_list(cfg, ptr(csr.indptr), ptr(csr.indices), csr.num_nodes, ptr(bufs.roots), n, rp, rs,
-                                              ptr(bufs.sorted_list), ptr(bufs.n_all), ptr(bufs.table), 0 if kr else bufs.capacity,
-                                              ptr(bufs.ids), ptr(bufs.slot), ptr(bufs.nsize), ptr(flags), st))
-        own, partner = _arange_segments(B, dev, PB)
+        check(L.subgacc_step_prologue_dedup(*tab, ptr(bufs.status), 4, ptr(e), ptr(bufs.roots), ptr(bufs.own), ptr(bufs.partner),
+                                            ptr(bufs.worklist), ptr(bufs.nsize), n, ptr(bufs.dedup_ws), bufs.dedup_ws.numel(),
+                                            ptr(bufs.n_distinct), st))
     else:
-        check(L.subgacc_step_prologue(ptr(bufs.table), 0 if kr else bufs.capacity, ptr(bufs.status), 4, ptr(e), ptr(bufs.roots), n, st))
-        bufs.walk_order = "batch"
-        if rr:
-            check(L.subgacc_rng_positions(cfg, ptr(csr.indptr), csr.num_nodes, ptr(bufs.roots), n, 1, 0, ptr(bufs.rng_pos),
-                                          ptr(bufs.rng_seed), ptr(bufs.rng_ws), bufs.rng_ws.numel(), st))
-        with _timed("walk_sets"):
-            if bufs.key64:
-                check(L.subgacc_walk_keyrows64(cfg, ptr(csr.indptr), ptr(csr.indices), csr.num_nodes, ptr(bufs.roots), n, rp, rs,
-                                               None, None, ptr(bufs.ids), ptr(bufs.slot), ptr(bufs.nsize), ptr(flags), st))
-            else:
-                check(L.subgacc_walk_spg(cfg, ptr(csr.indptr), ptr(csr.indices), csr.num_nodes, ptr(bufs.roots), n, 0, rp, rs,
-                                         ptr(bufs.table), 0 if kr else bufs.capacity, ptr(bufs.ids), ptr(bufs.slot), ptr(bufs.nsize),
-                                         ptr(flags), st))
-        own, partner = _arange_segments(B, dev, PB)
+        check(L.subgacc_step_prologue(*tab, ptr(bufs.status), 4, ptr(e), ptr(bufs.roots), n, st))
+    # the work list the walk kernel runs over.  Root dedup: its first occurrences (no sort by id there: what that order buys is mostly
+    # repeated endpoints standing next to each other, and those are gone -- measured, cit2 walk kernel 0.647 ms either way, and the
+    # sort costs its 25 us; a locality order groups distinct roots of one community: with order= they are walked in ascending rank).
+    # Otherwise the rows stay where the batch has them and the fused-row kernel takes them in ascending order of their root's id
+    # (or rank): roots that are neighbours in id space -- the same community of a graph with id locality -- are walked at the same
+    # time on the same XCD and share its L2
+    if bufs.dedup and bufs.order is None:
+        wl, nwl, bufs.walk_order = bufs.worklist, bufs.n_distinct, "batch"
+    elif bufs.dedup or (((bufs.order is not None) or (bufs.sort_roots and n >= SORT_ROOTS_MIN))
+                        and walk_kernel_name(csr, M, m, True) == "walk_rows_kernel"):
+        _sorted_list(bufs, csr, n, L, st)
+        wl, nwl, bufs.walk_order = bufs.sorted_list, bufs.n_all, ("rank" if bufs.order is not None else "id")
+    else:
+        wl, nwl, bufs.walk_order = None, None, "batch"
+    if rr:
+        check(L.subgacc_rng_positions(cfg, ptr(csr.indptr), csr.num_nodes, ptr(bufs.roots), n, 1, 0, ptr(bufs.rng_pos),
+                                      ptr(bufs.rng_seed), ptr(bufs.rng_ws), bufs.rng_ws.numel(), st))
+    graph = (cfg, ptr(csr.indptr), ptr(csr.indices), csr.num_nodes, ptr(bufs.roots), n)
+    rows = (ptr(bufs.ids), ptr(bufs.slot), ptr(bufs.nsize), ptr(flags), st)
+    with _timed("walk_sets"):
+        if bufs.key64:
+            check(L.subgacc_walk_keyrows64(*graph, rp, rs, ptr(wl), ptr(nwl), *rows))
+        elif bufs.dedup:
+            check(L.subgacc_walk_spg_sparse(*graph, ptr(wl), ptr(nwl), *tab, *rows))
+        elif wl is not None:
+            check(L.subgacc_walk_spg_list(*graph, rp, rs, ptr(wl), ptr(nwl), *tab, *rows))
+        else:
+            check(L.subgacc_walk_spg(*graph, 0, rp, rs, *tab, *rows))
+    own, partner = (bufs.own, bufs.partner) if bufs.dedup else _arange_segments(B, dev, PB)
     check(L.subgacc_sjoin_sizes_rows(ptr(bufs.nsize), n, ptr(own), ptr(partner), n, ptr(bufs.seg), ptr(flags), ptr(bufs.ws),
                                      bufs.ws.numel(), st))
-    if not kr:
+    if kr:
+        kind, payload = (JOIN_KEY64 if bufs.key64 else JOIN_KEY32), dict(num_walks=M, num_steps=m)
+    else:
         keys = bufs.table[: bufs.capacity * 8].view(torch.int64)
         check(L.subgacc_unpack_lp(ptr(keys), bufs.capacity, None, M, m, None, None, ptr(bufs.feat), 1, st))
-    res = out if out is not None else bufs.out
-    if res.dtype != torch.float32 or not res.is_contiguous() or res.device != dev or res.numel() < n * bufs.Q * 2 * k:
-        raise ValueError("out= must hold 2B * (M*m+1) * 2 * (m+1) float32 on the graph's device")
-    rows = res.numel() // (2 * k)
-    xz = res.view(-1)[: rows * 2 * k].view(rows, 2, k)
+        kind, payload = JOIN_SFPTR, dict(table=bufs.feat, table_rows=bufs.capacity + 1, k=k)
+    xz = _out_view(out if out is not None else bufs.out, dev, k, worst=n * bufs.Q)
     with _timed("sjoin_fill"):
-        if kr:
-            join_fill(JOIN_ROWS, JOIN_KEY64 if bufs.key64 else JOIN_KEY32, row_len=bufs.nsize, n_rows=n, row_stride=bufs.stride, ids=bufs.ids,
-                      payload=bufs.slot, own=own, partner=partner, S=n, seg=bufs.seg, pair_block=PB, num_walks=M, num_steps=m,
-                      out_xz=xz, flags=flags)
-        else:
-            join_fill(JOIN_ROWS, JOIN_SFPTR, row_len=bufs.nsize, n_rows=n, row_stride=bufs.stride, ids=bufs.ids, payload=bufs.slot,
-                      own=own, partner=partner, S=n, seg=bufs.seg, pair_block=PB, table=bufs.feat, table_rows=bufs.capacity + 1, k=k,
-                      out_xz=xz, flags=flags)
+        join_fill(JOIN_ROWS, kind, st, row_len=bufs.nsize, n_rows=n, row_stride=bufs.stride, ids=bufs.ids, payload=bufs.slot, own=own,
+                  partner=partner, S=n, seg=bufs.seg, pair_block=PB, out_xz=xz, flags=flags, **payload)
     sets = SampledSets(bufs.nsize, None, bufs.ids, None, None, None, M, m, bufs.stride, None)
     sets.slot, sets.table, sets.capacity, sets.strided = bufs.slot, bufs.table, (0 if kr else bufs.capacity), True
     if kr:
@@ -898,6 +740,15 @@ def _arange_segments(B, device, block=None):
     return hit
 
 
+def _packed_rows(spg, form):
+    """The row fields of the store the count / pair / index forms join: these forms have no headed one (ValueError, before any
+    device work)."""
+    size_pass, rows = spg.join_rows()
+    if size_pass is None:
+        raise ValueError(f"{form} joins the packed store: keep it, or join z.to_spg() (the headed layout is for gather / hgather)")
+    return rows
+
+
 def gather_counts(edge, x, table_rows, device=None):
     """Count form of gather() for mean aggregation (reference consumer model.py:78-83).
 
@@ -906,8 +757,9 @@ def gather_counts(edge, x, table_rows, device=None):
     embedding f:  segment_sum_j(f(xz).sum(-2)) == C[j] @ f(Z_SF), so `x = f(xz).sum(-2); aggr(x, ptr)` of the
     reference's Net.forward becomes `(C @ f(Z_SF)) / sizes[:, None]` and the [R,2,k] tensor never exists."""
     spg = _as_spg(x)
-    if spg.data.dtype != torch.int32 or getattr(spg, "keyrows", False):
-        raise TypeError("gather_counts needs an SFptr (integer) SpG (not a keyed() one)")
+    rows = _packed_rows(spg, "gather_counts")
+    if "row_off" not in rows or rows["payload"].dtype != torch.int32 or spg.keyrows:
+        raise TypeError("gather_counts needs a packed SFptr (integer) SpG (not a keyed() one)")
     if table_rows <= spg.max_data:
         raise IndexError(f"index {spg.max_data} is out of bounds for a table with {table_rows} rows")
     e = _as_rows(edge, spg.device)
@@ -920,9 +772,9 @@ def gather_counts(edge, x, table_rows, device=None):
     out = torch.empty((2 * B, int(table_rows)), dtype=torch.float32, device=dev)
     flags = torch.zeros(4, dtype=torch.int32, device=dev)
     with _timed("sjoin_counts"):
-        join_fill(JOIN_COUNTS, JOIN_SFPTR, row_off=spg.indptr, n_rows=spg.n_rows, ids=spg.indices, payload=spg.data, max_len=spg.max_len,
-                  own=own, partner=partner, S=2 * B, pair_block=B, table_rows=int(table_rows), out_counts=out, flags=flags)
-    sizes = spg.indptr[own + 1] - spg.indptr[own]
+        join_fill(JOIN_COUNTS, JOIN_SFPTR, **rows, own=own, partner=partner, S=2 * B, pair_block=B, table_rows=int(table_rows),
+                  out_counts=out, flags=flags)
+    sizes = rows["row_off"][own + 1] - rows["row_off"][own]
     _checked(out, sizes, flags)
     return out, sizes
 
@@ -953,7 +805,8 @@ def gather_pairs(edge, x, device=None):
     spg = _as_spg(x)
     if isinstance(spg, StridedSpG):
         spg = spg.to_csr()
-    if spg.data.dtype != torch.int32 or getattr(spg, "keyrows", False):
+    rows = _packed_rows(spg, "gather_pairs")
+    if rows["payload"].dtype != torch.int32 or spg.keyrows:
         raise TypeError("gather_pairs needs an SFptr (integer) SpG (not a keyed() one)")
     L, dev, st = lib(), spg.device, stream_ptr()
     e = _as_rows(edge, dev)
@@ -963,15 +816,15 @@ def gather_pairs(edge, x, device=None):
     S = 2 * B
     seg, flags = _seg_and_flags(S, dev)
     ws = torch.empty(L.subgacc_sjoin_workspace_bytes(S), dtype=torch.uint8, device=dev)
-    check(L.subgacc_sjoin_sizes(ptr(spg.indptr), spg.n_rows, ptr(own), ptr(partner), S, ptr(seg), ptr(flags), ptr(ws),
+    check(L.subgacc_sjoin_sizes(ptr(rows["row_off"]), spg.n_rows, ptr(own), ptr(partner), S, ptr(seg), ptr(flags), ptr(ws),
                                 ws.numel(), st))
     R = _size_and_row_check(seg, S, flags, spg.n_rows)
     pairs = torch.empty((R, 2), dtype=torch.int32, device=dev)
     mult = torch.empty(R, dtype=torch.int32, device=dev)
     cnt = torch.zeros(S, dtype=torch.int32, device=dev)
     with _timed("sjoin_pairs"):
-        join_fill(JOIN_PAIRS, JOIN_SFPTR, row_off=spg.indptr, n_rows=spg.n_rows, ids=spg.indices, payload=spg.data, max_len=spg.max_len,
-                  own=own, partner=partner, S=S, seg=seg, pair_block=B, out_pairs=pairs, out_mult=mult, out_cnt=cnt, flags=flags)
+        join_fill(JOIN_PAIRS, JOIN_SFPTR, st, **rows, own=own, partner=partner, S=S, seg=seg, pair_block=B, out_pairs=pairs, out_mult=mult,
+                  out_cnt=cnt, flags=flags)
     # rows of segment j sit at [seg[j], seg[j] + cnt[j]): close the gaps (R' ~ R/10 elements from here on)
     indptr = torch.zeros(S + 1, dtype=torch.int64, device=dev)
     torch.cumsum(cnt, 0, out=indptr[1:])
@@ -1016,6 +869,7 @@ def gather_index(edge, x, device=None):
     indptr int64 [2B+1]) with pairs[r] = (SFptr+1 of the member in its own row, in the partner row or 0) -- the row gather()
     would have emitted is encode[pairs[r]], in gather()'s row order (members sorted by node id inside a segment)."""
     spg = _as_spg(x)
+    _packed_rows(spg, "gather_index")
     if isinstance(spg, StridedSpG):     # index pairs need the numbering of the distinct LP rows (transient batches skip it)
         if spg.keyrows:
             spg = spg.to_csr()

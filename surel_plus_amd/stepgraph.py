@@ -18,7 +18,7 @@ import torch
 
 from . import _lib
 from .sampler import check_walk_flags, unpack_status
-from .spjoin import StepBuffers, _dedup_tick, sample_and_gather
+from .spjoin import StepBuffers, _dedup_tick, join_payload, sample_and_gather
 
 
 _DEBUG = os.environ.get("SUBGACC_DEBUG", "0") == "1"
@@ -212,8 +212,6 @@ class CapturedJoin:
     batches of ~1,024 pairs, but every replay costs the GPU ~20 us between graphs (`profiles/r24_join_call_probe.log`)."""
 
     def __init__(self, z, pairs, encode=None, warmup=2, graph=False, triplets=False):
-        import ctypes as C
-        from .spg import KEY_ROWS_ENCODE
         self.z, self.B, self.encode, self.triplets = z, int(pairs), encode, bool(triplets)
         dev = z.device
         B, S = self.B, (4 if triplets else 2) * self.B
@@ -221,44 +219,23 @@ class CapturedJoin:
             raise NotImplementedError          # (train.py:69-70)
         if triplets and graph:
             raise ValueError("triplets=True is the one-call form (graph=False)")
-        d = _lib.JoinDesc()
-        d.struct_bytes, d.form, d.options = C.sizeof(_lib.JoinDesc), _lib.JOIN_ROWS, _lib.JOIN_OPT_SIZES
-        if getattr(z, "keyrows", False):
-            if encode is not KEY_ROWS_ENCODE:
-                raise ValueError("a keyed() store is joined with encode=zk.slot_table()")
-            k, d.payload_kind, d.num_walks, d.num_steps = z.key_m + 1, _lib.JOIN_KEY32, z.key_M, z.key_m
-        elif z.data.dtype == torch.float64:
-            if encode is not None:
-                raise TypeError("a float-payload SpG is joined without an encode table (train.py:39-43)")
-            k, d.payload_kind = 1, _lib.JOIN_F64
-        else:
-            if encode is None:
-                raise NotImplementedError("an integer SpG needs the encode table")
-            self._table = encode.to(device=dev, dtype=torch.float32).contiguous()
-            if self._table.shape[0] <= z.max_data:
-                raise IndexError(f"index {z.max_data} is out of bounds for the encode table with {self._table.shape[0]} rows")
-            k, d.payload_kind = int(self._table.shape[1]), _lib.JOIN_SFPTR
-            d.table, d.table_rows, d.k = self._table.data_ptr(), self._table.shape[0], k
+        kind, k, payload = join_payload(z, encode)
+        self._table = payload.get("table")      # (the descriptor holds its address)
         self.edge = torch.zeros((3 if triplets else 2, B), dtype=torch.int64, device=dev)
         self.out = torch.empty(S * z.max_len * 2 * k, dtype=torch.float32, device=dev)
         self.ind = torch.zeros(S + 1, dtype=torch.int64, device=dev)
         self.flags = torch.zeros(4, dtype=torch.int32, device=dev)
         self._state = torch.zeros(_lib.lib().subgacc_sjoin_workspace_bytes(S), dtype=torch.uint8, device=dev)     # zeroed ONCE
         self._host = torch.zeros(2, dtype=torch.int64, pin_memory=True)
-        if hasattr(z, "pitch"):       # HeadedSpG (SpG.aligned()): rows on whole lines, their lengths in their first slots, no row pointers
-            d.row_stride, d.n_rows, d.ids, d.payload = z.pitch, z.n_rows, z.ids.data_ptr(), z.data.data_ptr()
-        else:
-            d.row_off, d.n_rows, d.ids, d.payload, d.max_len = z.indptr.data_ptr(), z.n_rows, z.indices.data_ptr(), z.data.data_ptr(), z.max_len
-        d.own, d.S, d.pair_block = self.edge.data_ptr(), S, B
         self.segid = None
         if triplets:       # own = [u | w | v | w] (hedge rows 0, 2, 1, 2), the mirrored partner blocks are derived by the kernels
             self._blocks = torch.empty((4, B), dtype=torch.int64, device=dev)
             self._sel = torch.tensor([0, 2, 1, 2], dtype=torch.int64, device=dev)
             self.segid = torch.empty(S * z.max_len, dtype=torch.int64, device=dev)
-            d.own, d.out_segid = self._blocks.data_ptr(), self.segid.data_ptr()
-        d.out_xz, d.flags, d.out_seg = self.out.data_ptr(), self.flags.data_ptr(), self.ind.data_ptr()
-        d.size_state, d.size_state_bytes, d.host_tail = self._state.data_ptr(), self._state.numel(), self._host.data_ptr()
-        self._d, self._ref = d, C.byref(d)
+        d = _lib.join_desc(_lib.JOIN_ROWS, kind, **z.join_rows()[1], **payload, own=self._blocks if triplets else self.edge, S=S,
+                           pair_block=B, options=_lib.JOIN_OPT_SIZES, out_xz=self.out, out_segid=self.segid, flags=self.flags,
+                           out_seg=self.ind, size_state=self._state, size_state_bytes=self._state.numel(), host_tail=self._host)
+        self._d, self._ref = d, _ctypes.byref(d)
         self._fill = _lib.lib().subgacc_sjoin_fill_v2
         self._own = None
         self.xz = self.out.view(S * z.max_len, 2, k)

@@ -157,7 +157,7 @@ int main(int argc, char **argv) {
         for (int j = 0; j <= m; ++j) CHECK(col[j] > 0.999f && col[j] < 1.001f);  /* every LP column sums to M (/M) */
     }
     /* the same join from the store re-keyed on the host (payload = the member's LP key = the low word of its row's 64-bit key):
-     * subgacc_sjoin_fill_keys unpacks the feature rows itself -- bit for bit the table join's xz */
+     * subgacc_sjoin_fill_v2 (KEY32) unpacks the feature rows itself -- bit for bit the table join's xz */
     {
         uint64_t *uk_h = malloc(c * 8);
         int32_t *zk_h = malloc(X * 4);

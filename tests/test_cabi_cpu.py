@@ -128,3 +128,20 @@ def test_join_descriptor_layout_matches_the_header(tmp_path, L):
     d.size_state, d.size_state_bytes = here, 8
     assert L.subgacc_sjoin_fill_v2(C.byref(d), None) == _lib.ERR_WORKSPACE       # a state too small
     assert L.subgacc_sjoin_workspace_bytes(4) >= 64 + 8 and L.subgacc_sjoin_workspace_bytes(1 << 22) >= 64 + 8 * (1 << 12)
+
+
+def test_headed_sizes_only_call_needs_ids(L):
+    """Headed rows keep their lengths in `ids`, and the one-launch size pass reads them: the sizes-only call (OPT_SIZES, no output)
+    with S > 0 and ids = NULL is refused before anything is launched, naming `ids` (it used to reach the state check)."""
+    import ctypes as C
+    from surel_plus_amd import _lib
+    buf = (C.c_int64 * 64)()
+    here = C.addressof(buf)
+    d = _lib.JoinDesc()
+    d.struct_bytes, d.form, d.options = C.sizeof(_lib.JoinDesc), _lib.JOIN_ROWS, _lib.JOIN_OPT_SIZES
+    d.row_stride, d.n_rows, d.S, d.pair_block = 32, 4, 4, 2
+    d.own, d.out_seg = here, here
+    assert L.subgacc_sjoin_fill_v2(C.byref(d), None) == _lib.ERR_BADARG
+    assert b"ids" in L.subgacc_last_error()
+    d.ids = here                                                                # with ids: on to the missing state, as before
+    assert L.subgacc_sjoin_fill_v2(C.byref(d), None) == _lib.ERR_WORKSPACE

@@ -185,7 +185,7 @@ def test_twitter_scale_int64_offsets(sp):
 
 def test_cit2_scale_four_hop_batch_with_64_bit_key_rows(sp):
     """The paper's sampler setting (Fig. 6a: citation2, m = 4, M = 200) at the bench's batch size: 65,536 pairs on demand through the
-    step buffers -- rows of 64-bit LP keys (subgacc_walk_keyrows64 / subgacc_sjoin_fill_keyrows64) -- against the table form of the
+    step buffers -- rows of 64-bit LP keys (subgacc_walk_keyrows64, joined as KEY64 rows) -- against the table form of the
     same batch, bit for bit; a random subset of the endpoints against the oracle; the invariants of subg_acc/test/test.py:34-45."""
     from surel_plus_amd.graphs import preset_graph, query_pairs
     csr = preset_graph("cit2")

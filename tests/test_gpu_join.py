@@ -565,7 +565,7 @@ def test_step_with_root_dedup_equals_the_plain_step(sp, B, M, hops, idx64):
 
 @pytest.mark.parametrize("M,hops", [(200, 3), (200, 2), (64, 3), (100, 4), (255, 4)])
 def test_keyed_store_joins_like_the_table_join(sp, M, hops):
-    """SpG.keyed(): the resident store re-keyed once (payload = LP key instead of SFptr+1, subgacc_sjoin_fill_keys) gives bit for
+    """SpG.keyed(): the resident store re-keyed once (payload = LP key instead of SFptr+1, joined as KEY32 rows) gives bit for
     bit the (xz, indptr) of the reference-style join with Z_SF = float32(enc) / M (main.py:174) -- and of the oracle"""
     ptr_, idx = sym_graph(4000, 30000, seed=17, hubs=2)
     csr = sp.DeviceCSR(ptr_, idx)
@@ -688,7 +688,7 @@ def test_captured_step_replays_equal_the_eager_step(sp, B, hops, rng):
                                           # (the paper's Fig. 6a setting m = 4, M = 200: 33 bits; subgacc_walk_keyrows64)
                                           (100, 4, False), (120, 4, True), (200, 4, False), (128, 4, True), (204, 4, False)])
 def test_key_rows_join_like_table_rows(sp, rng, M, hops, idx64):
-    """rows that carry the LP key instead of a table slot (csrc/walk_rows.hip KR form, subgacc_sjoin_fill_keyrows / _keyrows64):
+    """rows that carry the LP key instead of a table slot (csrc/walk_rows.hip KR form, joined as KEY32 / KEY64 rows):
     the same (xz, indptr) as the table form and as the oracle; numbering, enc and the packed CSR on demand (sampled again)"""
     from surel_plus_amd.graphs import query_pairs
     from surel_plus_amd.sampler import key_rows_form

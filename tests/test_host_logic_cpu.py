@@ -256,3 +256,31 @@ def test_keep_until_never_drops_an_unfinished_entry_under_four_threads():
         for ev, _ in _lib._KEPT:
             ev.done = True
         _lib._KEPT[:] = saved
+
+
+def test_count_pair_and_index_forms_refuse_a_headed_store_before_any_device_work(monkeypatch):
+    """The count / pair / index forms join the packed store: a HeadedSpG (SpG.aligned()) is refused with ValueError, and a StridedSpG
+    by gather_counts with its TypeError -- both before anything reaches the library or a device (here every way there raises)"""
+    from types import SimpleNamespace
+    from surel_plus_amd import spjoin
+    from surel_plus_amd.spg import HeadedSpG, StridedSpG
+
+    def device_work(*a, **k):
+        raise AssertionError("device work before the layout check")
+    for name in ("lib", "join_fill", "stream_ptr", "check", "_as_rows", "_seg_and_flags", "sjoin"):
+        monkeypatch.setattr(spjoin, name, device_work)
+    pitch, n = 32, 3
+    ids = torch.zeros(n * pitch, dtype=torch.int32)
+    ids[::pitch] = torch.tensor([2, 0, 1], dtype=torch.int32)      # row lengths in the rows' first slots
+    z = HeadedSpG(ids, torch.ones(n * pitch, dtype=torch.int32), pitch, n, 2, (n, 10), max_data=1)
+    edge = torch.tensor([[0, 1], [2, 0]])
+    with pytest.raises(ValueError, match="to_spg"):
+        sp.gather_counts(edge, z, 4)
+    with pytest.raises(ValueError, match="to_spg"):
+        sp.gather_pairs(edge, z)
+    with pytest.raises(ValueError, match="to_spg"):
+        sp.gather_index(edge, z)
+    sets = SimpleNamespace(strided=True, ids=ids, slot=ids.clone(), nsize=torch.zeros(n, dtype=torch.int32), stride=pitch, table=None,
+                           capacity=0, num_walks=8, num_steps=2)
+    with pytest.raises(TypeError, match="packed"):
+        sp.gather_counts(edge, StridedSpG(sets, 10), 4)

@@ -5,7 +5,7 @@
 (--store=1: the resident-store joins of the reference's flow -- table and keyed -- instead of the on-demand step's)
 
 One process per (workload, library): builds the preset graph, runs one buffered step (so that the step buffers hold the walk
-kernel's rows and the segment pointers), then times `n` launches of subgacc_sjoin_fill_keyrows(64) over those buffers with HIP
+kernel's rows and the segment pointers), then times `n` launches of the key-rows join (subgacc_sjoin_fill_v2, KEY32 / KEY64) over those buffers with HIP
 events on the launch stream; prints ms, algorithmic bytes and the fraction of the 8 TB/s peak.  `-` = the shipped
 library.  JB_PITCH=n: the same rows laid out again n words apart first (how the 128-byte-aligned pitch was measured before it became
 subgacc_walk_cfg::row_pitch; StepBuffers have it now).  Variant libraries are built HERE into tools/build/ (they travel to the GPU box): tools/join_bench.py --build "-DX=1" name."""
