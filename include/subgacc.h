@@ -247,6 +247,10 @@ int subgacc_sjoin_sizes(const int64_t *spg_indptr, int64_t n_rows, const int64_t
                         int64_t *out_seg, int32_t *flags, void *workspace, size_t workspace_bytes, void *stream);
 int subgacc_sjoin_sizes_rows(const int32_t *row_len, int64_t n_rows, const int64_t *own, const int64_t *partner, int64_t S,
                              int64_t *out_seg, int32_t *flags, void *workspace, size_t workspace_bytes, void *stream);   /* strided rows */
+/* the size pass of a star list (SUBGACC_JOIN_OPT_STAR below) over packed rows: own = the P sources, partner = the P*K targets,
+ * S = 2*P*K segments; out_seg [2*P*K+1] is what subgacc_sjoin_sizes writes for the expanded list.  P*K < 2^31. */
+int subgacc_sjoin_star_sizes(const int64_t *spg_indptr, int64_t n_rows, const int64_t *own, const int64_t *partner, int64_t P,
+                             int64_t K, int64_t *out_seg, int32_t *flags, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ONE entry point fills the R = out_seg[S] rows of every form of the join: the descriptor states what the store looks
  * like, what a member's payload is, which segments to join and which outputs are wanted; subgacc_sjoin_fill_v2 dispatches.
@@ -305,11 +309,24 @@ int subgacc_sjoin_sizes_rows(const int32_t *row_len, int64_t n_rows, const int64
  *              With NO output (out_xz = out_idx = NULL) the call is the size pass alone: out_seg and host_tail are written and
  *              nothing else -- the "count" half of a two-call pattern (then: allocate R rows, call again with seg = that out_seg
  *              and without the option) for callers that do not hold a worst-case buffer.
+ *              SUBGACC_JOIN_OPT_STAR: a STAR list -- one source row against K target rows, the MRR evaluation of the reference
+ *              (train.py:246-280 joins neg_edge = stack([source.repeat_interleave(K), target_neg.view(-1)]), utils.py:93-95), without
+ *              the expanded [2, P*K] list: own = the P source rows, partner = the P*K target rows (target j belongs to source j / K),
+ *              pair_block = K, S = 2*P*K.  The segments are the reference's: the left block [src(0) .. src(P*K-1)], then the right block
+ *              [tgt(0) .. tgt(P*K-1)]; seg, out_xz, out_segid and flags mean exactly what they mean for gather over the expanded edge
+ *              tensor (bit for bit the same rows).  The segment pointers come from subgacc_sjoin_star_sizes (packed rows) or, with
+ *              OPT_SIZES as well, from the one-launch size pass (packed or headed rows).  Scope: the row form; packed and headed rows;
+ *              payloads SFPTR, KEY32 and F64; out_xz (+ out_segid).  Refused with SUBGACC_ERR_BADARG before anything is launched:
+ *              strided rows, KEY64, the count and pair forms, out_idx, pair_block <= 0, S not 2*P*K, partner = NULL.  A row number
+ *              outside the store reads as an empty row and sets flags[3] |= 16, as for any other list.  A source row is staged in LDS
+ *              once per workgroup of targets; a source too long for that (packed rows: ~13k members with a table, ~8k float members)
+ *              is joined by the one-segment-per-wave kernel on the same list instead, with the same result.  flags[1] |= 1 when the
+ *              star kernel ran, |= 2 when a source took that fallback.
  *   struct_bytes = sizeof(subgacc_join_desc): a descriptor of another size is refused (SUBGACC_ERR_BADARG); fields a form does not
  *   read must be zero / NULL. */
 enum { SUBGACC_JOIN_SFPTR = 0, SUBGACC_JOIN_F64 = 1, SUBGACC_JOIN_KEY32 = 2, SUBGACC_JOIN_KEY64 = 3 };
 enum { SUBGACC_JOIN_ROWS = 0, SUBGACC_JOIN_COUNTS = 1, SUBGACC_JOIN_PAIRS = 2 };
-enum { SUBGACC_JOIN_OPT_SIZES = 1 };
+enum { SUBGACC_JOIN_OPT_SIZES = 1, SUBGACC_JOIN_OPT_STAR = 2 };
 typedef struct subgacc_join_desc {
     int32_t struct_bytes, form, payload_kind, max_len;
     const int64_t *row_off;

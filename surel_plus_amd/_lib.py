@@ -36,7 +36,7 @@ SYMBOLS = (
     "subgacc_step_prologue_dedup", "subgacc_walk_spg_sparse",
     "subgacc_keyrows_register", "subgacc_keyrows_cand_capacity", "subgacc_walk_tags", "subgacc_keyrows_compact", "subgacc_keyrows_translate", "subgacc_rng_replay", "subgacc_walk_keyrows64", "subgacc_worklist_workspace_bytes", "subgacc_worklist_by_root", "subgacc_walk_spg_list",
     "subgacc_locality_round", "subgacc_worklist_by_rank",
-    "subgacc_sjoin_fill_v2", "subgacc_publish_words", "subgacc_rows_to_headed",
+    "subgacc_sjoin_fill_v2", "subgacc_publish_words", "subgacc_rows_to_headed", "subgacc_sjoin_star_sizes",
 )
 
 
@@ -65,6 +65,7 @@ class JoinDesc(C.Structure):
 JOIN_SFPTR, JOIN_F64, JOIN_KEY32, JOIN_KEY64 = 0, 1, 2, 3      # payload_kind
 JOIN_ROWS, JOIN_COUNTS, JOIN_PAIRS = 0, 1, 2                   # form
 JOIN_OPT_SIZES = 1                                             # options: size pass + fill in one call
+JOIN_OPT_STAR = 2                                              # options: one source against K targets (gather_star)
 
 
 class SubgAccError(RuntimeError):
@@ -156,6 +157,7 @@ def lib():
     sig["subgacc_sjoin_fill_v2"] = (C.c_int, [C.POINTER(JoinDesc), vp])
     sig["subgacc_publish_words"] = (C.c_int, [vp, i64, vp, vp])
     sig["subgacc_rows_to_headed"] = (C.c_int, [vp, i64, vp, vp, i32, i64, vp, vp, vp, vp])
+    sig["subgacc_sjoin_star_sizes"] = (C.c_int, [vp, i64, vp, vp, i64, i64, vp, vp, vp, sz, vp])
     assert set(sig) == set(SYMBOLS)
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

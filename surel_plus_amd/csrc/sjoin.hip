@@ -38,15 +38,35 @@ struct SegLen {
     int64_t S;
     const int32_t *row_head = nullptr;      // headed rows (ABI 7): the length of row r is row_head[r * row_stride]
     int64_t row_stride = 0;
+    // The segment list's layout, stated: star_k = 0 -- own[j] / partner[j] (partner may be NULL: unchecked); star_k = K > 0 -- the
+    // star list of SUBGACC_JOIN_OPT_STAR: own = P source rows, partner = P*K target rows, segment j < P*K joins source own[j / K]
+    // with target partner[j], segment P*K + j the other way round (S = 2*P*K, P*K < 2^31)
+    int64_t star_k = 0;
     __device__ __forceinline__ int64_t len(int64_t a) const {
         return row_len ? (int64_t)row_len[a] : (row_head ? (int64_t)row_head[a * row_stride] : indptr[a + 1] - indptr[a]);
     }
+    // own row of segment j, and whether the rows of j lie outside the store
+    __device__ __forceinline__ int64_t row(int64_t j, bool &bad) const {
+        int64_t a, b = 0;
+        bool check_b = true;
+        if (star_k) {
+            const uint32_t half = (uint32_t)(S >> 1), jj = (uint32_t)j, k = (uint32_t)star_k;
+            const int64_t src = own[(jj < half ? jj : jj - half) / k], tgt = partner[jj < half ? jj : jj - half];
+            a = jj < half ? src : tgt, b = jj < half ? tgt : src;
+        } else {
+            a = own[j];
+            check_b = partner != nullptr;
+            if (check_b) b = partner[j];
+        }
+        bad = (uint64_t)a >= (uint64_t)n_rows || (check_b && (uint64_t)b >= (uint64_t)n_rows);
+        return a;
+    }
     __device__ __forceinline__ int64_t operator()(int64_t j, bool flag_it) const {
         if (j >= S) return 0;
-        const int64_t a = own[j];
-        const bool bad = (uint64_t)a >= (uint64_t)n_rows;
-        if (flag_it && (bad || (partner && (uint64_t)partner[j] >= (uint64_t)n_rows)) && flags) atomicOr(&flags[3], 16);
-        return bad ? 0 : len(a);
+        bool bad;
+        const int64_t a = row(j, bad);
+        if (flag_it && bad && flags) atomicOr(&flags[3], 16);
+        return (uint64_t)a >= (uint64_t)n_rows ? 0 : len(a);
     }
 };
 #ifndef SJ_SEG_ITEMS      // segments per lane of the two size kernels: 2 (131,072 segments = 256 workgroups; 8 per lane left 3/4 of the CUs idle: 17.8 -> 12 us)
@@ -146,10 +166,10 @@ __global__ __launch_bounds__(kScanThreads) void sjoin_sizes_onepass_kernel(const
             const int64_t j = base + k;
             v[k] = 0;
             if (j < L.S) {
-                const int64_t a = L.own[j];
-                const bool oob = (uint64_t)a >= (uint64_t)L.n_rows;
-                bad |= oob || (L.partner && (uint64_t)L.partner[j] >= (uint64_t)L.n_rows);
-                if (!oob) v[k] = L.len(a);
+                bool oob;
+                const int64_t a = L.row(j, oob);
+                bad |= oob;
+                if ((uint64_t)a < (uint64_t)L.n_rows) v[k] = L.len(a);
             }
             s += v[k];
         }
@@ -270,6 +290,8 @@ struct JoinArgs {
     int64_t pb = 0;           // pair_block of a mirrored list: with partner == NULL the partner of segment j is the own row of its mirror
     int32_t split = 1;        // sjoin_pair_kernel: workgroups per pair (small batches: every one stages both rows and emits
                               // its share of the 64-row spans, so that a batch of ~1,000 pairs still fills the chip)
+    int64_t star_k = 0;       // the star list of SUBGACC_JOIN_OPT_STAR (K targets per source; SegLen::star_k): sjoin_star_kernel, and
+    int32_t star_cap = 0;     // sjoin_fill_kernel for the sources longer than the star_cap members that kernel stages
 };
 
 // Workgroups per pair of sjoin_pair_kernel: batches far below the chip's ~4,096 resident workgroups are split in two
@@ -423,8 +445,18 @@ __global__ __launch_bounds__(kJoinThreads) void sjoin_fill_kernel(const JoinArgs
     if (j >= a.S) return;
     if (a.sized_here && (a.flags[3] & 64)) return;
     const int lane = threadIdx.x;
-    const int64_t ra = a.own[j], rb = join_partner(a, j);
+    int64_t ra, rb;
     int64_t ab, na, bb, nb64;
+    if (a.star_k) {      // a star list: only the segments of sources that sjoin_star_kernel could not stage are joined here
+        const uint32_t half = (uint32_t)(a.S >> 1), jj = (uint32_t)j, t = jj < half ? jj : jj - half;
+        const int64_t src = a.own[t / (uint32_t)a.star_k], tgt = a.partner[t];
+        ra = jj < half ? src : tgt, rb = jj < half ? tgt : src;
+        int64_t sb, sn;
+        join_row(a, src, sb, sn);
+        if (sn <= a.star_cap) return;
+        if (lane == 0) atomicOr(&a.flags[1], 2);
+    } else
+        ra = a.own[j], rb = join_partner(a, j);
     join_row(a, ra, ab, na);
     join_row(a, rb, bb, nb64);
     if (nb64 > (STAGE ? (int64_t)a.max_len : (int64_t)0x7FFFFFFF)) {
@@ -1075,6 +1107,120 @@ __global__ __launch_bounds__(NT) void sjoin_f64pair_kernel(const JoinArgs a, uin
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Star lists (SUBGACC_JOIN_OPT_STAR): ONE source against K targets -- the MRR evaluation of the reference, which joins
+// stack([source.repeat_interleave(K), target_neg.view(-1)]) (train.py:246-280, utils.py:93-95).  The pair kernels above would read and
+// stage the source row once for each of its K targets; here one workgroup takes one source and a chunk of its targets.  The source
+// row (ids, payload) is staged in LDS ONCE; every target is then streamed span by span, each of its members searched in the staged
+// source (halving lower bound, wave-uniform trip count).  A hit gives the target member the source member's value and hands the
+// target's value to the source member's slot of pa[], the per-target scratch, which the lane that emits it zeroes again.  Both
+// blocks of every pair leave as the pair kernels write them: emit_key_span (64-row spans staged at the output's offset mod 16,
+// streaming stores, count / num_walks by the two-fma quotient) or, for the float payload, float2 rows.  Targets are never staged,
+// so their length is not bounded here; a source longer than star_cap is left to sjoin_fill_kernel (launch_star).
+// MODE: 0 = LP keys (KEY32), 1 = SFptr+1 with the Z_SF table (SFPTR), 2 = float payload (F64).
+template <int KV, int NT, int MODE>
+__global__ __launch_bounds__(NT) void sjoin_star_kernel(const JoinArgs a, uint32_t P, uint32_t K, uint32_t chunk, uint32_t chunks) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    constexpr bool F64 = MODE == 2, TAB = MODE == 1;
+    using Val = typename std::conditional<F64, double, uint32_t>::type;
+    constexpr int NW = NT / kWave;
+    const int cap = a.star_cap;
+    Val *valA = (Val *)lds_raw;                 // [cap] payload of the source's members
+    Val *pa = valA + cap;                       // [cap] the current target's value of every source member (0 = absent)
+    int32_t *idsA = (int32_t *)(pa + cap);      // [cap]
+    const int kc = F64 ? 1 : (KV > 0 ? KV : a.k), w = 2 * kc;
+    const int tid = threadIdx.x, lane = tid & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(tid / kWave);
+    const size_t stage_off = ((size_t)cap * (2 * sizeof(Val) + 4) + 15) & ~(size_t)15;
+    float *stage = (float *)(lds_raw + stage_off) + wave * (kWave * w + 4);
+
+    if (a.sized_here && (a.flags[3] & 64)) return;
+    if (blockIdx.x == 0 && tid == 0) atomicOr(&a.flags[1], 1);      // (this kernel ran: a caller can tell it from sjoin_fill_kernel's bit 2)
+    const uint32_t wg = (uint32_t)(blockIdx.x & (kXcds - 1)) * (gridDim.x / kXcds) + (blockIdx.x / kXcds);    // xcd_item, 32 bits
+    const uint32_t p = wg / chunks, part = wg - p * chunks;
+    if (p >= P) return;
+    const uint32_t t_beg = part * chunk, t_end = t_beg + chunk < K ? t_beg + chunk : K;
+    if (t_beg >= t_end) return;
+    int64_t ab, na64;
+    join_row(a, a.own[p], ab, na64);
+    if (na64 > cap) {         // sjoin_fill_kernel's (or, beyond the store's own bound, nobody's)
+        if (na64 > a.max_len && tid == 0) atomicOr(&a.flags[3], 1);
+        return;
+    }
+    const int na = (int)na64;
+    const Val *vals = (const Val *)a.data;
+    for (int r = tid; r < na; r += NT) {        // (plain loads: the other chunks of this source read the row too)
+        idsA[r] = a.indices[ab + r];
+        valA[r] = vals[ab + r];
+        pa[r] = 0;
+    }
+    KeyQuot q;
+    q.fm = (float)a.key_M, q.rcp = 1.0f / q.fm, q.divide = a.key_M >= 4096;
+    float2 *xz = reinterpret_cast<float2 *>(a.out_xz);
+    const int chunksA = (na + kWave - 1) / kWave;
+    const int64_t half = (int64_t)P * K;
+    __syncthreads();
+    for (uint32_t t = t_beg; t < t_end; ++t) {
+        const int64_t j = (int64_t)p * K + t, j2 = half + j;
+        int64_t bb, nb64;
+        join_row(a, a.partner[j], bb, nb64);
+        const int nb = (int)nb64;
+        const int64_t oA = a.seg[j], oB = a.seg[j2];
+        // the target's spans: every member searched in the source, the span emitted on the spot
+        const int chunksB = (nb + kWave - 1) / kWave;
+        for (int c = wave; c < chunksB; c += NW) {
+            const int t0 = c * kWave;
+            const bool live = t0 + lane < nb;
+            int32_t id = 0;
+            Val v = 0;
+            if (live) {
+                id = stream_load(&a.indices[bb + t0 + lane]);
+                v = stream_load(&vals[bb + t0 + lane]);
+            }
+            int bx = 0, n = na;
+            while (n > 1) {
+                const int h = n >> 1;
+                bx = idsA[bx + h] <= id ? bx + h : bx;
+                n -= h;
+            }
+            const bool hit = live && n == 1 && idsA[bx] == id;
+            Val g = 0;
+            if (hit) {
+                pa[bx] = v;
+                g = valA[bx];
+            }
+            if constexpr (F64) {
+                if (live) {      // (partner or 0.0) + 1.0 - 1.0 in double, then the cast (train.py:33,39-43)
+                    float2 o;
+                    o.x = (float)v, o.y = (float)((g + 1.0) - 1.0);
+                    stream_store(xz + oB + t0 + lane, o);
+                    if (a.out_segid) __builtin_nontemporal_store(j2, a.out_segid + oB + t0 + lane);
+                }
+            } else
+                emit_key_span<KV, false, TAB, uint32_t>(a, lane, live, v, g, nb - t0 < kWave ? nb - t0 : kWave, oB + t0, j2, kc, q, stage);
+        }
+        __syncthreads();      // pa[] holds this target's values
+        const int rot = (NW - chunksB % NW) % NW;       // the source's span c goes to wave (c + chunksB) % NW
+        for (int c = (wave + rot) % NW; c < chunksA; c += NW) {
+            const int t0 = c * kWave;
+            const bool live = t0 + lane < na;
+            const int i = live ? t0 + lane : t0;
+            const Val v = valA[i], g = pa[i];
+            if (live) pa[i] = 0;
+            if constexpr (F64) {
+                if (live) {
+                    float2 o;
+                    o.x = (float)v, o.y = (float)((g + 1.0) - 1.0);
+                    stream_store(xz + oA + i, o);
+                    if (a.out_segid) __builtin_nontemporal_store(j, a.out_segid + oA + i);
+                }
+            } else
+                emit_key_span<KV, false, TAB, uint32_t>(a, lane, live, v, g, na - t0 < kWave ? na - t0 : kWave, oA + t0, j, kc, q, stage);
+        }
+        __syncthreads();      // pa[] zero again before the next target's search writes it
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // Count form of the join ("next" row f.1 of SURVEY.md section 8: SpJoin fused with the first model stage).
 // The reference's Net.forward (model.py:78-83) embeds both feature slots of every output row with the same MLP
 // and, for mean aggregation, sums the rows of a segment: segment_sum_j = sum_p C[j,p] * MLP(Z_SF[p]) with
@@ -1327,7 +1473,7 @@ extern "C" size_t subgacc_sjoin_workspace_bytes(int64_t S) {
 
 static int join_sizes(const int64_t *spg_indptr, const int32_t *row_len, int64_t n_rows, const int64_t *own,
                       const int64_t *partner, int64_t S, int64_t *out_seg, int32_t *flags, void *workspace,
-                      size_t workspace_bytes, void *stream) {
+                      size_t workspace_bytes, void *stream, int64_t star_k = 0) {
     SG_REQUIRE(S >= 0 && out_seg && n_rows >= 0, SUBGACC_ERR_BADARG, "sjoin_sizes: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     if (S == 0) return exclusive_scan_i64(nullptr, 0, out_seg, nullptr, 0, s);
@@ -1335,6 +1481,7 @@ static int join_sizes(const int64_t *spg_indptr, const int32_t *row_len, int64_t
     SG_REQUIRE(workspace && workspace_bytes >= subgacc_sjoin_workspace_bytes(S), SUBGACC_ERR_WORKSPACE,
                "sjoin_sizes: workspace too small");
     SegLen L{spg_indptr, row_len, n_rows, own, partner, flags, S};
+    L.star_k = star_k;
     const int64_t nb = ceil_div(S, kSegTile);
     SG_REQUIRE(nb < (1ll << 31), SUBGACC_ERR_BADARG, "sjoin_sizes: too many segments");
     if (nb == 1) {
@@ -1367,6 +1514,7 @@ static int join_sizes_onepass(const subgacc_join_desc *d, hipStream_t s) {
                "sjoin_fill_v2: size_state too small (subgacc_sjoin_workspace_bytes(S) bytes, zeroed once)");
     SegLen L{d->row_off, d->row_len, d->n_rows, d->own, d->partner, d->flags, d->S};
     if (!d->row_off && !d->row_len) L.row_head = d->ids, L.row_stride = d->row_stride;      // headed rows
+    if (d->options & SUBGACC_JOIN_OPT_STAR) L.star_k = d->pair_block;
     hipLaunchKernelGGL(sjoin_sizes_onepass_kernel<kOnePassItems>, dim3((unsigned)nb), dim3(kScanThreads), 0, s, L, d->out_seg,
                        (unsigned long long *)d->size_state, d->host_tail, (int)nb);
     SG_LAUNCH_CHECK();
@@ -1378,6 +1526,16 @@ extern "C" int subgacc_sjoin_sizes(const int64_t *spg_indptr, int64_t n_rows, co
                                    void *stream) {
     SG_REQUIRE(spg_indptr || S == 0, SUBGACC_ERR_BADARG, "sjoin_sizes: null argument");
     return join_sizes(spg_indptr, nullptr, n_rows, own, partner, S, out_seg, flags, workspace, workspace_bytes, stream);
+}
+
+extern "C" int subgacc_sjoin_star_sizes(const int64_t *spg_indptr, int64_t n_rows, const int64_t *own, const int64_t *partner,
+                                        int64_t P, int64_t K, int64_t *out_seg, int32_t *flags, void *workspace,
+                                        size_t workspace_bytes, void *stream) {
+    SG_REQUIRE(P >= 0 && K >= 0 && P < (1ll << 31) && K < (1ll << 31) && P * K < (1ll << 31), SUBGACC_ERR_BADARG,
+               "sjoin_star_sizes: P = %lld sources x K = %lld targets (P*K < 2^31)", (long long)P, (long long)K);
+    const int64_t S = 2 * P * K;
+    SG_REQUIRE(S == 0 || (spg_indptr && own && partner), SUBGACC_ERR_BADARG, "sjoin_star_sizes: null argument");
+    return join_sizes(spg_indptr, nullptr, n_rows, own, partner, S, out_seg, flags, workspace, workspace_bytes, stream, K);
 }
 
 extern "C" int subgacc_sjoin_sizes_rows(const int32_t *row_len, int64_t n_rows, const int64_t *own, const int64_t *partner,
@@ -1423,8 +1581,7 @@ static int launch_table_pairs(JoinArgs &a, int64_t S, int64_t pair_block, bool v
 // A descriptor says what the store looks like (packed, strided or headed rows; which payload), which segments to join, what the
 // feature rows are made from and which outputs are wanted.  The kernels' arguments are built from it ONCE, here.
 // key payload (strided rows of a transient batch, or a packed store whose payload was re-keyed): shared launcher
-static int launch_key_join(JoinArgs &a, int32_t num_walks, int32_t num_steps, int64_t S, int64_t pair_block, void *stream,
-                           const char *who, bool wide = false) {
+static int key_args(JoinArgs &a, int32_t num_walks, int32_t num_steps, const char *who, bool wide) {
     const int shift = subgacc_key_shift(num_walks, num_steps);
     if (shift < 0) return shift;
     SG_REQUIRE(num_steps * shift + 1 <= (wide ? 63 : 31) && num_steps + 1 <= 16, SUBGACC_ERR_KEYWIDTH,
@@ -1433,6 +1590,13 @@ static int launch_key_join(JoinArgs &a, int32_t num_walks, int32_t num_steps, in
     a.out_idx = nullptr;
     a.slot_id = nullptr, a.val_add = 0;
     a.key_M = num_walks, a.key_m = num_steps, a.key_shift = shift;
+    return SUBGACC_OK;
+}
+
+static int launch_key_join(JoinArgs &a, int32_t num_walks, int32_t num_steps, int64_t S, int64_t pair_block, void *stream,
+                           const char *who, bool wide = false) {
+    const int rc = key_args(a, num_walks, num_steps, who, wide);
+    if (rc != SUBGACC_OK) return rc;
     // LDS: the longer row of a pair (id + key + partner key per member), one staging area per wave
     const int nt = (a.max_len > 512 && pair_split(S / 2) == 1 && (a.k == 4 || (wide && a.k == 5))) ? 256 : kPairEmit;
     // (rows of 3- and 4-hop sets -- up to 601 / 801 members -- take 256 lanes per pair: the two rows arrive in half the trips and eight
@@ -1518,6 +1682,60 @@ static int launch_segments(JoinArgs &a, bool f64, bool vec4, void *stream) {
     return SUBGACC_OK;
 }
 
+// Star lists (SUBGACC_JOIN_OPT_STAR): a workgroup per source and chunk of its K targets.  The chunk is chosen so that the grid holds
+// about kStarGroups workgroups -- a few times the chip's resident ones (256 CUs; cf. pair_split) -- whatever the shape: 1,024
+// sources x 1,000 targets -> 8 chunks of 125 targets, 64 x 1,000 -> 128 chunks of 8.  LDS: the source row (id + value + the
+// target's value per member) and, for feature rows, one staging area per wave.  A source longer than fits (packed rows: the
+// store's max_len is not bounded) is joined by sjoin_fill_kernel on the same list, launched behind: the one-segment-per-wave
+// kernel the library takes for such rows anyway; its segments of the other sources return at once.
+#ifndef SJ_STAR_GROUPS      // dev builds: tools/join_bench.py --build "-DSJ_STAR_GROUPS=n"
+#define SJ_STAR_GROUPS 8192
+#endif
+constexpr int64_t kStarGroups = SJ_STAR_GROUPS;
+static int launch_star(JoinArgs &a, int mode, bool vec4, bool packed, int64_t K, void *stream) {
+    const int64_t S = a.S, P = S / (2 * K);
+    SG_REQUIRE(S / 2 < (1ll << 31), SUBGACC_ERR_BADARG, "sjoin_fill_v2: the star option (OPT_STAR) joins fewer than 2^31 pairs, not %lld", (long long)(S / 2));
+    const bool f64 = mode == 2;
+    const int nt = f64 && a.max_len <= 2 * kWave ? kWave : kPairEmit;
+    const size_t per = f64 ? 20 : 12, stage = f64 ? 16 : key_stage_bytes(nt / kWave, a.k);
+    const size_t room = (size_t)kLdsBytes - stage - 16;
+    int64_t cap = a.max_len;
+    if ((size_t)cap * per > room) cap = (int64_t)(room / per);
+    SG_REQUIRE(cap == a.max_len || (packed && mode != 0), SUBGACC_ERR_LDS, "sjoin_fill_v2: rows of %d members do not fit LDS",
+               (int)a.max_len);
+    a.star_k = K, a.star_cap = (int32_t)cap;
+    int64_t chunks = ceil_div(kStarGroups, P);
+    if (chunks > K) chunks = K;
+    const int64_t chunk = ceil_div(K, chunks);
+    chunks = ceil_div(K, chunk);
+    const int64_t grid = xcd_grid(P * chunks);
+    SG_REQUIRE(grid < (1ll << 31), SUBGACC_ERR_BADARG, "sjoin_fill_v2: too many segments in one call");
+    const size_t lds = (((size_t)cap * per + 15) & ~(size_t)15) + stage;
+    hipStream_t s = (hipStream_t)stream;
+#define SG_STAR_LAUNCH(KVV, NTT, M)                                                                                            \
+    do {                                                                                                                        \
+        if (lds > 64 * 1024)                                                                                                    \
+            SG_CHECK_HIP(hipFuncSetAttribute((const void *)sjoin_star_kernel<KVV, NTT, M>,                                      \
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                            \
+        hipLaunchKernelGGL((sjoin_star_kernel<KVV, NTT, M>), dim3((unsigned)grid), dim3(NTT), lds, s, a, (uint32_t)P, (uint32_t)K, \
+                           (uint32_t)chunk, (uint32_t)chunks);                                                                   \
+    } while (0)
+    if (f64 && nt == kWave) SG_STAR_LAUNCH(0, kWave, 2);
+    else if (f64) SG_STAR_LAUNCH(0, kPairEmit, 2);
+    else if (mode == 1 && vec4) SG_STAR_LAUNCH(4, kPairEmit, 1);
+    else if (mode == 1 && a.k == 3) SG_STAR_LAUNCH(3, kPairEmit, 1);
+    else if (mode == 1 && a.k == 5) SG_STAR_LAUNCH(5, kPairEmit, 1);
+    else if (mode == 1) SG_STAR_LAUNCH(0, kPairEmit, 1);
+    else if (a.k == 4) SG_STAR_LAUNCH(4, kPairEmit, 0);
+    else if (a.k == 3) SG_STAR_LAUNCH(3, kPairEmit, 0);
+    else if (a.k == 5) SG_STAR_LAUNCH(5, kPairEmit, 0);
+    else SG_STAR_LAUNCH(0, kPairEmit, 0);
+#undef SG_STAR_LAUNCH
+    SG_LAUNCH_CHECK();
+    if (cap < a.max_len) return launch_segments(a, f64, vec4, stream);      // the sources longer than cap
+    return SUBGACC_OK;
+}
+
 static int launch_counts(JoinArgs &a, int64_t pair_block, float *out_counts, void *stream) {
     const size_t lds = (size_t)a.max_len * 8 + (size_t)a.table_rows * 8 + 16;
     SG_REQUIRE(lds <= (size_t)kLdsBytes, SUBGACC_ERR_LDS,
@@ -1561,7 +1779,8 @@ extern "C" int subgacc_sjoin_fill_v2(const subgacc_join_desc *d, void *stream) {
                "sjoin_fill_v2: exactly one of row_off (packed rows) / row_len (strided rows) / neither, with row_stride (headed rows)");
     SG_REQUIRE(packed || (d->row_stride > (headed ? 1 : 0) && d->row_stride < (1ll << 31)), SUBGACC_ERR_BADARG,
                "sjoin_fill_v2: row_stride = %lld", (long long)d->row_stride);
-    SG_REQUIRE((d->options & ~SUBGACC_JOIN_OPT_SIZES) == 0, SUBGACC_ERR_BADARG, "sjoin_fill_v2: unknown option bits %d", (int)d->options);
+    SG_REQUIRE((d->options & ~(SUBGACC_JOIN_OPT_SIZES | SUBGACC_JOIN_OPT_STAR)) == 0, SUBGACC_ERR_BADARG,
+               "sjoin_fill_v2: unknown option bits %d", (int)d->options);
     SG_REQUIRE(d->form >= SUBGACC_JOIN_ROWS && d->form <= SUBGACC_JOIN_PAIRS, SUBGACC_ERR_BADARG, "sjoin_fill_v2: unknown form %d", (int)d->form);
     SG_REQUIRE(d->payload_kind >= SUBGACC_JOIN_SFPTR && d->payload_kind <= SUBGACC_JOIN_KEY64, SUBGACC_ERR_BADARG,
                "sjoin_fill_v2: unknown payload kind %d", (int)d->payload_kind);
@@ -1569,12 +1788,26 @@ extern "C" int subgacc_sjoin_fill_v2(const subgacc_join_desc *d, void *stream) {
     const bool f64 = kind == SUBGACC_JOIN_F64, keyed = kind == SUBGACC_JOIN_KEY32 || kind == SUBGACC_JOIN_KEY64;
     const bool sized = (d->options & SUBGACC_JOIN_OPT_SIZES) != 0;
     const bool sizes_only = sized && !d->out_xz && !d->out_idx;      // the "count" half of a two-call pattern: out_seg and host_tail only
+    const bool star = (d->options & SUBGACC_JOIN_OPT_STAR) != 0;
     const int64_t *seg = sized ? d->out_seg : d->seg;
     const int64_t S = d->S, pb = d->pair_block;
     // ---- what the kernels would not survive is refused here, before anything is launched (with OPT_SIZES: before the size pass has
     //      written out_seg / host_tail)
     SG_REQUIRE(S >= 0 && d->n_rows >= 0 && d->max_len >= 0, SUBGACC_ERR_BADARG, "sjoin_fill_v2: bad arguments");
     SG_REQUIRE(!sized || d->form == SUBGACC_JOIN_ROWS, SUBGACC_ERR_BADARG, "sjoin_fill_v2: OPT_SIZES goes with the row form");
+    if (star) {      // one source against K targets: the scope of include/subgacc.h, refused here before the size pass runs
+        SG_REQUIRE(d->form == SUBGACC_JOIN_ROWS, SUBGACC_ERR_BADARG, "sjoin_fill_v2: the star option (OPT_STAR) goes with the row form (not the count or pair form)");
+        SG_REQUIRE(!strided, SUBGACC_ERR_BADARG, "sjoin_fill_v2: the star option (OPT_STAR) joins packed or headed rows, not strided rows");
+        SG_REQUIRE(kind != SUBGACC_JOIN_KEY64, SUBGACC_ERR_BADARG, "sjoin_fill_v2: the star option (OPT_STAR) does not join 64-bit keys (KEY64)");
+        SG_REQUIRE(pb > 0, SUBGACC_ERR_BADARG, "sjoin_fill_v2: the star option (OPT_STAR) needs pair_block = K > 0 targets per source (pair_block = %lld)",
+                   (long long)pb);
+        SG_REQUIRE(S >= 0 && S % (2 * pb) == 0, SUBGACC_ERR_BADARG, "sjoin_fill_v2: the star option (OPT_STAR) needs S = 2*P*K (S = %lld, K = %lld)",
+                   (long long)S, (long long)pb);
+        SG_REQUIRE(S == 0 || d->own, SUBGACC_ERR_BADARG, "sjoin_fill_v2: the star option (OPT_STAR) needs own (the P sources); own = NULL");
+        SG_REQUIRE(S == 0 || d->partner, SUBGACC_ERR_BADARG,
+                   "sjoin_fill_v2: the star option (OPT_STAR) needs partner (the P*K targets); partner = NULL");
+        SG_REQUIRE(!d->out_idx, SUBGACC_ERR_BADARG, "sjoin_fill_v2: the star option (OPT_STAR) writes out_xz, not index pairs (out_idx)");
+    }
     if (!sizes_only) {
         SG_REQUIRE(d->flags, SUBGACC_ERR_BADARG, "sjoin_fill_v2: null argument (flags)");
         SG_REQUIRE(!(kind == SUBGACC_JOIN_KEY64 && packed) && !(keyed && strided && d->out_segid), SUBGACC_ERR_BADARG,
@@ -1632,6 +1865,10 @@ extern "C" int subgacc_sjoin_fill_v2(const subgacc_join_desc *d, void *stream) {
     if (keyed) {
         SG_REQUIRE(mirrored && d->out_xz, SUBGACC_ERR_BADARG,
                    "sjoin_fill_v2: key rows are joined as mirrored blocks (pair_block > 0, S a multiple of 2*pair_block) into out_xz");
+        if (star) {
+            const int rc = key_args(a, d->num_walks, d->num_steps, "sjoin_fill_v2", false);
+            return rc != SUBGACC_OK ? rc : launch_star(a, 0, false, packed, pb, stream);
+        }
         return launch_key_join(a, d->num_walks, d->num_steps, S, pb, stream, "sjoin_fill_v2", kind == SUBGACC_JOIN_KEY64);
     }
     if (f64) {
@@ -1639,6 +1876,7 @@ extern "C" int subgacc_sjoin_fill_v2(const subgacc_join_desc *d, void *stream) {
                    "sjoin_fill_v2: float payload writes out_xz [R,2,1] only (train.py:39-43)");
         a.k = 1, a.table = nullptr, a.table_rows = 0;
         a.spec_len = packed ? 0 : (d->max_len > 0 ? d->max_len : (int32_t)(a.max_len < 128 ? a.max_len : 128));     // (headed / strided rows: max_len is the hint)
+        if (star) return launch_star(a, 2, false, packed, pb, stream);
         if (mirrored && (size_t)a.max_len * 20 + 16 <= (size_t)kLdsBytes) return launch_f64_pairs(a, S, pb, stream);
         SG_REQUIRE(packed, SUBGACC_ERR_BADARG, "sjoin_fill_v2: strided / headed float rows are joined as mirrored blocks (pair_block > 0)");
         return launch_segments(a, true, false, stream);
@@ -1653,6 +1891,7 @@ extern "C" int subgacc_sjoin_fill_v2(const subgacc_join_desc *d, void *stream) {
         a.val_add = d->uniq_table ? 0 : 1;
     }
     const bool vec4 = d->out_xz && d->k == 4 && ((uintptr_t)d->table % 16 == 0) && ((uintptr_t)d->out_xz % 16 == 0);
+    if (star) return launch_star(a, 1, vec4, packed, pb, stream);
     if (mirrored && (size_t)a.max_len * 16 <= (size_t)kLdsBytes) return launch_table_pairs(a, S, pb, vec4, stream, "sjoin_fill_v2");
     SG_REQUIRE(packed, SUBGACC_ERR_BADARG, "sjoin_fill_v2: strided / headed rows are joined as mirrored blocks (pair_block > 0)");
     return launch_segments(a, false, vec4, stream);

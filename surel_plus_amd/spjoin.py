@@ -96,7 +96,7 @@ def _out_view(out, dev, k, R=None, worst=None):
     return out.view(-1)[: rows * 2 * k].view(rows, 2, k)
 
 
-def sjoin(spg, own, partner, encode=None, ptr_mode=True, return_index=False, pair_block=0, out=None, lazy=False):
+def sjoin(spg, own, partner, encode=None, ptr_mode=True, return_index=False, pair_block=0, out=None, lazy=False, star=False):
     """Generic segment join (include/subgacc.h: the layout's size pass + subgacc_sjoin_fill_v2) over any store: its rows are described
     by spg.join_rows(), its payload by join_payload().
 
@@ -109,10 +109,13 @@ def sjoin(spg, own, partner, encode=None, ptr_mode=True, return_index=False, pai
     number of rows R stays on the device as ind[-1] and xz is the whole buffer viewed as [capacity, 2, k], of which the first R rows
     are valid.  Headed rows: the size pass is the library's one-launch form (SUBGACC_JOIN_OPT_SIZES) -- lazily it and the fill are
     ONE call; eagerly it runs alone first (no output), the host reads [R, status] from pinned memory, and the fill follows.
+    star=True: a star list (SUBGACC_JOIN_OPT_STAR, gather_star): own = P source rows, partner = P*K target rows, pair_block = K;
+    the S = 2*P*K segments are those of the expanded list [own.repeat_interleave(K) | partner] and its mirror.
     Returns (xz, ind, flags): xz float32 [R,2,k] (or int32 [R,2] index pairs when return_index), ind = int64 [S+1]
     segment pointers (ptr_mode) or int64 [R] segment ids, flags the join's int32[4] status words.
     """
-    L, dev, S = lib(), spg.device, own.numel()
+    L, dev = lib(), spg.device
+    S = 2 * partner.numel() if star else own.numel()
     own = own.contiguous()
     if partner is not None:
         partner = partner.contiguous()
@@ -133,11 +136,12 @@ def sjoin(spg, own, partner, encode=None, ptr_mode=True, return_index=False, pai
         raise ValueError("a key-rows batch is joined with segment pointers (ptr=True); use z.to_csr() for segment ids")
     seg, flags = _seg_and_flags(S, dev)
     st, R = stream_ptr(), None              # (R stays on the device in a lazy join)
-    desc = dict(rows, **payload, own=own, partner=partner, S=S, pair_block=pair_block, flags=flags, seg=seg)
+    star_bit = _lib.JOIN_OPT_STAR if star else 0
+    desc = dict(rows, **payload, own=own, partner=partner, S=S, pair_block=pair_block, flags=flags, seg=seg, options=star_bit)
     if size_pass is None:
         state = torch.zeros(L.subgacc_sjoin_workspace_bytes(S), dtype=torch.uint8, device=dev)
         host = torch.empty(2, dtype=torch.int64, pin_memory=True)
-        onepass = dict(options=_lib.JOIN_OPT_SIZES, seg=None, out_seg=seg, size_state=state, size_state_bytes=state.numel(), host_tail=host)
+        onepass = dict(options=_lib.JOIN_OPT_SIZES | star_bit, seg=None, out_seg=seg, size_state=state, size_state_bytes=state.numel(), host_tail=host)
         if lazy:
             desc.update(onepass)
         else:
@@ -151,7 +155,11 @@ def sjoin(spg, own, partner, encode=None, ptr_mode=True, return_index=False, pai
     else:
         fn, lens = size_pass
         ws = torch.empty(L.subgacc_sjoin_workspace_bytes(S), dtype=torch.uint8, device=dev)
-        check(getattr(L, fn)(ptr(lens), spg.n_rows, ptr(own), ptr(partner), S, ptr(seg), ptr(flags), ptr(ws), ws.numel(), st))
+        if star:        # (a packed store: the star list's own size pass)
+            check(L.subgacc_sjoin_star_sizes(ptr(lens), spg.n_rows, ptr(own), ptr(partner), own.numel(), pair_block, ptr(seg), ptr(flags),
+                                             ptr(ws), ws.numel(), st))
+        else:
+            check(getattr(L, fn)(ptr(lens), spg.n_rows, ptr(own), ptr(partner), S, ptr(seg), ptr(flags), ptr(ws), ws.numel(), st))
         if not lazy:
             R = _size_and_row_check(seg, S, flags, spg.n_rows)     # the one host round trip
     if return_index and kind == JOIN_SFPTR:          # (a float store answers with its xz, as bgather() wants it)
@@ -241,6 +249,62 @@ def gather(edge, x, device=None, ptr=True, encode=None, out=None, lazy=False):
     # own = [u.. | v..] is the contiguous [2, B] tensor itself; the mirrored partner list [v.. | u..] is derived by the kernels
     own = e.contiguous().view(-1)
     return _checked(*sjoin(spg, own, None, encode, ptr_mode=ptr, pair_block=e.shape[1], out=out, lazy=lazy), lazy=lazy)
+
+
+def _star_rows(source, targets):
+    """gather_star's arguments checked on the host -- before any device work -- as (source int64 [P], targets int64 [P, K]), each a
+    torch tensor where it is still (a NumPy array stays on the host until the store's device is known)"""
+    def as_int(v, what, ndim):
+        if not torch.is_tensor(v):
+            try:
+                v = np.asarray(v)
+            except ValueError as e:           # (NumPy >= 1.24 refuses a ragged nested list itself)
+                raise ValueError(f"gather_star: {what} must be a rectangular integer array ({e})") from None
+            if v.dtype == object:
+                raise ValueError(f"gather_star: {what} must be a rectangular integer array, not a ragged one")
+            kind_ok = np.issubdtype(v.dtype, np.integer)
+        else:
+            kind_ok = not v.dtype.is_floating_point and not v.dtype.is_complex and v.dtype != torch.bool
+        if not kind_ok:
+            raise TypeError(f"gather_star: {what} must hold integer row numbers, not {v.dtype}")
+        if v.ndim != ndim:
+            raise ValueError(f"gather_star: {what} must be {ndim}-D ({'[P]' if ndim == 1 else '[P, K]'}), got shape {tuple(v.shape)}")
+        return v
+    source, targets = as_int(source, "source", 1), as_int(targets, "targets", 2)
+    if targets.shape[0] != source.shape[0]:
+        raise ValueError(f"gather_star: targets has {targets.shape[0]} rows for {source.shape[0]} sources ([P, K] for source [P])")
+    return source, targets
+
+
+def gather_star(source, targets, x, device=None, ptr=True, encode=None, out=None, lazy=False, kernel="pairs"):
+    """One source against K targets: the MRR evaluation queries of the reference (train.py:246-280: gather over
+    neg_edge = stack([source.repeat_interleave(K), target_neg.view(-1)]), utils.py:93-95) without the expanded edge tensor.
+
+    source int [P], targets int [P, K] (NumPy or torch, as gather() takes edges).  Returns bit for bit what
+    gather(stack([source.repeat_interleave(K), targets.reshape(-1)]), x, device, ptr, encode) returns -- xz, ind, dtypes and devices --
+    from the library's star form (SUBGACC_JOIN_OPT_STAR): a workgroup stages a source row once and joins it with a run of its
+    targets.  x: an SpG with its encode table, SpG.keyed(...) with its slot_table(), a float SpG, or a HeadedSpG.  out= / lazy= as
+    for sjoin(); the worst case is P*K*(2 * max_len) rows.
+    kernel: "pairs" (default) joins the expanded list with gather's pair kernels, which were faster than the star kernel on every
+    store measured (profiles/star_bench.log); "star" takes the library's star form -- ind.join_flags then holds the
+    join's status words: flags[1] & 1 says the star kernel ran, & 2 that a source too long for it was joined by the
+    one-segment-per-wave kernel."""
+    if kernel not in ("pairs", "star"):
+        raise ValueError(f"gather_star: kernel must be 'pairs' or 'star', not {kernel!r}")
+    if isinstance(x, StridedSpG):
+        raise ValueError("gather_star joins a resident store -- an SpG (with its encode table, or keyed), a float SpG or a HeadedSpG "
+                         "-- not a StridedSpG (use gather on the expanded pairs, or z.to_csr())")
+    source, targets = _star_rows(source, targets)
+    spg = _as_spg(x)
+    P, K = int(targets.shape[0]), int(targets.shape[1])
+    if P * K == 0:      # nothing to join: the expanded edge tensor is [2, 0]
+        return gather(torch.empty((2, 0), dtype=torch.int64, device=spg.device), spg, device, ptr, encode, out, lazy)
+    src, tgt = _as_rows(source, spg.device).contiguous(), _as_rows(targets, spg.device).reshape(-1).contiguous()
+    if kernel == "pairs":
+        return gather(torch.stack([src.repeat_interleave(K), tgt]), spg, device, ptr, encode, out, lazy)
+    xz, ind, flags = sjoin(spg, src, tgt, encode, ptr_mode=ptr, pair_block=K, out=out, lazy=lazy, star=True)
+    ind.join_flags = flags
+    return _checked(xz, ind, flags, lazy=lazy)
 
 
 class BatchViews:
