@@ -356,6 +356,29 @@ typedef struct subgacc_join_desc {
 } subgacc_join_desc;
 int subgacc_sjoin_fill_v2(const subgacc_join_desc *d, void *stream);
 
+/* The first model stage of the PPR / SPD / DEG encoders (utils.py:35-36 and main.py:170-196: a float payload, xz [R,2,1]) fused with
+ * the join -- model.py:78-83, x = pe_embedding(xz).sum(dim=-2); xl, xr = MeanAggregation(x, ptr) -- for pe_embedding =
+ * Sequential(Linear(1, H), ReLU, Linear(H, H')).  Mean aggregation is linear, so for segment j with n_j >= 1 rows (a_t, b_t)
+ *     mean_t pe(a_t) + pe(b_t) = W2 M_j + 2 b2,   M_j[c] = (1/n_j) sum_t relu(fmaf(w1[c], a_t, b1[c])) + relu(fmaf(w1[c], b_t, b1[c]))
+ * and the join writes only M (f32 [S, H]), not xz and the [R,2,H] activations.  (a_t, b_t) are bit for bit the rows the row form
+ * writes: a = float(own), b = float((partner or 0.0) + 1.0 - 1.0) in double (train.py:33).  For the backward, out_p / out_q (both or
+ * neither) receive  P_j[c] = (1/n_j) sum_t sum_{s in {a_t, b_t}} s [fmaf(w1[c], s, b1[c]) > 0]  and  Q_j[c] = (1/n_j) sum_t sum_s
+ * [fmaf(w1[c], s, b1[c]) > 0]:  dL/dw1 = sum_j G_j * P_j, dL/db1 = sum_j G_j * Q_j with G = dL/dM (ReLU's gradient at 0 is 0).
+ * Summation order, the same on every path (packed or headed rows, staged or streamed, every run): per channel c, the own row's members
+ * in ascending id order, for each the a-term and then the b-term added to an fp32 sum starting at 0; then one IEEE division by n_j.
+ * An empty segment (n_j = 0, or a row outside the store) gives zero rows in all three outputs.
+ *   d        the descriptor of a mirrored row-form join of an F64 store: packed (row_off, max_len) or headed (row_stride) rows, own /
+ *            partner (partner may be NULL), pair_block = P > 0, S = 2*P*nb, flags (int32[4], caller zeroes).  No size pass, no seg: a
+ *            segment's size is its own row's length -- one launch.
+ *   w1, b1   f32 [H]: Linear(1, H)'s weight and bias (a zero b1 for a Linear without bias); 1 <= H <= 1024.
+ * Flags as the row form: flags[3] |= 16 a row number outside the store, |= 1 a packed row longer than max_len, |= 4 a list that is
+ * not mirrored (the segments of such a pair are not written); flags[1] |= 2 when a pair had a row too long to stage (1,024 members)
+ * and streamed.  Refused with SUBGACC_ERR_BADARG before anything is launched: a payload other than F64, strided rows, form != ROWS or
+ * any option bit, pair_block <= 0 or S not a multiple of 2*pair_block, own = NULL with S > 0, w1 / b1 / out_mean NULL, H outside
+ * [1, 1024], exactly one of out_p / out_q, any out_* or seg field of the descriptor set, headed rows the row form refuses. */
+int subgacc_sjoin_relu_mean(const subgacc_join_desc *d, const float *w1, const float *b1, int32_t H, float *out_mean,
+                            float *out_p, float *out_q, void *stream);
+
 
 /* Packed rows -> headed rows (ABI 7): the resident store of a serving loop laid out on whole lines -- the rows random_walks.py:79-81
  * builds as a SciPy CSR and train.py:17-18 / :39-43 slice one by one (x[edge[0]]), in the layout the pair kernels read with one

@@ -11,10 +11,13 @@
 //                                       payload = LP key (32 / 64 bits: the feature row is unpacked, count / num_walks by an
 //                                       fma-refined reciprocal) or -- TAB -- SFptr+1 / table slot with the Z_SF table
 //   sjoin_f64pair_kernel                the same plan for the PPR encoder's float payload (train.py:39-43)
+//   sjoin_f64mean_kernel                the same join fused with the float encoders' first model stage (model.py:78-83): per segment
+//                                       the mean of relu(w1 s + b1) over its pairs, no output row (subgacc_sjoin_relu_mean)
 //   sjoin_fill_kernel                   any other list: one wave per segment, the partner row in LDS (or searched in place when it
 //                                       does not fit)
 //   sjoin_counts_kernel / sjoin_pairs_kernel   the count and pair forms of the join
-// One entry point, subgacc_sjoin_fill_v2(descriptor), at the end of the file.
+// One entry point for every form of the join, subgacc_sjoin_fill_v2(descriptor), and subgacc_sjoin_relu_mean for the fused stage,
+// at the end of the file.
 // The [R,2] index array of the reference never exists in memory unless asked for (out_idx).
 #include <cstdlib>
 #include "common.hpp"
@@ -874,30 +877,42 @@ __global__ __launch_bounds__(NT) void sjoin_keypair_kernel(const JoinArgs a, uin
 // 65.8-66.1, profiles/r24_ppr_pairs_per_wg.log.  Starting the workgroups is hidden behind the ones that run; timing builds
 // (profiles/r24_ppr_join_experiments.log: 67 us; 38 without the row loads, 52 without the stores, 37 without both, 55 without the
 // search) and the counters (HBM traffic 1.31x the algorithmic bytes = 4.9 TB/s of what a copy reaches here) say the rest.)
-template <int NT>
-__global__ __launch_bounds__(NT) void sjoin_f64pair_kernel(const JoinArgs a, uint32_t pb, uint32_t pairs) {
-    extern __shared__ __align__(16) unsigned char lds_raw[];
+// The pair join of a float payload up to its output, shared by the row form (sjoin_f64pair_kernel) and the fused first model stage
+// (sjoin_f64mean_kernel): the pair's two rows read, T staged in LDS (valT / idsT, pv[t] = 0.0), every member of S searched in T -- a
+// hit writes S's value into pv -- and every member t of S handed to span_s(t, emit, own value, partner value or 0.0) in ascending
+// order of t within each lane.  ML is the number of members the LDS arrays hold.  T's rows are the caller's, behind a barrier.
+// Returns false for a workgroup without a pair, with a pair that is not mirrored (flags[3] |= 4) or with a row longer than ML -- that
+// pair is handed to too_long() first (nothing staged; p.na / p.nb say how long) --, true once the rows are staged and S is handed
+// over.  SEG: read the segment pointers of j and j2 (p.oS / p.oT).
+struct F64Pair {
+    int64_t j, j2, ra, rb;        // the pair's segments (j2 = the mirror of j) and their own rows
+    bool okA, okB;                // ra / rb inside the store (else an empty row, never dereferenced)
+    int64_t na, nb;               // the rows' lengths
+    int ns, nt;                   // S = the shorter row, T = the longer one ((u,u): the same row)
+    int64_t oS, oT, jS, jT;       // segment pointers (SEG) and segment numbers of S's and T's segments
+    uint32_t part;                // this workgroup's share of the pair (a.split workgroups per pair)
+};
+constexpr int kF64RegTrips = 4;   // trips of S in registers (rows of up to 4 * NT members; longer ones span by span)
+
+template <int NT, bool SEG, typename SpanS, typename TooLong>
+__device__ __forceinline__ bool f64pair_stage(const JoinArgs &a, uint32_t pb, uint32_t pairs, int ML, double *valT, double *pv,
+                                             int32_t *idsT, F64Pair &p, SpanS span_s, TooLong too_long) {
     constexpr int NW = NT / kWave;
-    const int ML = a.max_len;
-    double *valT = (double *)lds_raw;                 // [max_len] values of T
-    double *pv = valT + ML;                           // [max_len] partner values of T's members (0.0 = absent)
-    int32_t *idsT = (int32_t *)(pv + ML);             // [max_len]
+    constexpr int kRegTrips = kF64RegTrips;
     const int tid = threadIdx.x, lane = tid & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(tid / kWave);
 
-    SJ_HOOK_PAIR_ENTRY();
-    if (a.sized_here && (a.flags[3] & 64)) return;
     const uint32_t wg = (uint32_t)(blockIdx.x & (kXcds - 1)) * (gridDim.x / kXcds) + (blockIdx.x / kXcds);    // xcd_item, 32 bits
-    uint32_t p = wg, part = 0;
+    uint32_t pr = wg, part = 0;
     if (a.split > 1) {
-        p = wg / (uint32_t)a.split;
-        part = wg - p * (uint32_t)a.split;
+        pr = wg / (uint32_t)a.split;
+        part = wg - pr * (uint32_t)a.split;
     }
-    if (p >= pairs) return;
-    uint32_t blk = 0, off = p;
+    if (pr >= pairs) return false;
+    uint32_t blk = 0, off = pr;
     if (pb != pairs) {                 // several mirrored blocks (nb batches in one launch)
-        blk = p / pb;
-        off = p - blk * pb;
+        blk = pr / pb;
+        off = pr - blk * pb;
     }
     const int64_t j = (int64_t)blk * 2 * pb + off, j2 = j + pb;
     const double *vals = (const double *)a.data;
@@ -907,14 +922,13 @@ __global__ __launch_bounds__(NT) void sjoin_f64pair_kernel(const JoinArgs a, uin
         rb = a.partner[j];
         if (a.own[j2] != rb || a.partner[j2] != ra) {   // not a mirrored pair: the caller broke the precondition
             if (tid == 0) atomicOr(&a.flags[3], 4);
-            return;
+            return false;
         }
     } else
         rb = a.own[j2];
-    const int64_t oA = a.seg[j], oB = a.seg[j2];
+    const int64_t oA = SEG ? a.seg[j] : 0, oB = SEG ? a.seg[j2] : 0;
     const bool okA = (uint64_t)ra < (uint64_t)a.n_rows, okB = (uint64_t)rb < (uint64_t)a.n_rows;   // else: an empty row, never dereferenced
     int64_t ab = 0, bb = 0, na64 = 0, nb64 = 0;
-    constexpr int kRegTrips = 4;       // trips of S in registers (rows of up to 4 * NT members; longer ones span by span below)
     int32_t sid[kRegTrips];
     double sval[kRegTrips], sgot[kRegTrips];
     int ns, nt;
@@ -942,8 +956,9 @@ __global__ __launch_bounds__(NT) void sjoin_f64pair_kernel(const JoinArgs a, uin
         if (okA) na64 = a.row_len ? a.row_len[ra] : a.row_head[ab];
         if (okB) nb64 = a.row_len ? a.row_len[rb] : a.row_head[bb];
         if (na64 > ML || nb64 > ML) {
-            if (tid == 0) atomicOr(&a.flags[3], 1);
-            return;
+            p.j = j, p.j2 = j2, p.ra = ra, p.rb = rb, p.okA = okA, p.okB = okB, p.na = na64, p.nb = nb64;
+            too_long();
+            return false;
         }
         const int na = (int)na64, nb = (int)nb64;
 #pragma unroll
@@ -984,8 +999,9 @@ __global__ __launch_bounds__(NT) void sjoin_f64pair_kernel(const JoinArgs a, uin
             nb64 = a.indptr[rb + 1] - bb;
         }
         if (na64 > ML || nb64 > ML) {
-            if (tid == 0) atomicOr(&a.flags[3], 1);
-            return;
+            p.j = j, p.j2 = j2, p.ra = ra, p.rb = rb, p.okA = okA, p.okB = okB, p.na = na64, p.nb = nb64;
+            too_long();
+            return false;
         }
         const int na = (int)na64, nb = (int)nb64;
         // roles: S = the shorter row, searched member by member in T = the longer one ((u,u): S and T are the same row)
@@ -1027,11 +1043,16 @@ __global__ __launch_bounds__(NT) void sjoin_f64pair_kernel(const JoinArgs a, uin
         valT[r] = stream_load(&vals[tb + r]);
         pv[r] = 0.0;
     }
+    // (the pair's description is written only now, behind every load of the dependent chain: written earlier, its stores kept the
+    //  compiler from proving those loads unclobbered, and it issued them per lane instead of as scalar loads)
+    p.j = j, p.j2 = j2, p.ra = ra, p.rb = rb, p.okA = okA, p.okB = okB, p.na = na64, p.nb = nb64;
+    p.ns = ns, p.nt = nt, p.oS = oS, p.oT = oT, p.jS = jS, p.jT = jT, p.part = part;
     __syncthreads();
-    SJ_HOOK_PAIR_ROWS_READY();
-    const int chunksS = (ns + kWave - 1) / kWave, chunksT = (nt + kWave - 1) / kWave;
+    bool go_on = false;      // (a dev build's SJ_HOOK_PAIR_ROWS_READY returns from the lambda: the workgroup ends here)
+    [&]() { SJ_HOOK_PAIR_ROWS_READY(); go_on = true; }();
+    if (!go_on) return false;
+    const int chunksS = (ns + kWave - 1) / kWave;
     const bool whole = a.split == 1;
-    float2 *xz = reinterpret_cast<float2 *>(a.out_xz);
     {
         int b[kRegTrips];
 #pragma unroll
@@ -1074,35 +1095,191 @@ __global__ __launch_bounds__(NT) void sjoin_f64pair_kernel(const JoinArgs a, uin
         const double g = valT[bx];
         const bool hit = live && n == 1 && f == id;
         if (hit) pv[bx] = v;
-        if (live && (whole || (uint32_t)(c / NW) % (uint32_t)a.split == part)) {
-            // the scipy expression computes (partner value or 0) + 1.0 - 1.0 in double, then casts (train.py:33,39-43)
-            float2 o;
-            o.x = (float)v, o.y = (float)(((hit ? g : 0.0) + 1.0) - 1.0);
-            stream_store(xz + oS + t0 + lane, o);
-            if (a.out_segid) __builtin_nontemporal_store(jS, a.out_segid + oS + t0 + lane);
-        }
+        span_s(t0 + lane, live && (whole || (uint32_t)(c / NW) % (uint32_t)a.split == part), v, hit ? g : 0.0);
     }
-    // S's spans leave right away (nobody waits for them); T's after the barrier that completes pv
+    // S's spans leave right away (nobody waits for them); T's are the caller's, after the barrier that completes pv
 #pragma unroll
     for (int u = 0; u < kRegTrips; ++u) {
-        const int64_t t = (wave + u * NW) * kWave + lane;
-        if (t < ns && (whole || (uint32_t)u % (uint32_t)a.split == part)) {
-            float2 o;
-            o.x = (float)sval[u], o.y = (float)((sgot[u] + 1.0) - 1.0);
-            stream_store(xz + oS + t, o);
-            if (a.out_segid) __builtin_nontemporal_store(jS, a.out_segid + oS + t);
-        }
+        const int t = (wave + u * NW) * kWave + lane;
+        span_s(t, t < ns && (whole || (uint32_t)u % (uint32_t)a.split == part), sval[u], sgot[u]);
     }
+    return true;
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void sjoin_f64pair_kernel(const JoinArgs a, uint32_t pb, uint32_t pairs) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    constexpr int NW = NT / kWave;
+    const int ML = a.max_len;
+    double *valT = (double *)lds_raw;                 // [max_len] values of T
+    double *pv = valT + ML;                           // [max_len] partner values of T's members (0.0 = absent)
+    int32_t *idsT = (int32_t *)(pv + ML);             // [max_len]
+    const int tid = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid / kWave);
+
+    SJ_HOOK_PAIR_ENTRY();
+    if (a.sized_here && (a.flags[3] & 64)) return;
+    F64Pair p;
+    float2 *xz = reinterpret_cast<float2 *>(a.out_xz);
+    int64_t *segid = a.out_segid;
+    int32_t *flags = a.flags;
+    const auto span_s = [xz, segid, &p](int t, bool emit, double v, double got) {
+        if (emit) {
+            // the scipy expression computes (partner value or 0) + 1.0 - 1.0 in double, then casts (train.py:33,39-43)
+            float2 o;
+            o.x = (float)v, o.y = (float)((got + 1.0) - 1.0);
+            stream_store(xz + p.oS + t, o);
+            if (segid) __builtin_nontemporal_store(p.jS, segid + p.oS + t);
+        }
+    };
+    if (!f64pair_stage<NT, true>(a, pb, pairs, ML, valT, pv, idsT, p, span_s, [flags, tid]() {
+            if (tid == 0) atomicOr(&flags[3], 1);
+        }))
+        return;
     __syncthreads();
+    const int chunksS = (p.ns + kWave - 1) / kWave, chunksT = (p.nt + kWave - 1) / kWave;
     const int rot = (NW - chunksS % NW) % NW;       // T's span c goes to wave (c + chunksS) % NW: the round robin simply goes on
-    for (int c = (wave + rot) % NW + (int)part * NW; c < chunksT; c += a.split * NW) {
-        const int t = c * kWave + lane;
-        if (t < nt) {
+    for (int c = (wave + rot) % NW + (int)p.part * NW; c < chunksT; c += a.split * NW) {
+        const int t = c * kWave + (tid & (kWave - 1));
+        if (t < p.nt) {
             float2 o;
             o.x = (float)valT[t], o.y = (float)((pv[t] + 1.0) - 1.0);
-            stream_store(xz + oT + t, o);
-            if (a.out_segid) __builtin_nontemporal_store(jT, a.out_segid + oT + t);
+            stream_store(xz + p.oT + t, o);
+            if (a.out_segid) __builtin_nontemporal_store(p.jT, a.out_segid + p.oT + t);
         }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The first model stage of the PPR / SPD / DEG encoders fused with the join (subgacc_sjoin_relu_mean, model.py:78-83 with
+// pe_embedding = Sequential(Linear(1, H), ReLU, Linear(H, H'))): per segment j of n_j rows (a_t, b_t) -- the pairs the row form writes,
+// a = float(own), b = float((partner or 0.0) + 1.0 - 1.0) -- only the H-vectors
+//     M_j[c] = (1/n_j) sum_t relu(fmaf(w1[c], a_t, b1[c])) + relu(fmaf(w1[c], b_t, b1[c]))
+// and, for the backward, P_j[c] = (1/n_j) sum_t sum_s s [fmaf(w1[c], s, b1[c]) > 0], Q_j[c] = (1/n_j) sum_t sum_s [... > 0] leave the
+// kernel; no output row is written.  Summation order (include/subgacc.h): per channel, the own row's members in ascending id order, the
+// a-term before the b-term, then one IEEE division by n_j; an empty segment gives a zero row.
+// One workgroup per mirrored pair.  Rows of up to `cap` members are staged and searched by f64pair_stage (as the row form does), every
+// pair (a, b) of S and T then lies in LDS as a float2 and the lanes go through (segment, channel) items, each summing its channel over
+// its segment's members.  A pair with a longer row (a hub of a DEG store) streams instead: each segment's own row in chunks of NT
+// members, every member searched in the partner row where it lies, its (a, b) put in LDS and the chunk summed by the channel lanes --
+// the same sequence of additions, so the same bits (flags[1] |= 2).  cap stays well below what LDS could hold, so that a store with
+// one hub row does not cost every short pair its occupancy.
+struct MeanArgs {
+    const float *w1, *b1;
+    int32_t H;
+    float *out_mean, *out_p, *out_q;
+};
+
+template <bool PQ>
+__device__ __forceinline__ void relu_mean_add(const float2 *rows, int n, float w, float b, float &m, float &p, float &q) {
+    for (int t = 0; t < n; ++t) {
+        const float2 r = rows[t];
+        const float ya = fmaf(w, r.x, b), yb = fmaf(w, r.y, b);
+        m += ya > 0.f ? ya : 0.f;
+        m += yb > 0.f ? yb : 0.f;
+        if (PQ) {
+            p += ya > 0.f ? r.x : 0.f;
+            p += yb > 0.f ? r.y : 0.f;
+            q += ya > 0.f ? 1.f : 0.f;
+            q += yb > 0.f ? 1.f : 0.f;
+        }
+    }
+}
+
+template <bool PQ>
+__device__ __forceinline__ void relu_mean_store(const MeanArgs &m, int64_t j, int c, int n, float sm, float sp, float sq) {
+    const float fn = (float)n;      // (exact: rows are far shorter than 2^24 members)
+    const int64_t o = j * m.H + c;
+    m.out_mean[o] = n ? sm / fn : 0.f;
+    if (PQ) {
+        m.out_p[o] = n ? sp / fn : 0.f;
+        m.out_q[o] = n ? sq / fn : 0.f;
+    }
+}
+
+constexpr int kMeanThreads = kPairEmit;
+constexpr int kMeanCap = 1024;     // longest row staged by sjoin_f64mean_kernel (28 KiB of LDS); longer ones stream
+
+// a pair with a row longer than the kernel stages: each segment's own row in chunks of NT members, every member searched in the partner
+// row where it lies, the chunk's pairs in LDS (ab[NT]) summed by the channel lanes -- the staged path's sequence of additions
+template <bool PQ>
+__device__ __forceinline__ void f64mean_stream(const JoinArgs &a, const F64Pair &p, const MeanArgs &m, float2 *ab) {
+    constexpr int NT = kMeanThreads;
+    const int tid = threadIdx.x, H = m.H;
+    if (a.row_stride == 0 && (p.na > a.max_len || p.nb > a.max_len)) {     // the row form's flags[3] & 1: not joined
+        if (tid == 0) atomicOr(&a.flags[3], 1);
+        return;
+    }
+    if (tid == 0) atomicOr(&a.flags[1], 2);
+    const double *vals = (const double *)a.data;
+    for (int side = 0; side < 2; ++side) {
+        int64_t ob, on, qb, qn;
+        join_row(a, side ? p.rb : p.ra, ob, on);
+        join_row(a, side ? p.ra : p.rb, qb, qn);
+        const int32_t *qids = a.indices + qb;
+        for (int c0 = 0; c0 < H; c0 += NT) {
+            const int c = c0 + tid;
+            const bool live = c < H;
+            const float w = live ? m.w1[c] : 0.f, b = live ? m.b1[c] : 0.f;
+            float sm = 0.f, sp = 0.f, sq = 0.f;
+            for (int64_t t0 = 0; t0 < on; t0 += NT) {
+                __syncthreads();                      // the previous chunk is summed
+                if (t0 + tid < on) {
+                    const int32_t id = a.indices[ob + t0 + tid];
+                    int64_t lo = 0, hi = qn;          // lower bound of id in the partner row, where it lies
+                    while (lo < hi) {
+                        const int64_t mid = (lo + hi) >> 1;
+                        if (qids[mid] < id) lo = mid + 1;
+                        else hi = mid;
+                    }
+                    const double got = lo < qn && qids[lo] == id ? vals[qb + lo] : 0.0;
+                    ab[tid] = make_float2((float)vals[ob + t0 + tid], (float)((got + 1.0) - 1.0));
+                }
+                __syncthreads();
+                if (live) relu_mean_add<PQ>(ab, (int)(on - t0 < NT ? on - t0 : NT), w, b, sm, sp, sq);
+            }
+            if (live) relu_mean_store<PQ>(m, side ? p.j2 : p.j, c, (int)on, sm, sp, sq);
+        }
+    }
+}
+
+template <bool PQ>
+__global__ __launch_bounds__(kMeanThreads) void sjoin_f64mean_kernel(const JoinArgs a, uint32_t pb, uint32_t pairs, int32_t cap,
+                                                                     const MeanArgs m) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    constexpr int NT = kMeanThreads;
+    double *valT = (double *)lds_raw;                 // [cap] values of T; after the search T's pairs as float2, in place
+    double *pv = valT + cap;                          // [cap] partner values of T's members (0.0 = absent)
+    int32_t *idsT = (int32_t *)(pv + cap);            // [cap]
+    float2 *abS = (float2 *)(idsT + ((cap + 1) & ~1));   // [max(cap, NT)] S's pairs (streaming: the current chunk's)
+    const int tid = threadIdx.x;
+    const int H = m.H;
+    F64Pair p;
+    const auto span_s = [&](int t, bool emit, double v, double got) {
+        if (emit) abS[t] = make_float2((float)v, (float)((got + 1.0) - 1.0));
+    };
+    const auto bad_rows = [&]() {       // (the row form's size pass raises this one)
+        if (tid == 0 && !(p.okA && p.okB)) atomicOr(&a.flags[3], 16);
+    };
+    if (!f64pair_stage<NT, false>(a, pb, pairs, cap, valT, pv, idsT, p, span_s, [&]() {
+            bad_rows();
+            f64mean_stream<PQ>(a, p, m, abS);
+        }))
+        return;
+    bad_rows();
+    __syncthreads();                                  // pv complete
+    float2 *abT = (float2 *)valT;
+    for (int t = tid; t < p.nt; t += NT) {            // the thread that reads slot t writes it
+        const double v = valT[t], got = pv[t];
+        abT[t] = make_float2((float)v, (float)((got + 1.0) - 1.0));
+    }
+    __syncthreads();
+    for (int i = tid; i < 2 * H; i += NT) {
+        const bool onT = i >= H;
+        const int c = onT ? i - H : i, n = onT ? p.nt : p.ns;
+        float sm = 0.f, sp = 0.f, sq = 0.f;
+        relu_mean_add<PQ>(onT ? abT : abS, n, m.w1[c], m.b1[c], sm, sp, sq);
+        relu_mean_store<PQ>(m, onT ? p.jT : p.jS, c, n, sm, sp, sq);
     }
 }
 
@@ -1895,4 +2072,66 @@ extern "C" int subgacc_sjoin_fill_v2(const subgacc_join_desc *d, void *stream) {
     if (mirrored && (size_t)a.max_len * 16 <= (size_t)kLdsBytes) return launch_table_pairs(a, S, pb, vec4, stream, "sjoin_fill_v2");
     SG_REQUIRE(packed, SUBGACC_ERR_BADARG, "sjoin_fill_v2: strided / headed rows are joined as mirrored blocks (pair_block > 0)");
     return launch_segments(a, false, vec4, stream);
+}
+
+// The first model stage of the float encoders fused with the join (include/subgacc.h): the descriptor of a mirrored F64 join, no row
+// output.  Every refusal comes before anything is launched.
+extern "C" int subgacc_sjoin_relu_mean(const subgacc_join_desc *d, const float *w1, const float *b1, int32_t H, float *out_mean,
+                                       float *out_p, float *out_q, void *stream) {
+    SG_REQUIRE(d, SUBGACC_ERR_BADARG, "sjoin_relu_mean: null descriptor");
+    SG_REQUIRE(d->struct_bytes == (int32_t)sizeof(subgacc_join_desc), SUBGACC_ERR_BADARG,
+               "sjoin_relu_mean: descriptor of %d bytes, this library's is %d (set struct_bytes = sizeof(subgacc_join_desc))",
+               (int)d->struct_bytes, (int)sizeof(subgacc_join_desc));
+    const bool packed = d->row_off != nullptr, strided = d->row_len != nullptr;
+    const bool headed = !packed && !strided && d->row_stride > 1;
+    const int64_t S = d->S, pb = d->pair_block;
+    SG_REQUIRE(d->payload_kind == SUBGACC_JOIN_F64, SUBGACC_ERR_BADARG,
+               "sjoin_relu_mean: the fused stage joins a float payload (F64), not payload kind %d", (int)d->payload_kind);
+    SG_REQUIRE(!strided, SUBGACC_ERR_BADARG, "sjoin_relu_mean: joins packed or headed rows, not strided rows");
+    SG_REQUIRE(packed != headed, SUBGACC_ERR_BADARG,
+               "sjoin_relu_mean: exactly one of row_off (packed rows) / row_stride > 1 (headed rows)");
+    SG_REQUIRE(packed || d->row_stride < (1ll << 31), SUBGACC_ERR_BADARG, "sjoin_relu_mean: row_stride = %lld", (long long)d->row_stride);
+    SG_REQUIRE(d->form == SUBGACC_JOIN_ROWS && d->options == 0, SUBGACC_ERR_BADARG,
+               "sjoin_relu_mean: form must be ROWS and options 0 (form %d, options %d)", (int)d->form, (int)d->options);
+    SG_REQUIRE(pb > 0, SUBGACC_ERR_BADARG, "sjoin_relu_mean: needs a mirrored list, pair_block > 0 (pair_block = %lld)", (long long)pb);
+    SG_REQUIRE(S >= 0 && S % (2 * pb) == 0, SUBGACC_ERR_BADARG,
+               "sjoin_relu_mean: S = %lld is not a multiple of 2*pair_block = %lld", (long long)S, (long long)(2 * pb));
+    SG_REQUIRE(d->own || S == 0, SUBGACC_ERR_BADARG, "sjoin_relu_mean: own = NULL with S = %lld segments", (long long)S);
+    SG_REQUIRE(w1 && b1 && out_mean, SUBGACC_ERR_BADARG, "sjoin_relu_mean: w1, b1 and out_mean are required (a NULL one given)");
+    SG_REQUIRE(H >= 1 && H <= 1024, SUBGACC_ERR_BADARG, "sjoin_relu_mean: H = %d outside [1, 1024]", (int)H);
+    SG_REQUIRE((out_p == nullptr) == (out_q == nullptr), SUBGACC_ERR_BADARG, "sjoin_relu_mean: out_p and out_q go together (one is NULL)");
+    SG_REQUIRE(!d->out_xz && !d->out_idx && !d->out_segid && !d->out_counts && !d->out_pairs && !d->out_mult && !d->out_cnt &&
+                   !d->out_seg && !d->seg,
+               SUBGACC_ERR_BADARG, "sjoin_relu_mean: writes out_mean (out_p, out_q) only: the descriptor's out_* and seg fields must be NULL");
+    SG_REQUIRE(d->n_rows >= 0 && d->max_len >= 0, SUBGACC_ERR_BADARG, "sjoin_relu_mean: bad arguments");
+    if (S == 0) return SUBGACC_OK;
+    SG_REQUIRE(d->flags && d->ids && d->payload, SUBGACC_ERR_BADARG, "sjoin_relu_mean: null argument (flags / ids / payload)");
+    JoinArgs a;
+    a.indptr = d->row_off, a.indices = headed ? d->ids + 1 : d->ids, a.data = d->payload;
+    a.row_len = nullptr, a.row_stride = packed ? 0 : d->row_stride, a.row_head = headed ? d->ids : nullptr;
+    a.pb = pb, a.own = d->own, a.partner = d->partner, a.seg = nullptr, a.S = S, a.n_rows = d->n_rows;
+    a.table = nullptr, a.table_rows = 0, a.k = 1;
+    a.out_xz = nullptr, a.out_idx = nullptr, a.out_segid = nullptr;
+    a.max_len = packed ? (d->max_len > 0 ? d->max_len : 1) : (int32_t)(d->row_stride - 1);
+    a.flags = d->flags;
+    a.slot_id = nullptr, a.val_add = 0;
+    a.key_M = a.key_m = a.key_shift = 0;
+    a.spec_len = packed ? 0 : (d->max_len > 0 ? d->max_len : (int32_t)(a.max_len < 128 ? a.max_len : 128));
+    a.split = 1;
+    // headed rows that the row form does not join are refused as it refuses them (sjoin_fill_v2: no one-segment kernel for them)
+    SG_REQUIRE(packed || (size_t)a.max_len * 20 + 16 <= (size_t)kLdsBytes, SUBGACC_ERR_BADARG,
+               "sjoin_relu_mean: headed float rows of %d members do not fit LDS (the row form refuses them too)", (int)a.max_len);
+    const int32_t cap = a.max_len < kMeanCap ? a.max_len : kMeanCap;
+    const size_t lds = (size_t)cap * 16 + (size_t)((cap + 1) & ~1) * 4 + (size_t)(cap > kMeanThreads ? cap : kMeanThreads) * 8;
+    SG_REQUIRE(S / 2 < (1ll << 31), SUBGACC_ERR_BADARG, "sjoin_relu_mean: too many segments in one call");
+    const int64_t grid = xcd_grid(S / 2);
+    SG_REQUIRE(grid < (1ll << 31), SUBGACC_ERR_BADARG, "sjoin_relu_mean: too many segments in one call");
+    MeanArgs m{w1, b1, H, out_mean, out_p, out_q};
+    hipStream_t s = (hipStream_t)stream;
+    if (out_p)
+        hipLaunchKernelGGL((sjoin_f64mean_kernel<true>), dim3((unsigned)grid), dim3(kMeanThreads), lds, s, a, (uint32_t)pb, (uint32_t)(S / 2), cap, m);
+    else
+        hipLaunchKernelGGL((sjoin_f64mean_kernel<false>), dim3((unsigned)grid), dim3(kMeanThreads), lds, s, a, (uint32_t)pb, (uint32_t)(S / 2), cap, m);
+    SG_LAUNCH_CHECK();
+    return SUBGACC_OK;
 }

@@ -5,6 +5,7 @@ same argument meaning, same return values (xz float32 [R,2,k], indptr-or-segment
 `x` is an SpG (surel_plus_amd.spg.SpG) or a scipy CSR (uploaded once and cached), `encode` the Z_SF table
 as a float32 CUDA tensor or None for a float payload.  The work is done by csrc/sjoin.hip.
 """
+import ctypes
 import os
 import threading
 import weakref
@@ -970,3 +971,106 @@ def lstm_stage(edge, x, encode, embed, lstm):
     dense[seg, posn] = rows
     out = lstm(dense)[0][:, -1]
     return out.view(2, -1, out.shape[-1])
+
+
+def _relu_mlp(embed):
+    """(Linear(1, H), Linear(H, H')) of embed = Sequential(Linear(1, H), ReLU(), Linear(H, H')) -- the reference's pe_embedding for the
+    float encoders (model.py:54-55, input_dim = 1) -- or TypeError"""
+    nn = torch.nn
+    if not (isinstance(embed, nn.Sequential) and len(embed) == 3 and isinstance(embed[0], nn.Linear) and isinstance(embed[1], nn.ReLU)
+            and isinstance(embed[2], nn.Linear) and embed[0].in_features == 1 and embed[2].in_features == embed[0].out_features):
+        raise TypeError("float_mean_stage fuses embed = Sequential(Linear(1, H), ReLU(), Linear(H, H')) only; for any other module "
+                        "use xz, ind = gather(edge, x) and the module on xz")
+    return embed[0], embed[2]
+
+
+def _edge_rows(edge):
+    """float_mean_stage's `edge` checked on the host: a [2, B] integer array (torch or NumPy), before any device work"""
+    if not torch.is_tensor(edge):
+        try:
+            edge = np.asarray(edge)
+        except ValueError as e:             # (NumPy >= 1.24 refuses a ragged nested list itself)
+            raise ValueError(f"float_mean_stage: edge must be a [2, B] integer array ({e})") from None
+        ok = edge.dtype != object and np.issubdtype(edge.dtype, np.integer)
+    else:
+        ok = not edge.dtype.is_floating_point and not edge.dtype.is_complex and edge.dtype != torch.bool
+    if not ok or edge.ndim != 2 or edge.shape[0] != 2:
+        raise ValueError(f"float_mean_stage: edge must be a [2, B] integer array, got {getattr(edge, 'dtype', type(edge))} "
+                         f"of shape {tuple(getattr(edge, 'shape', ()))}")
+    return edge
+
+
+class _ReluMean(torch.autograd.Function):
+    """M [S, H] of subgacc_sjoin_relu_mean as a function of (w1, b1); backward: dL/dw1 = sum_j G_j * P_j, dL/db1 = sum_j G_j * Q_j with
+    the P / Q sums the forward asked the kernel for"""
+
+    @staticmethod
+    def forward(ctx, w1, b1, join):
+        M, P, Q = join(w1.detach().contiguous(), b1.detach().contiguous())
+        ctx.save_for_backward(P, Q)
+        return M
+
+    @staticmethod
+    def backward(ctx, G):
+        P, Q = ctx.saved_tensors
+        return (G * P).sum(0), (G * Q).sum(0), None
+
+
+def float_mean_stage(edge, x, embed):
+    """The reference's first model stage for the float encoders (PPR, SPD, DEG: utils.py:20-38, main.py:170-196), fused:  model.py:78-83
+        x = pe_embedding(xz).sum(dim=-2);  xl, xr = aggr.MeanAggregation()(x, ptr=ptr).view(2, -1, H)
+    with pe_embedding = embed = Sequential(Linear(1, H), ReLU(), Linear(H, H')) over the float join's xz [R,2,1].  Mean aggregation is
+    linear, so the stage is  W2 M_j + 2 b2  per segment, M_j = mean over the segment's rows of relu(w1 a + b1) + relu(w1 b + b1): the
+    library's fused kernel (subgacc_sjoin_relu_mean) joins the pairs and writes M [2B, H] -- neither xz nor the [R,2,H] activations
+    exist.  Autograd reaches all four parameters: w1 / b1 through the per-segment sums the kernel writes for the backward (only when
+    grad is enabled and one of them requires it), W2 / b2 through ordinary torch ops.
+    edge: [2, B] integer (torch or NumPy); x: a float64 SpG or HeadedSpG (topk_ppr_matrix / ppr.encoding).
+    Returns float32 [2, B, H'] (left endpoints, right endpoints) as mean_stage does; empty segments give zero rows.  The result
+    carries the join's status words as .join_flags (flags[1] & 2: a pair with a row too long to stage streamed)."""
+    lin1, lin2 = _relu_mlp(embed)
+    H = lin1.out_features
+    if not 1 <= H <= 1024:
+        raise ValueError(f"float_mean_stage: Linear(1, H) with H = {H}; the fused stage takes 1 <= H <= 1024")
+    if isinstance(x, StridedSpG):
+        raise TypeError("float_mean_stage joins a resident float store (SpG or HeadedSpG), not a StridedSpG")
+    if not isinstance(x, (SpG, HeadedSpG)):
+        raise TypeError(f"float_mean_stage joins a float64 SpG or HeadedSpG, not {type(x).__name__}")
+    if x.keyrows or x.data.dtype != torch.float64:
+        raise TypeError("float_mean_stage joins a float (PPR / SPD / DEG) store; an integer (LP) store has mean_stage(edge, x, encode, "
+                        "embed)")
+    edge = _edge_rows(edge)
+    dev = x.device
+    if lin1.weight.device != dev or lin2.weight.device != dev or lin1.weight.dtype != torch.float32:
+        raise ValueError(f"float_mean_stage: embed must hold float32 parameters on the store's device ({dev})")
+    e = _as_rows(edge, dev)
+    B = int(e.shape[1])
+    own = e.contiguous().view(-1)
+    _, rows = x.join_rows()
+    flags = torch.zeros(4, dtype=torch.int32, device=dev)
+    w1 = lin1.weight.view(-1)
+    b1 = lin1.bias if lin1.bias is not None else torch.zeros(H, dtype=torch.float32, device=dev)
+    grads = torch.is_grad_enabled() and (w1.requires_grad or b1.requires_grad)
+
+    def join(w, b):
+        M = torch.empty((2 * B, H), dtype=torch.float32, device=dev)
+        P, Q = (torch.empty_like(M), torch.empty_like(M)) if grads else (None, None)
+        if B == 0:          # (an empty list has no pair_block the library would accept)
+            return M, P, Q
+        with _timed("sjoin_relu_mean"):
+            d = _lib.join_desc(JOIN_ROWS, JOIN_F64, **rows, own=own, S=2 * B, pair_block=B, flags=flags)
+            check(lib().subgacc_sjoin_relu_mean(ctypes.byref(d), ptr(w), ptr(b), H, ptr(M), ptr(P), ptr(Q), stream_ptr()))
+        status = int(flags[3].item())
+        if status & 16:
+            raise IndexError(f"row index out of range for an SpG with {x.n_rows} rows")
+        if status & 1:
+            raise _lib.SubgAccError("SpG row longer than SpG.max_len")
+        return M, P, Q
+
+    M = _ReluMean.apply(w1, b1, join) if grads else join(w1.detach(), b1.detach())[0]
+    sizes = rows["row_off"][own + 1] - rows["row_off"][own] if "row_off" in rows else rows["ids"][own * rows["row_stride"]]
+    h = torch.nn.functional.linear(M, lin2.weight)
+    if lin2.bias is not None:
+        h = h + 2 * lin2.bias
+    out = (h * (sizes > 0).to(h.dtype)[:, None]).view(2, B, h.shape[-1])
+    out.join_flags = flags
+    return out
