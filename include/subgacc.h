@@ -379,6 +379,40 @@ int subgacc_sjoin_fill_v2(const subgacc_join_desc *d, void *stream);
 int subgacc_sjoin_relu_mean(const subgacc_join_desc *d, const float *w1, const float *b1, int32_t H, float *out_mean,
                             float *out_p, float *out_q, void *stream);
 
+/* The same first stage with attentional aggregation (--aggr attn: model.py:59-62,78-81, torch_geometric 2.2's
+ * AttentionalAggregation(gate_nn, nn) with one-Linear gate_nn (wg, bg) and nn).  Every step after r_t is affine: for segment j with
+ * rows (a_t, b_t), r_t[c] = relu(fmaf(w1[c], a_t, b1[c])) + relu(fmaf(w1[c], b_t, b1[c])) and x_t = W2 r_t + 2 b2, the gate is
+ * u . r_t + (a constant softmax drops) with u = W2^T wg, and out_j = nn(W2 A_j + 2 b2) [n_j > 0] with A_j the softmax-weighted mean of
+ * r_t.  The join writes only (f32 [S, H])
+ *     A_j[c] = (sum_t e_t r_t[c]) / den_j,   e_t = expf(l_t - m_j),  l_t = u . r_t,  m_j = max_t l_t,  den_j = sum_t e_t
+ * and, when the backward is wanted, out_max / out_den (both or neither; f32 [S]) receive m_j and den_j.  (den_j >= 1, so PyG's
+ * den + 1e-16 is den in fp32.)  (a_t, b_t) are the rows the row form writes, as for subgacc_sjoin_relu_mean.
+ * Summation order, the same on every path (packed or headed rows, staged or streamed, every run): l_t = an fp32 fmaf chain over c
+ * ascending from 0, l = fmaf(u[c], r_t[c], l), r_t[c] the a-term plus the b-term; den_j and every A_j[c] (acc = fmaf(e_t, r_t[c],
+ * acc)) over the own row's members in ascending id order from 0, then one IEEE division; m_j a max (order-free); expf, never __expf.
+ * An empty segment (n_j = 0, or a row outside the store) gives a zero row and m_j = den_j = 0.
+ *   d        as subgacc_sjoin_relu_mean's (a mirrored row-form join of an F64 store, packed or headed rows, no seg, no out_*).
+ *   w1, b1   f32 [H]: Linear(1, H)'s weight and bias (a zero b1 for a Linear without bias); u f32 [H]; 1 <= H <= 1024.
+ * Flags as subgacc_sjoin_relu_mean's: flags[3] |= 16 a row outside the store, |= 1 a packed row longer than max_len, |= 4 a list that is
+ * not mirrored; flags[1] |= 2 a pair with a row longer than 1,024 members streamed (one pass for m_j, one for den_j and A_j).
+ * Refused with SUBGACC_ERR_BADARG before anything is launched: a payload other than F64, strided rows, form != ROWS or any option bit,
+ * pair_block <= 0 or S not a multiple of 2*pair_block, own = NULL with S > 0, w1 / b1 / u / out_a NULL, H outside [1, 1024],
+ * exactly one of out_max / out_den, any out_* or seg field of the descriptor set, headed rows the row form refuses. */
+int subgacc_sjoin_relu_attn(const subgacc_join_desc *d, const float *w1, const float *b1, const float *u, int32_t H, float *out_a,
+                            float *out_max, float *out_den, void *stream);
+
+/* The backward of subgacc_sjoin_relu_attn over the same descriptor: g = dL/dA, a = A, max / den = m, den as the forward wrote them.
+ * The pair is joined again and r_t, e_t recomputed bit for bit; alpha_t = e_t / den_j, beta_t = alpha_t (G_j . r_t - G_j . A_j) (both
+ * dot products fmaf chains over c ascending), dr_t[c] = fmaf(alpha_t, G_j[c], beta_t u[c]).  Written per segment (f32 [S, H], no
+ * atomics: dL/du = sum_j Du_j, dL/dw1 = sum_j Dw_j, dL/db1 = sum_j Db_j):
+ *     Du_j[c] = sum_t beta_t r_t[c],  Dw_j[c] = sum_t dr_t[c] (a_t [ya > 0] + b_t [yb > 0]),  Db_j[c] = sum_t dr_t[c] ([ya > 0] + [yb > 0])
+ * with ya = fmaf(w1[c], a_t, b1[c]), yb likewise (ReLU's gradient at 0 is 0), each an fmaf chain over the own row's members in
+ * ascending id order from 0; an empty segment gives zero rows.  Flags and refusals as the forward's; g, a, max, den and the three
+ * outputs are required. */
+int subgacc_sjoin_relu_attn_backward(const subgacc_join_desc *d, const float *w1, const float *b1, const float *u, int32_t H,
+                                     const float *g, const float *a, const float *max, const float *den, float *out_dw, float *out_db,
+                                     float *out_du, void *stream);
+
 
 /* Packed rows -> headed rows (ABI 7): the resident store of a serving loop laid out on whole lines -- the rows random_walks.py:79-81
  * builds as a SciPy CSR and train.py:17-18 / :39-43 slice one by one (x[edge[0]]), in the layout the pair kernels read with one

@@ -13,11 +13,13 @@
 //   sjoin_f64pair_kernel                the same plan for the PPR encoder's float payload (train.py:39-43)
 //   sjoin_f64mean_kernel                the same join fused with the float encoders' first model stage (model.py:78-83): per segment
 //                                       the mean of relu(w1 s + b1) over its pairs, no output row (subgacc_sjoin_relu_mean)
+//   sjoin_f64attn_kernel<BWD>           the same with attentional aggregation (model.py:59-62,78-81): per segment the softmax-weighted
+//                                       mean of relu(w1 s + b1), and its backward (subgacc_sjoin_relu_attn[_backward])
 //   sjoin_fill_kernel                   any other list: one wave per segment, the partner row in LDS (or searched in place when it
 //                                       does not fit)
 //   sjoin_counts_kernel / sjoin_pairs_kernel   the count and pair forms of the join
-// One entry point for every form of the join, subgacc_sjoin_fill_v2(descriptor), and subgacc_sjoin_relu_mean for the fused stage,
-// at the end of the file.
+// One entry point for every form of the join, subgacc_sjoin_fill_v2(descriptor), and subgacc_sjoin_relu_mean / _relu_attn /
+// _relu_attn_backward for the fused stages, at the end of the file.
 // The [R,2] index array of the reference never exists in memory unless asked for (out_idx).
 #include <cstdlib>
 #include "common.hpp"
@@ -1200,23 +1202,49 @@ __device__ __forceinline__ void relu_mean_store(const MeanArgs &m, int64_t j, in
 constexpr int kMeanThreads = kPairEmit;
 constexpr int kMeanCap = 1024;     // longest row staged by sjoin_f64mean_kernel (28 KiB of LDS); longer ones stream
 
+// A pair that f64pair_stage hands over with a row longer than the kernel stages.  f64stream_begin: false for a packed row longer than
+// max_len (the row form's flags[3] & 1: not joined), else flags[1] |= 2 and the pair streams.  f64stream_rows: the own row (ob, on)
+// of the pair's side 0 (ra) or 1 (rb) and its partner row (qb, qn).  f64stream_member: member t of the own row as the row form
+// writes it, (own value, partner value or 0.0), the partner row searched where it lies.
+__device__ __forceinline__ bool f64stream_begin(const JoinArgs &a, const F64Pair &p) {
+    if (a.row_stride == 0 && (p.na > a.max_len || p.nb > a.max_len)) {
+        if (threadIdx.x == 0) atomicOr(&a.flags[3], 1);
+        return false;
+    }
+    if (threadIdx.x == 0) atomicOr(&a.flags[1], 2);
+    return true;
+}
+
+__device__ __forceinline__ void f64stream_rows(const JoinArgs &a, const F64Pair &p, int side, int64_t &ob, int64_t &on, int64_t &qb,
+                                               int64_t &qn) {
+    join_row(a, side ? p.rb : p.ra, ob, on);
+    join_row(a, side ? p.ra : p.rb, qb, qn);
+}
+
+__device__ __forceinline__ float2 f64stream_member(const JoinArgs &a, int64_t ob, int64_t qb, int64_t qn, int64_t t) {
+    const double *vals = (const double *)a.data;
+    const int32_t *qids = a.indices + qb;
+    const int32_t id = a.indices[ob + t];
+    int64_t lo = 0, hi = qn;          // lower bound of id in the partner row
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (qids[mid] < id) lo = mid + 1;
+        else hi = mid;
+    }
+    const double got = lo < qn && qids[lo] == id ? vals[qb + lo] : 0.0;
+    return make_float2((float)vals[ob + t], (float)((got + 1.0) - 1.0));
+}
+
 // a pair with a row longer than the kernel stages: each segment's own row in chunks of NT members, every member searched in the partner
 // row where it lies, the chunk's pairs in LDS (ab[NT]) summed by the channel lanes -- the staged path's sequence of additions
 template <bool PQ>
 __device__ __forceinline__ void f64mean_stream(const JoinArgs &a, const F64Pair &p, const MeanArgs &m, float2 *ab) {
     constexpr int NT = kMeanThreads;
     const int tid = threadIdx.x, H = m.H;
-    if (a.row_stride == 0 && (p.na > a.max_len || p.nb > a.max_len)) {     // the row form's flags[3] & 1: not joined
-        if (tid == 0) atomicOr(&a.flags[3], 1);
-        return;
-    }
-    if (tid == 0) atomicOr(&a.flags[1], 2);
-    const double *vals = (const double *)a.data;
+    if (!f64stream_begin(a, p)) return;
     for (int side = 0; side < 2; ++side) {
         int64_t ob, on, qb, qn;
-        join_row(a, side ? p.rb : p.ra, ob, on);
-        join_row(a, side ? p.ra : p.rb, qb, qn);
-        const int32_t *qids = a.indices + qb;
+        f64stream_rows(a, p, side, ob, on, qb, qn);
         for (int c0 = 0; c0 < H; c0 += NT) {
             const int c = c0 + tid;
             const bool live = c < H;
@@ -1224,17 +1252,7 @@ __device__ __forceinline__ void f64mean_stream(const JoinArgs &a, const F64Pair 
             float sm = 0.f, sp = 0.f, sq = 0.f;
             for (int64_t t0 = 0; t0 < on; t0 += NT) {
                 __syncthreads();                      // the previous chunk is summed
-                if (t0 + tid < on) {
-                    const int32_t id = a.indices[ob + t0 + tid];
-                    int64_t lo = 0, hi = qn;          // lower bound of id in the partner row, where it lies
-                    while (lo < hi) {
-                        const int64_t mid = (lo + hi) >> 1;
-                        if (qids[mid] < id) lo = mid + 1;
-                        else hi = mid;
-                    }
-                    const double got = lo < qn && qids[lo] == id ? vals[qb + lo] : 0.0;
-                    ab[tid] = make_float2((float)vals[ob + t0 + tid], (float)((got + 1.0) - 1.0));
-                }
+                if (t0 + tid < on) ab[tid] = f64stream_member(a, ob, qb, qn, t0 + tid);
                 __syncthreads();
                 if (live) relu_mean_add<PQ>(ab, (int)(on - t0 < NT ? on - t0 : NT), w, b, sm, sp, sq);
             }
@@ -1280,6 +1298,247 @@ __global__ __launch_bounds__(kMeanThreads) void sjoin_f64mean_kernel(const JoinA
         float sm = 0.f, sp = 0.f, sq = 0.f;
         relu_mean_add<PQ>(onT ? abT : abS, n, m.w1[c], m.b1[c], sm, sp, sq);
         relu_mean_store<PQ>(m, onT ? p.jT : p.jS, c, n, sm, sp, sq);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The first model stage of the PPR / SPD / DEG encoders for --aggr attn fused with the join (subgacc_sjoin_relu_attn, model.py:59-62,
+// 78-81 with pe_embedding = Sequential(Linear(1, H), ReLU, Linear(H, H')) and one-Linear gate / value nets).  Everything after
+// r_t[c] = relu(fmaf(w1[c], a_t, b1[c])) + relu(fmaf(w1[c], b_t, b1[c])) is affine, so per segment j the kernel writes only
+//     A_j[c] = (sum_t e_t r_t[c]) / den_j,   e_t = expf(l_t - m_j),  l_t = u . r_t,  m_j = max_t l_t,  den_j = sum_t e_t
+// (u = W2^T wg); the backward kernel rejoins the pair and writes the per-segment sums for u, w1 and b1.  Summation order
+// (include/subgacc.h), the same on every path: l_t an fma chain over c ascending, den_j and every channel's sum over the own row's
+// members in ascending id order, one expf.  The layout is sjoin_f64mean_kernel's: one workgroup per mirrored pair, rows of up to `cap`
+// members staged by f64pair_stage, longer ones streamed chunk by chunk (flags[1] |= 2) with the same per-member and per-channel
+// sequences.  Per-member work (logits; exp; alpha, beta) goes on lanes over members, the channel sums on lanes over channels.
+struct AttnArgs {
+    const float *w1, *b1, *u;
+    int32_t H;
+    float *out_a, *out_max, *out_den;           // forward (out_max / out_den: both or neither)
+    const float *g, *a, *max, *den;             // backward: dL/dA and the forward's A, m, den
+    float *out_dw, *out_db, *out_du;            // backward
+};
+
+// r_t[c]: the a-term, then the b-term (relu_mean_add's order)
+__device__ __forceinline__ float attn_r(float w, float b, float2 s, float &ya, float &yb) {
+    ya = fmaf(w, s.x, b), yb = fmaf(w, s.y, b);
+    return (ya > 0.f ? ya : 0.f) + (yb > 0.f ? yb : 0.f);
+}
+
+// l = u . r (and, with G, gr = G . r): fma chains over c ascending from 0
+template <bool GR>
+__device__ __forceinline__ float attn_logit(const AttnArgs &m, float2 s, const float *G, float &gr) {
+    float l = 0.f;
+    gr = 0.f;
+    for (int c = 0; c < m.H; ++c) {
+        float ya, yb;
+        const float r = attn_r(m.w1[c], m.b1[c], s, ya, yb);
+        l = fmaf(m.u[c], r, l);
+        if (GR) gr = fmaf(G[c], r, gr);
+    }
+    return l;
+}
+
+__device__ __forceinline__ float wave_max_f32(float v) {
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, kWave));
+    return v;
+}
+
+// the forward's channel sums over n members (their pairs ab, their e) added to den / acc in ascending order
+__device__ __forceinline__ void attn_fwd_add(const float2 *ab, const float *e, int n, float w, float b, float &den, float &acc) {
+    for (int t = 0; t < n; ++t) {
+        float ya, yb;
+        const float r = attn_r(w, b, ab[t], ya, yb);
+        den += e[t];
+        acc = fmaf(e[t], r, acc);
+    }
+}
+
+__device__ __forceinline__ void attn_fwd_store(const AttnArgs &m, int64_t j, int c, int n, float den, float acc) {
+    m.out_a[j * m.H + c] = n ? acc / den : 0.f;
+    if (c == 0 && m.out_den) m.out_den[j] = n ? den : 0.f;
+}
+
+// the backward's per-member factors: alpha_t = e_t / den_j, beta_t = alpha_t (G_j . r_t - G_j . A_j)
+__device__ __forceinline__ void attn_member_grad(const AttnArgs &m, float2 s, const float *G, float mj, float denj, float gA, float &al,
+                                                 float &be) {
+    float gr;
+    const float l = attn_logit<true>(m, s, G, gr);
+    al = expf(l - mj) / denj;
+    be = al * (gr - gA);
+}
+
+// G_j . A_j: an fma chain over c ascending
+__device__ __forceinline__ float attn_ga(const AttnArgs &m, int64_t j) {
+    const float *G = m.g + j * m.H, *A = m.a + j * m.H;
+    float s = 0.f;
+    for (int c = 0; c < m.H; ++c) s = fmaf(G[c], A[c], s);
+    return s;
+}
+
+// the backward's channel sums over n members, in ascending order:  dr = alpha G[c] + beta u[c];  du += beta r;
+// dw += dr (a [ya > 0] + b [yb > 0]);  db += dr ([ya > 0] + [yb > 0])
+__device__ __forceinline__ void attn_bwd_add(const float2 *ab, const float *al, const float *be, int n, float w, float b, float uc, float gc,
+                                             float &dw, float &db, float &du) {
+    for (int t = 0; t < n; ++t) {
+        const float2 s = ab[t];
+        float ya, yb;
+        const float r = attn_r(w, b, s, ya, yb);
+        const float dr = fmaf(al[t], gc, be[t] * uc);
+        du = fmaf(be[t], r, du);
+        dw = fmaf(dr, (ya > 0.f ? s.x : 0.f) + (yb > 0.f ? s.y : 0.f), dw);
+        db = fmaf(dr, (ya > 0.f ? 1.f : 0.f) + (yb > 0.f ? 1.f : 0.f), db);
+    }
+}
+
+__device__ __forceinline__ void attn_bwd_store(const AttnArgs &m, int64_t j, int c, float dw, float db, float du) {
+    const int64_t o = j * m.H + c;
+    m.out_dw[o] = dw, m.out_db[o] = db, m.out_du[o] = du;
+}
+
+// a pair with a row longer than the kernel stages, side by side: the own row in chunks of NT members (f64stream_member), the same
+// per-member and per-channel sequences as the staged path.  Forward: one pass for m_j (a block max), then per block of NT channels one
+// pass for den_j and the sums.  Backward: per block of NT channels one pass.  ab / x / y hold the current chunk, red[NW] the block max.
+template <bool BWD>
+__device__ __forceinline__ void f64attn_stream(const JoinArgs &a, const F64Pair &p, const AttnArgs &m, float2 *ab, float *x, float *y,
+                                               float *red) {
+    constexpr int NT = kMeanThreads, NW = NT / kWave;
+    const int tid = threadIdx.x, H = m.H;
+    if (!f64stream_begin(a, p)) return;
+    for (int side = 0; side < 2; ++side) {
+        int64_t ob, on, qb, qn;
+        f64stream_rows(a, p, side, ob, on, qb, qn);
+        const int64_t j = side ? p.j2 : p.j;
+        float mj = 0.f, denj = 1.f, gA = 0.f;
+        const float *G = BWD ? m.g + j * H : nullptr;
+        if (BWD) {
+            mj = m.max[j], denj = m.den[j];
+            if (on) gA = attn_ga(m, j);
+        } else {
+            float mx = -INFINITY, gr;
+            for (int64_t t = tid; t < on; t += NT) mx = fmaxf(mx, attn_logit<false>(m, f64stream_member(a, ob, qb, qn, t), nullptr, gr));
+            mx = wave_max_f32(mx);
+            __syncthreads();                          // red is free (the previous side read it)
+            if ((tid & (kWave - 1)) == 0) red[tid / kWave] = mx;
+            __syncthreads();
+            mj = red[0];
+            for (int w = 1; w < NW; ++w) mj = fmaxf(mj, red[w]);
+            if (tid == 0 && m.out_max) m.out_max[j] = on ? mj : 0.f;
+        }
+        for (int c0 = 0; c0 < H; c0 += NT) {
+            const int c = c0 + tid;
+            const bool live = c < H;
+            const float w = live ? m.w1[c] : 0.f, b = live ? m.b1[c] : 0.f;
+            const float uc = BWD && live ? m.u[c] : 0.f, gc = BWD && live ? G[c] : 0.f;
+            float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+            for (int64_t t0 = 0; t0 < on; t0 += NT) {
+                __syncthreads();                      // the previous chunk is summed
+                if (t0 + tid < on) {
+                    const float2 s = f64stream_member(a, ob, qb, qn, t0 + tid);
+                    ab[tid] = s;
+                    if (BWD) {
+                        attn_member_grad(m, s, G, mj, denj, gA, x[tid], y[tid]);
+                    } else {
+                        float gr;
+                        x[tid] = expf(attn_logit<false>(m, s, nullptr, gr) - mj);
+                    }
+                }
+                __syncthreads();
+                const int n = (int)(on - t0 < NT ? on - t0 : NT);
+                if (live) {
+                    if (BWD) attn_bwd_add(ab, x, y, n, w, b, uc, gc, s0, s1, s2);
+                    else attn_fwd_add(ab, x, n, w, b, s0, s1);
+                }
+            }
+            if (live) {
+                if (BWD) attn_bwd_store(m, j, c, s0, s1, s2);
+                else attn_fwd_store(m, j, c, (int)on, s0, s1);
+            }
+        }
+    }
+}
+
+// the forward (BWD = false: A, and m / den when asked for) and the backward (BWD: the per-segment sums for w1, b1, u) of the fused
+// attention stage.  LDS: f64pair_stage's arrays, S's pairs abS, per-member factors xS / yS for S (forward: e; backward: alpha, beta) and
+// xT / yT for T -- over pv, free once T's pairs are float2s --, red[NW].
+template <bool BWD>
+__global__ __launch_bounds__(kMeanThreads) void sjoin_f64attn_kernel(const JoinArgs a, uint32_t pb, uint32_t pairs, int32_t cap,
+                                                                     const AttnArgs m) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    constexpr int NT = kMeanThreads, NW = NT / kWave;
+    const int SC = cap > NT ? cap : NT;
+    double *valT = (double *)lds_raw;                 // [cap] values of T; after the search T's pairs as float2, in place
+    double *pv = valT + cap;                          // [cap] partner values of T's members; then xT / yT
+    int32_t *idsT = (int32_t *)(pv + cap);            // [cap]
+    float2 *abS = (float2 *)(idsT + ((cap + 1) & ~1));   // [SC] S's pairs (streaming: the current chunk's)
+    float *xS = (float *)(abS + SC), *yS = xS + SC;   // [SC] each
+    float *red = yS + SC;                             // [NW]
+    const int tid = threadIdx.x, lane = tid & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(tid / kWave);
+    const int H = m.H;
+    F64Pair p;
+    const auto span_s = [&](int t, bool emit, double v, double got) {
+        if (emit) abS[t] = make_float2((float)v, (float)((got + 1.0) - 1.0));
+    };
+    const auto bad_rows = [&]() {       // (the row form's size pass raises this one)
+        if (tid == 0 && !(p.okA && p.okB)) atomicOr(&a.flags[3], 16);
+    };
+    if (!f64pair_stage<NT, false>(a, pb, pairs, cap, valT, pv, idsT, p, span_s, [&]() {
+            bad_rows();
+            f64attn_stream<BWD>(a, p, m, abS, xS, yS, red);
+        }))
+        return;
+    bad_rows();
+    __syncthreads();                                  // pv complete
+    float2 *abT = (float2 *)valT;
+    for (int t = tid; t < p.nt; t += NT) {            // the thread that reads slot t writes it
+        const double v = valT[t], got = pv[t];
+        abT[t] = make_float2((float)v, (float)((got + 1.0) - 1.0));
+    }
+    __syncthreads();                                  // pv is free
+    float *xT = (float *)pv, *yT = xT + cap;
+    // per-member factors, side by side (side 0: S, 1: T)
+    for (int side = 0; side < 2; ++side) {
+        const float2 *ab = side ? abT : abS;
+        float *x = side ? xT : xS, *y = side ? yT : yS;
+        const int n = side ? p.nt : p.ns;
+        const int64_t j = side ? p.jT : p.jS;
+        if (BWD) {
+            if (!n) continue;
+            const float *G = m.g + j * H;
+            const float mj = m.max[j], denj = m.den[j], gA = attn_ga(m, j);
+            for (int t = tid; t < n; t += NT) attn_member_grad(m, ab[t], G, mj, denj, gA, x[t], y[t]);
+        } else {
+            float gr;
+            for (int t = tid; t < n; t += NT) x[t] = attn_logit<false>(m, ab[t], nullptr, gr);
+        }
+    }
+    if (!BWD) {                                       // one wave per side: m_j, then e_t = expf(l_t - m_j) in place
+        __syncthreads();
+        for (int side = wave; side < 2; side += NW) {
+            float *x = side ? xT : xS;
+            const int n = side ? p.nt : p.ns;
+            float mx = -INFINITY;
+            for (int t = lane; t < n; t += kWave) mx = fmaxf(mx, x[t]);
+            mx = wave_max_f32(mx);
+            for (int t = lane; t < n; t += kWave) x[t] = expf(x[t] - mx);
+            if (lane == 0 && m.out_max) m.out_max[side ? p.jT : p.jS] = n ? mx : 0.f;
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < 2 * H; i += NT) {
+        const bool onT = i >= H;
+        const int c = onT ? i - H : i, n = onT ? p.nt : p.ns;
+        const int64_t j = onT ? p.jT : p.jS;
+        float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+        if (BWD) {
+            attn_bwd_add(onT ? abT : abS, onT ? xT : xS, onT ? yT : yS, n, m.w1[c], m.b1[c], m.u[c], n ? m.g[j * H + c] : 0.f, s0, s1, s2);
+            attn_bwd_store(m, j, c, s0, s1, s2);
+        } else {
+            attn_fwd_add(onT ? abT : abS, onT ? xT : xS, n, m.w1[c], m.b1[c], s0, s1);
+            attn_fwd_store(m, j, c, n, s0, s1);
+        }
     }
 }
 
@@ -2074,39 +2333,40 @@ extern "C" int subgacc_sjoin_fill_v2(const subgacc_join_desc *d, void *stream) {
     return launch_segments(a, false, vec4, stream);
 }
 
-// The first model stage of the float encoders fused with the join (include/subgacc.h): the descriptor of a mirrored F64 join, no row
-// output.  Every refusal comes before anything is launched.
-extern "C" int subgacc_sjoin_relu_mean(const subgacc_join_desc *d, const float *w1, const float *b1, int32_t H, float *out_mean,
-                                       float *out_p, float *out_q, void *stream) {
-    SG_REQUIRE(d, SUBGACC_ERR_BADARG, "sjoin_relu_mean: null descriptor");
+// The first model stages of the float encoders fused with the join (include/subgacc.h): the descriptor of a mirrored F64 join, no row
+// output.  f64stage_check: the descriptor's and H's refusals, shared by every fused stage (`name` leads the message); f64stage_join:
+// for S > 0, the JoinArgs, the staged row cap and the grid.  Every refusal comes before anything is launched.
+static int f64stage_check(const char *name, const subgacc_join_desc *d, int32_t H) {
+    SG_REQUIRE(d, SUBGACC_ERR_BADARG, "%s: null descriptor", name);
     SG_REQUIRE(d->struct_bytes == (int32_t)sizeof(subgacc_join_desc), SUBGACC_ERR_BADARG,
-               "sjoin_relu_mean: descriptor of %d bytes, this library's is %d (set struct_bytes = sizeof(subgacc_join_desc))",
+               "%s: descriptor of %d bytes, this library's is %d (set struct_bytes = sizeof(subgacc_join_desc))", name,
                (int)d->struct_bytes, (int)sizeof(subgacc_join_desc));
     const bool packed = d->row_off != nullptr, strided = d->row_len != nullptr;
     const bool headed = !packed && !strided && d->row_stride > 1;
     const int64_t S = d->S, pb = d->pair_block;
     SG_REQUIRE(d->payload_kind == SUBGACC_JOIN_F64, SUBGACC_ERR_BADARG,
-               "sjoin_relu_mean: the fused stage joins a float payload (F64), not payload kind %d", (int)d->payload_kind);
-    SG_REQUIRE(!strided, SUBGACC_ERR_BADARG, "sjoin_relu_mean: joins packed or headed rows, not strided rows");
-    SG_REQUIRE(packed != headed, SUBGACC_ERR_BADARG,
-               "sjoin_relu_mean: exactly one of row_off (packed rows) / row_stride > 1 (headed rows)");
-    SG_REQUIRE(packed || d->row_stride < (1ll << 31), SUBGACC_ERR_BADARG, "sjoin_relu_mean: row_stride = %lld", (long long)d->row_stride);
+               "%s: the fused stage joins a float payload (F64), not payload kind %d", name, (int)d->payload_kind);
+    SG_REQUIRE(!strided, SUBGACC_ERR_BADARG, "%s: joins packed or headed rows, not strided rows", name);
+    SG_REQUIRE(packed != headed, SUBGACC_ERR_BADARG, "%s: exactly one of row_off (packed rows) / row_stride > 1 (headed rows)", name);
+    SG_REQUIRE(packed || d->row_stride < (1ll << 31), SUBGACC_ERR_BADARG, "%s: row_stride = %lld", name, (long long)d->row_stride);
     SG_REQUIRE(d->form == SUBGACC_JOIN_ROWS && d->options == 0, SUBGACC_ERR_BADARG,
-               "sjoin_relu_mean: form must be ROWS and options 0 (form %d, options %d)", (int)d->form, (int)d->options);
-    SG_REQUIRE(pb > 0, SUBGACC_ERR_BADARG, "sjoin_relu_mean: needs a mirrored list, pair_block > 0 (pair_block = %lld)", (long long)pb);
+               "%s: form must be ROWS and options 0 (form %d, options %d)", name, (int)d->form, (int)d->options);
+    SG_REQUIRE(pb > 0, SUBGACC_ERR_BADARG, "%s: needs a mirrored list, pair_block > 0 (pair_block = %lld)", name, (long long)pb);
     SG_REQUIRE(S >= 0 && S % (2 * pb) == 0, SUBGACC_ERR_BADARG,
-               "sjoin_relu_mean: S = %lld is not a multiple of 2*pair_block = %lld", (long long)S, (long long)(2 * pb));
-    SG_REQUIRE(d->own || S == 0, SUBGACC_ERR_BADARG, "sjoin_relu_mean: own = NULL with S = %lld segments", (long long)S);
-    SG_REQUIRE(w1 && b1 && out_mean, SUBGACC_ERR_BADARG, "sjoin_relu_mean: w1, b1 and out_mean are required (a NULL one given)");
-    SG_REQUIRE(H >= 1 && H <= 1024, SUBGACC_ERR_BADARG, "sjoin_relu_mean: H = %d outside [1, 1024]", (int)H);
-    SG_REQUIRE((out_p == nullptr) == (out_q == nullptr), SUBGACC_ERR_BADARG, "sjoin_relu_mean: out_p and out_q go together (one is NULL)");
+               "%s: S = %lld is not a multiple of 2*pair_block = %lld", name, (long long)S, (long long)(2 * pb));
+    SG_REQUIRE(d->own || S == 0, SUBGACC_ERR_BADARG, "%s: own = NULL with S = %lld segments", name, (long long)S);
+    SG_REQUIRE(H >= 1 && H <= 1024, SUBGACC_ERR_BADARG, "%s: H = %d outside [1, 1024]", name, (int)H);
     SG_REQUIRE(!d->out_xz && !d->out_idx && !d->out_segid && !d->out_counts && !d->out_pairs && !d->out_mult && !d->out_cnt &&
                    !d->out_seg && !d->seg,
-               SUBGACC_ERR_BADARG, "sjoin_relu_mean: writes out_mean (out_p, out_q) only: the descriptor's out_* and seg fields must be NULL");
-    SG_REQUIRE(d->n_rows >= 0 && d->max_len >= 0, SUBGACC_ERR_BADARG, "sjoin_relu_mean: bad arguments");
-    if (S == 0) return SUBGACC_OK;
-    SG_REQUIRE(d->flags && d->ids && d->payload, SUBGACC_ERR_BADARG, "sjoin_relu_mean: null argument (flags / ids / payload)");
-    JoinArgs a;
+               SUBGACC_ERR_BADARG, "%s: writes its own outputs only: the descriptor's out_* and seg fields must be NULL", name);
+    SG_REQUIRE(d->n_rows >= 0 && d->max_len >= 0, SUBGACC_ERR_BADARG, "%s: bad arguments", name);
+    return SUBGACC_OK;
+}
+
+static int f64stage_join(const char *name, const subgacc_join_desc *d, JoinArgs &a, int32_t &cap, int64_t &grid) {
+    const bool packed = d->row_off != nullptr, headed = !packed;
+    const int64_t S = d->S, pb = d->pair_block;
+    SG_REQUIRE(d->flags && d->ids && d->payload, SUBGACC_ERR_BADARG, "%s: null argument (flags / ids / payload)", name);
     a.indptr = d->row_off, a.indices = headed ? d->ids + 1 : d->ids, a.data = d->payload;
     a.row_len = nullptr, a.row_stride = packed ? 0 : d->row_stride, a.row_head = headed ? d->ids : nullptr;
     a.pb = pb, a.own = d->own, a.partner = d->partner, a.seg = nullptr, a.S = S, a.n_rows = d->n_rows;
@@ -2120,18 +2380,77 @@ extern "C" int subgacc_sjoin_relu_mean(const subgacc_join_desc *d, const float *
     a.split = 1;
     // headed rows that the row form does not join are refused as it refuses them (sjoin_fill_v2: no one-segment kernel for them)
     SG_REQUIRE(packed || (size_t)a.max_len * 20 + 16 <= (size_t)kLdsBytes, SUBGACC_ERR_BADARG,
-               "sjoin_relu_mean: headed float rows of %d members do not fit LDS (the row form refuses them too)", (int)a.max_len);
-    const int32_t cap = a.max_len < kMeanCap ? a.max_len : kMeanCap;
+               "%s: headed float rows of %d members do not fit LDS (the row form refuses them too)", name, (int)a.max_len);
+    cap = a.max_len < kMeanCap ? a.max_len : kMeanCap;
+    SG_REQUIRE(S / 2 < (1ll << 31), SUBGACC_ERR_BADARG, "%s: too many segments in one call", name);
+    grid = xcd_grid(S / 2);
+    SG_REQUIRE(grid < (1ll << 31), SUBGACC_ERR_BADARG, "%s: too many segments in one call", name);
+    return SUBGACC_OK;
+}
+
+extern "C" int subgacc_sjoin_relu_mean(const subgacc_join_desc *d, const float *w1, const float *b1, int32_t H, float *out_mean,
+                                       float *out_p, float *out_q, void *stream) {
+    const char *name = "sjoin_relu_mean";
+    if (int rc = f64stage_check(name, d, H)) return rc;
+    SG_REQUIRE(w1 && b1 && out_mean, SUBGACC_ERR_BADARG, "sjoin_relu_mean: w1, b1 and out_mean are required (a NULL one given)");
+    SG_REQUIRE((out_p == nullptr) == (out_q == nullptr), SUBGACC_ERR_BADARG, "sjoin_relu_mean: out_p and out_q go together (one is NULL)");
+    if (d->S == 0) return SUBGACC_OK;
+    JoinArgs a;
+    int32_t cap;
+    int64_t grid;
+    if (int rc = f64stage_join(name, d, a, cap, grid)) return rc;
     const size_t lds = (size_t)cap * 16 + (size_t)((cap + 1) & ~1) * 4 + (size_t)(cap > kMeanThreads ? cap : kMeanThreads) * 8;
-    SG_REQUIRE(S / 2 < (1ll << 31), SUBGACC_ERR_BADARG, "sjoin_relu_mean: too many segments in one call");
-    const int64_t grid = xcd_grid(S / 2);
-    SG_REQUIRE(grid < (1ll << 31), SUBGACC_ERR_BADARG, "sjoin_relu_mean: too many segments in one call");
+    const int64_t pb = d->pair_block, S = d->S;
     MeanArgs m{w1, b1, H, out_mean, out_p, out_q};
     hipStream_t s = (hipStream_t)stream;
     if (out_p)
         hipLaunchKernelGGL((sjoin_f64mean_kernel<true>), dim3((unsigned)grid), dim3(kMeanThreads), lds, s, a, (uint32_t)pb, (uint32_t)(S / 2), cap, m);
     else
         hipLaunchKernelGGL((sjoin_f64mean_kernel<false>), dim3((unsigned)grid), dim3(kMeanThreads), lds, s, a, (uint32_t)pb, (uint32_t)(S / 2), cap, m);
+    SG_LAUNCH_CHECK();
+    return SUBGACC_OK;
+}
+
+// sjoin_f64attn_kernel's LDS: f64pair_stage's arrays, S's pairs and two per-member factors, the block max
+static size_t f64attn_lds(int32_t cap) {
+    const size_t sc = (size_t)(cap > kMeanThreads ? cap : kMeanThreads);
+    return (size_t)cap * 16 + (size_t)((cap + 1) & ~1) * 4 + sc * 16 + (kMeanThreads / kWave) * 4;
+}
+
+extern "C" int subgacc_sjoin_relu_attn(const subgacc_join_desc *d, const float *w1, const float *b1, const float *u, int32_t H,
+                                       float *out_a, float *out_max, float *out_den, void *stream) {
+    const char *name = "sjoin_relu_attn";
+    if (int rc = f64stage_check(name, d, H)) return rc;
+    SG_REQUIRE(w1 && b1 && u && out_a, SUBGACC_ERR_BADARG, "sjoin_relu_attn: w1, b1, u and out_a are required (a NULL one given)");
+    SG_REQUIRE((out_max == nullptr) == (out_den == nullptr), SUBGACC_ERR_BADARG,
+               "sjoin_relu_attn: out_max and out_den go together (one is NULL)");
+    if (d->S == 0) return SUBGACC_OK;
+    JoinArgs a;
+    int32_t cap;
+    int64_t grid;
+    if (int rc = f64stage_join(name, d, a, cap, grid)) return rc;
+    AttnArgs m{w1, b1, u, H, out_a, out_max, out_den, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipLaunchKernelGGL((sjoin_f64attn_kernel<false>), dim3((unsigned)grid), dim3(kMeanThreads), f64attn_lds(cap), (hipStream_t)stream, a,
+                       (uint32_t)d->pair_block, (uint32_t)(d->S / 2), cap, m);
+    SG_LAUNCH_CHECK();
+    return SUBGACC_OK;
+}
+
+extern "C" int subgacc_sjoin_relu_attn_backward(const subgacc_join_desc *d, const float *w1, const float *b1, const float *u, int32_t H,
+                                                const float *g, const float *a_in, const float *max, const float *den, float *out_dw,
+                                                float *out_db, float *out_du, void *stream) {
+    const char *name = "sjoin_relu_attn_backward";
+    if (int rc = f64stage_check(name, d, H)) return rc;
+    SG_REQUIRE(w1 && b1 && u && g && a_in && max && den && out_dw && out_db && out_du, SUBGACC_ERR_BADARG,
+               "sjoin_relu_attn_backward: w1, b1, u, g, a, max, den, out_dw, out_db and out_du are required (a NULL one given)");
+    if (d->S == 0) return SUBGACC_OK;
+    JoinArgs a;
+    int32_t cap;
+    int64_t grid;
+    if (int rc = f64stage_join(name, d, a, cap, grid)) return rc;
+    AttnArgs m{w1, b1, u, H, nullptr, nullptr, nullptr, g, a_in, max, den, out_dw, out_db, out_du};
+    hipLaunchKernelGGL((sjoin_f64attn_kernel<true>), dim3((unsigned)grid), dim3(kMeanThreads), f64attn_lds(cap), (hipStream_t)stream, a,
+                       (uint32_t)d->pair_block, (uint32_t)(d->S / 2), cap, m);
     SG_LAUNCH_CHECK();
     return SUBGACC_OK;
 }

@@ -973,31 +973,89 @@ def lstm_stage(edge, x, encode, embed, lstm):
     return out.view(2, -1, out.shape[-1])
 
 
-def _relu_mlp(embed):
+def _relu_mlp(embed, name="float_mean_stage"):
     """(Linear(1, H), Linear(H, H')) of embed = Sequential(Linear(1, H), ReLU(), Linear(H, H')) -- the reference's pe_embedding for the
     float encoders (model.py:54-55, input_dim = 1) -- or TypeError"""
     nn = torch.nn
     if not (isinstance(embed, nn.Sequential) and len(embed) == 3 and isinstance(embed[0], nn.Linear) and isinstance(embed[1], nn.ReLU)
             and isinstance(embed[2], nn.Linear) and embed[0].in_features == 1 and embed[2].in_features == embed[0].out_features):
-        raise TypeError("float_mean_stage fuses embed = Sequential(Linear(1, H), ReLU(), Linear(H, H')) only; for any other module "
+        raise TypeError(f"{name} fuses embed = Sequential(Linear(1, H), ReLU(), Linear(H, H')) only; for any other module "
                         "use xz, ind = gather(edge, x) and the module on xz")
     return embed[0], embed[2]
 
 
-def _edge_rows(edge):
-    """float_mean_stage's `edge` checked on the host: a [2, B] integer array (torch or NumPy), before any device work"""
+def _edge_rows(edge, name="float_mean_stage"):
+    """a fused float stage's `edge` checked on the host: a [2, B] integer array (torch or NumPy), before any device work"""
     if not torch.is_tensor(edge):
         try:
             edge = np.asarray(edge)
         except ValueError as e:             # (NumPy >= 1.24 refuses a ragged nested list itself)
-            raise ValueError(f"float_mean_stage: edge must be a [2, B] integer array ({e})") from None
+            raise ValueError(f"{name}: edge must be a [2, B] integer array ({e})") from None
         ok = edge.dtype != object and np.issubdtype(edge.dtype, np.integer)
     else:
         ok = not edge.dtype.is_floating_point and not edge.dtype.is_complex and edge.dtype != torch.bool
     if not ok or edge.ndim != 2 or edge.shape[0] != 2:
-        raise ValueError(f"float_mean_stage: edge must be a [2, B] integer array, got {getattr(edge, 'dtype', type(edge))} "
+        raise ValueError(f"{name}: edge must be a [2, B] integer array, got {getattr(edge, 'dtype', type(edge))} "
                          f"of shape {tuple(getattr(edge, 'shape', ()))}")
     return edge
+
+
+class _FloatStage:
+    """What the fused float stages (float_mean_stage, float_attn_stage) share: the checks of the store, embed and edge -- every one before
+    any device work --, the mirrored F64 descriptor of the join and the status words it leaves.  `unfused` names the module call a caller
+    with an integer (LP) store has instead."""
+
+    def __init__(self, name, unfused, edge, x, embed):
+        self.name = name
+        self.lin1, self.lin2 = _relu_mlp(embed, name)
+        H = self.H = self.lin1.out_features
+        if not 1 <= H <= 1024:
+            raise ValueError(f"{name}: Linear(1, H) with H = {H}; the fused stage takes 1 <= H <= 1024")
+        if isinstance(x, StridedSpG):
+            raise TypeError(f"{name} joins a resident float store (SpG or HeadedSpG), not a StridedSpG")
+        if not isinstance(x, (SpG, HeadedSpG)):
+            raise TypeError(f"{name} joins a float64 SpG or HeadedSpG, not {type(x).__name__}")
+        if x.keyrows or x.data.dtype != torch.float64:
+            raise TypeError(f"{name} joins a float (PPR / SPD / DEG) store; an integer (LP) store has {unfused}")
+        self.edge = _edge_rows(edge, name)
+        self.x, self.dev = x, x.device
+        dev = self.dev
+        if self.lin1.weight.device != dev or self.lin2.weight.device != dev or self.lin1.weight.dtype != torch.float32:
+            raise ValueError(f"{name}: embed must hold float32 parameters on the store's device ({dev})")
+
+    def join_on(self):
+        """the device side: the endpoints, the store's rows, the status words, w1 and b1"""
+        dev = self.dev
+        e = _as_rows(self.edge, dev)
+        self.B = int(e.shape[1])
+        self.own = e.contiguous().view(-1)
+        _, self.rows = self.x.join_rows()
+        self.flags = torch.zeros(4, dtype=torch.int32, device=dev)
+        self.w1 = self.lin1.weight.view(-1)
+        self.b1 = self.lin1.bias if self.lin1.bias is not None else torch.zeros(self.H, dtype=torch.float32, device=dev)
+
+    def desc(self):
+        return _lib.join_desc(JOIN_ROWS, JOIN_F64, **self.rows, own=self.own, S=2 * self.B, pair_block=self.B, flags=self.flags)
+
+    def checked(self):
+        status = int(self.flags[3].item())
+        if status & 16:
+            raise IndexError(f"row index out of range for an SpG with {self.x.n_rows} rows")
+        if status & 1:
+            raise _lib.SubgAccError("SpG row longer than SpG.max_len")
+
+    def nonempty(self):
+        """[2B] 1.0 where the endpoint's own row has members (an empty segment gives a zero row)"""
+        rows, own = self.rows, self.own
+        sizes = rows["row_off"][own + 1] - rows["row_off"][own] if "row_off" in rows else rows["ids"][own * rows["row_stride"]]
+        return sizes > 0
+
+    def tail(self, M):
+        """W2 M + 2 b2 ([2B, H'])"""
+        h = torch.nn.functional.linear(M, self.lin2.weight)
+        if self.lin2.bias is not None:
+            h = h + 2 * self.lin2.bias
+        return h
 
 
 class _ReluMean(torch.autograd.Function):
@@ -1026,30 +1084,12 @@ def float_mean_stage(edge, x, embed):
     grad is enabled and one of them requires it), W2 / b2 through ordinary torch ops.
     edge: [2, B] integer (torch or NumPy); x: a float64 SpG or HeadedSpG (topk_ppr_matrix / ppr.encoding).
     Returns float32 [2, B, H'] (left endpoints, right endpoints) as mean_stage does; empty segments give zero rows.  The result
-    carries the join's status words as .join_flags (flags[1] & 2: a pair with a row too long to stage streamed)."""
-    lin1, lin2 = _relu_mlp(embed)
-    H = lin1.out_features
-    if not 1 <= H <= 1024:
-        raise ValueError(f"float_mean_stage: Linear(1, H) with H = {H}; the fused stage takes 1 <= H <= 1024")
-    if isinstance(x, StridedSpG):
-        raise TypeError("float_mean_stage joins a resident float store (SpG or HeadedSpG), not a StridedSpG")
-    if not isinstance(x, (SpG, HeadedSpG)):
-        raise TypeError(f"float_mean_stage joins a float64 SpG or HeadedSpG, not {type(x).__name__}")
-    if x.keyrows or x.data.dtype != torch.float64:
-        raise TypeError("float_mean_stage joins a float (PPR / SPD / DEG) store; an integer (LP) store has mean_stage(edge, x, encode, "
-                        "embed)")
-    edge = _edge_rows(edge)
-    dev = x.device
-    if lin1.weight.device != dev or lin2.weight.device != dev or lin1.weight.dtype != torch.float32:
-        raise ValueError(f"float_mean_stage: embed must hold float32 parameters on the store's device ({dev})")
-    e = _as_rows(edge, dev)
-    B = int(e.shape[1])
-    own = e.contiguous().view(-1)
-    _, rows = x.join_rows()
-    flags = torch.zeros(4, dtype=torch.int32, device=dev)
-    w1 = lin1.weight.view(-1)
-    b1 = lin1.bias if lin1.bias is not None else torch.zeros(H, dtype=torch.float32, device=dev)
-    grads = torch.is_grad_enabled() and (w1.requires_grad or b1.requires_grad)
+    carries the join's status words as .join_flags (flags[1] & 2: a pair with a row too long to stage streamed).
+    For --aggr attn, float_attn_stage(edge, x, embed, gate_nn, value_nn)."""
+    st = _FloatStage("float_mean_stage", "mean_stage(edge, x, encode, embed)", edge, x, embed)
+    st.join_on()
+    B, H, dev = st.B, st.H, st.dev
+    grads = torch.is_grad_enabled() and (st.w1.requires_grad or st.b1.requires_grad)
 
     def join(w, b):
         M = torch.empty((2 * B, H), dtype=torch.float32, device=dev)
@@ -1057,20 +1097,116 @@ def float_mean_stage(edge, x, embed):
         if B == 0:          # (an empty list has no pair_block the library would accept)
             return M, P, Q
         with _timed("sjoin_relu_mean"):
-            d = _lib.join_desc(JOIN_ROWS, JOIN_F64, **rows, own=own, S=2 * B, pair_block=B, flags=flags)
+            d = st.desc()
             check(lib().subgacc_sjoin_relu_mean(ctypes.byref(d), ptr(w), ptr(b), H, ptr(M), ptr(P), ptr(Q), stream_ptr()))
-        status = int(flags[3].item())
-        if status & 16:
-            raise IndexError(f"row index out of range for an SpG with {x.n_rows} rows")
-        if status & 1:
-            raise _lib.SubgAccError("SpG row longer than SpG.max_len")
+        st.checked()
         return M, P, Q
 
-    M = _ReluMean.apply(w1, b1, join) if grads else join(w1.detach(), b1.detach())[0]
-    sizes = rows["row_off"][own + 1] - rows["row_off"][own] if "row_off" in rows else rows["ids"][own * rows["row_stride"]]
-    h = torch.nn.functional.linear(M, lin2.weight)
-    if lin2.bias is not None:
-        h = h + 2 * lin2.bias
-    out = (h * (sizes > 0).to(h.dtype)[:, None]).view(2, B, h.shape[-1])
-    out.join_flags = flags
+    M = _ReluMean.apply(st.w1, st.b1, join) if grads else join(st.w1.detach(), st.b1.detach())[0]
+    h = st.tail(M)
+    out = (h * st.nonempty().to(h.dtype)[:, None]).view(2, B, h.shape[-1])
+    out.join_flags = st.flags
+    return out
+
+
+def _one_linear(mod, what, d_in, d_out=None):
+    """the nn.Linear of `mod` = Linear(d_in, d_out) or Sequential(Linear(d_in, d_out)) (d_out None: any), or TypeError"""
+    nn = torch.nn
+    lin = mod[0] if isinstance(mod, nn.Sequential) and len(mod) == 1 else mod
+    if not (isinstance(lin, nn.Linear) and lin.in_features == d_in and (d_out is None or lin.out_features == d_out)):
+        shape = f"({d_in}, {d_out if d_out is not None else 'H2'})"
+        raise TypeError(f"float_attn_stage fuses {what} = Linear{shape} (or a Sequential of that one Linear; PyG's MLP([...]) as its "
+                        f".lins[0]) only; for any other module use xz, ind = gather(edge, x) and the modules on xz")
+    return lin
+
+
+class _ReluAttn(torch.autograd.Function):
+    """A [S, H] of subgacc_sjoin_relu_attn as a function of (w1, b1, u) -- and of the gate bias, whose gradient is exactly zero (softmax
+    drops a constant); backward: subgacc_sjoin_relu_attn_backward's per-segment sums, summed over the segments"""
+
+    @staticmethod
+    def forward(ctx, w1, b1, u, bg, join):
+        ctx.join = join
+        ctx.has_bg = bg is not None
+        A, mx, den = join.forward(w1.detach().contiguous(), b1.detach().contiguous(), u.detach().contiguous(), True)
+        ctx.save_for_backward(w1.detach(), b1.detach(), u.detach(), A, mx, den)
+        return A
+
+    @staticmethod
+    def backward(ctx, G):
+        w1, b1, u, A, mx, den = ctx.saved_tensors
+        Dw, Db, Du = ctx.join.backward(w1.contiguous(), b1.contiguous(), u.contiguous(), G.contiguous(), A, mx, den)
+        bg = torch.zeros((1,), dtype=G.dtype, device=G.device) if ctx.has_bg else None
+        return Dw.sum(0), Db.sum(0), Du.sum(0), bg, None
+
+
+class _AttnJoin:
+    """the two library calls of float_attn_stage over one _FloatStage"""
+
+    def __init__(self, st):
+        self.st = st
+
+    def forward(self, w, b, u, keep):
+        st = self.st
+        S, H = 2 * st.B, st.H
+        A = torch.empty((S, H), dtype=torch.float32, device=st.dev)
+        mx, den = (torch.empty(S, dtype=torch.float32, device=st.dev), torch.empty(S, dtype=torch.float32, device=st.dev)) if keep \
+            else (None, None)
+        if st.B == 0:       # (an empty list has no pair_block the library would accept)
+            return A, mx, den
+        with _timed("sjoin_relu_attn"):
+            d = st.desc()
+            check(lib().subgacc_sjoin_relu_attn(ctypes.byref(d), ptr(w), ptr(b), ptr(u), H, ptr(A), ptr(mx), ptr(den), stream_ptr()))
+        st.checked()
+        return A, mx, den
+
+    def backward(self, w, b, u, G, A, mx, den):
+        st = self.st
+        Dw, Db, Du = (torch.zeros_like(A) for _ in range(3))
+        if st.B == 0:
+            return Dw, Db, Du
+        with _timed("sjoin_relu_attn_backward"):
+            d = st.desc()
+            check(lib().subgacc_sjoin_relu_attn_backward(ctypes.byref(d), ptr(w), ptr(b), ptr(u), st.H, ptr(G), ptr(A), ptr(mx),
+                                                         ptr(den), ptr(Dw), ptr(Db), ptr(Du), stream_ptr()))
+        return Dw, Db, Du
+
+
+def float_attn_stage(edge, x, embed, gate_nn, value_nn=None):
+    """The reference's first model stage for the float encoders with --aggr attn, fused:  model.py:59-62,78-81
+        x = pe_embedding(xz).sum(dim=-2);  xl, xr = AttentionalAggregation(gate_nn, nn)(x, ptr=ptr).view(2, -1, H'')
+    with pe_embedding = embed = Sequential(Linear(1, H), ReLU(), Linear(H, H')) over the float join's xz [R,2,1] and one-Linear
+    gate_nn (H' -> 1) and nn (value_nn: H' -> H'', or None).  Row t of segment j is x_t = W2 r_t + 2 b2 with r_t = relu(w1 a_t + b1) +
+    relu(w1 b_t + b1), so the gate is u . r_t plus a constant the softmax drops (u = W2^T wg), and, the weights summing to 1,
+        out_j = nn(W2 A_j + 2 b2) [n_j > 0],   A_j = sum_t softmax_j(u . r)_t r_t
+    The library's kernels (subgacc_sjoin_relu_attn / _backward) join the pairs and write A [2B, H] -- neither xz nor the [R,2,H]
+    activations exist -- and, when autograd asks, the per-segment sums for w1, b1 and u; the rest are ordinary torch ops.  Every
+    parameter of embed, gate_nn and value_nn receives a gradient; the gate bias's is exactly zero, as the reference's is analytically.
+    gate_nn: nn.Linear(H', 1) or nn.Sequential of that one Linear; value_nn: None, nn.Linear(H', H'') or a one-Linear Sequential.
+    The reference builds them as torch_geometric MLP([H', 1]) / MLP([H', H']): with a two-entry channel list, PyG 2.2's MLP is one plain
+    Linear (no norm, no activation after the last layer), held in .lins[0] -- pass that Linear.  (This rests on PyG 2.2's MLP as
+    released; PyG is not a dependency here.)
+    edge: [2, B] integer (torch or NumPy); x: a float64 SpG or HeadedSpG.  Returns float32 [2, B, H''] (H' without value_nn), empty
+    segments giving zero rows, with the join's status words as .join_flags (flags[1] & 2: a pair with a row too long to stage streamed)."""
+    st = _FloatStage("float_attn_stage", "attn_stage(edge, x, encode, embed, gate_nn, value_nn)", edge, x, embed)
+    H2 = st.lin2.out_features
+    gate = _one_linear(gate_nn, "gate_nn", H2, 1)
+    val = _one_linear(value_nn, "value_nn", H2) if value_nn is not None else None
+    for lin in (gate, val):
+        if lin is not None and (lin.weight.device != st.dev or lin.weight.dtype != torch.float32):
+            raise ValueError(f"float_attn_stage: gate_nn / value_nn must hold float32 parameters on the store's device ({st.dev})")
+    st.join_on()
+    B = st.B
+    u = (gate.weight @ st.lin2.weight).view(-1)         # W2^T wg
+    join = _AttnJoin(st)
+    params = [st.w1, st.b1, u] + ([gate.bias] if gate.bias is not None else [])
+    if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+        A = _ReluAttn.apply(st.w1, st.b1, u, gate.bias, join)
+    else:
+        A = join.forward(st.w1.detach(), st.b1.detach(), u.detach(), False)[0]
+    h = st.tail(A)
+    if val is not None:
+        h = torch.nn.functional.linear(h, val.weight, val.bias)
+    out = (h * st.nonempty().to(h.dtype)[:, None]).view(2, B, h.shape[-1])
+    out.join_flags = st.flags
     return out
