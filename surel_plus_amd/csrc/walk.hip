@@ -758,16 +758,43 @@ extern "C" int subgacc_hop_records_build(const void *indptr, int32_t indptr64, c
     return SUBGACC_OK;
 }
 
-static int launch_walk(const subgacc_walk_cfg *cfg, const void *indptr, const int32_t *indices, int64_t num_nodes,
-                       const int32_t *query, int64_t n, const uint32_t *rng_pos, const uint32_t *rng_seed,
-                       int32_t *set_ids, uint64_t *set_keys, int32_t *set_slot, void *uniq_table, int64_t uniq_capacity,
-                       int64_t root_base, int32_t *nsize, int32_t *walks, int32_t *flags, void *stream,
-                       bool holes = false, const int32_t *worklist = nullptr, const int64_t *n_work = nullptr,
-                       bool tags_only = false, int64_t work_cap = 0, bool order_only_list = false) {
-    const bool spg = set_slot != nullptr;
-    SG_REQUIRE(cfg && indptr && set_ids && (set_keys || spg) && nsize && flags, SUBGACC_ERR_BADARG,
-               "walk: null argument");
-    SG_REQUIRE(n >= 0 && num_nodes >= 0, SUBGACC_ERR_BADARG, "walk: negative size");
+// One walk as launch_walk reads it: each subgacc_walk_* entry point checks its own arguments and fills one.  Rows (form): general
+// sets, ids + 64-bit LP keys in first-visit order (+ raw walks); fused rows, ids sorted + the slot of the LP key in the table of
+// distinct rows (kRowsTable) or the key itself (kRowsKeys32: slot, kRowsKeys64: keys); or none, the sets' LP keys registered in
+// the table with their exact first-visit tags.  Work list: kListSelect, the rows to sample -- worklist[0 .. *n_work), or without
+// one the rows whose root is not SUBGACC_NO_ROOT -- the others passed over, which only the fused-row kernel does; kListOrder, an
+// order over all n rows, which the general kernel (it reads no list) replaces by batch order.
+enum WalkRowForm { kRowsSets, kRowsTable, kRowsKeys32, kRowsKeys64, kRowsTagsOnly };
+enum WalkList { kListNone, kListSelect, kListOrder };
+struct WalkLaunch {
+    const subgacc_walk_cfg *cfg;
+    const void *indptr;
+    const int32_t *indices;
+    int64_t num_nodes;
+    const int32_t *query;   // the roots, query[0 .. n)
+    int64_t n;
+    const uint32_t *rng_pos, *rng_seed;
+    int32_t *flags;
+    void *stream;
+    WalkRowForm form;
+    int32_t *ids = nullptr, *slot = nullptr, *nsize = nullptr, *walks = nullptr;   // the rows: what `form` writes
+    uint64_t *keys = nullptr;
+    void *uniq_table = nullptr;   // kRowsTable, kRowsTagsOnly
+    int64_t uniq_capacity = 0, root_base = 0;
+    WalkList list = kListNone;
+    const int32_t *worklist = nullptr;
+    const int64_t *n_work = nullptr;
+    int64_t work_cap = 0;
+};
+
+static int launch_walk(const WalkLaunch &w) {
+    const subgacc_walk_cfg *cfg = w.cfg;
+    const int64_t n = w.n;
+    const bool spg = w.form != kRowsSets;      // fused rows of any form: walk_rows_kernel, else walk_sets_kernel<SPG>
+    const bool tags_only = w.form == kRowsTagsOnly;
+    const bool table = w.form == kRowsTable || tags_only;
+    SG_REQUIRE(cfg && w.indptr && (tags_only || (w.ids && w.nsize)) && w.flags, SUBGACC_ERR_BADARG, "walk: null argument");
+    SG_REQUIRE(n >= 0 && w.num_nodes >= 0, SUBGACC_ERR_BADARG, "walk: negative size");
     SG_REQUIRE(cfg->rng_mode == SUBGACC_RNG_RAND_R || cfg->rng_mode == SUBGACC_RNG_PHILOX, SUBGACC_ERR_BADARG,
                "walk: unknown rng_mode %d", cfg->rng_mode);
     const int shift = subgacc_key_shift(cfg->num_walks, cfg->num_steps);
@@ -776,30 +803,30 @@ static int launch_walk(const subgacc_walk_cfg *cfg, const void *indptr, const in
     SG_REQUIRE((int64_t)M * m + 1 <= (1 << 20), SUBGACC_ERR_LDS, "walk: M*m+1 = %lld too large", (long long)M * m + 1);
     const int Q = M * m + 1;
     const int stride = cfg->bucket > 0 ? cfg->bucket : Q;
-    SG_REQUIRE(!cfg->emit_walks || walks, SUBGACC_ERR_BADARG, "walk: emit_walks without a walks buffer");
-    SG_REQUIRE(cfg->rng_mode != SUBGACC_RNG_RAND_R || (rng_pos && rng_seed) || n == 0, SUBGACC_ERR_BADARG,
+    SG_REQUIRE(!cfg->emit_walks || w.walks, SUBGACC_ERR_BADARG, "walk: emit_walks without a walks buffer");
+    SG_REQUIRE(cfg->rng_mode != SUBGACC_RNG_RAND_R || (w.rng_pos && w.rng_seed) || n == 0, SUBGACC_ERR_BADARG,
                "walk: RAND_R mode needs rng_pos/rng_seed from subgacc_rng_positions");
     if (spg) {
         SG_REQUIRE(table_size_for(Q) <= kSpgPerLane * kWalkThreads, SUBGACC_ERR_LDS,
                    "walk_spg: M*m+1 = %d needs a per-root table above %d slots; use subgacc_walk_sets + subgacc_spg_build",
                    Q, kSpgPerLane * kWalkThreads);
-        SG_REQUIRE(!uniq_table || (uniq_capacity > 0 && (uniq_capacity & (uniq_capacity - 1)) == 0 &&
-                                   uniq_capacity < (1ll << 31) && root_base >= 0),
+        SG_REQUIRE(!table || (w.uniq_capacity > 0 && (w.uniq_capacity & (w.uniq_capacity - 1)) == 0 &&
+                              w.uniq_capacity < (1ll << 31) && w.root_base >= 0),
                    SUBGACC_ERR_BADARG, "walk_spg: needs a power-of-two table of distinct rows (or none: key rows)");
     }
     if (n == 0) return SUBGACC_OK;
-    SG_REQUIRE(query, SUBGACC_ERR_BADARG, "walk: null query");   // `indices` may be NULL for an edgeless graph
-    SG_REQUIRE(num_nodes >= 1, SUBGACC_ERR_BADARG, "walk: %lld roots but a graph without nodes", (long long)n);
+    SG_REQUIRE(w.query, SUBGACC_ERR_BADARG, "walk: null query");   // `indices` may be NULL for an edgeless graph
+    SG_REQUIRE(w.num_nodes >= 1, SUBGACC_ERR_BADARG, "walk: %lld roots but a graph without nodes", (long long)n);
 
     WalkArgs a;
-    a.indptr = indptr, a.indices = indices, a.query = query, a.n = n, a.num_nodes = num_nodes;
-    a.worklist = worklist, a.n_work = n_work;
-    a.work_cap = work_cap, a.tags_only = tags_only ? 1 : 0;
+    a.indptr = w.indptr, a.indices = w.indices, a.query = w.query, a.n = n, a.num_nodes = w.num_nodes;
+    a.worklist = w.worklist, a.n_work = w.n_work;
+    a.work_cap = w.work_cap, a.tags_only = tags_only ? 1 : 0;
     a.walk_pos = cfg->rng_mode == SUBGACC_RNG_RAND_R ? cfg->walk_pos : nullptr;
-    a.rng_pos = rng_pos, a.rng_seed = rng_seed;
-    a.set_ids = set_ids, a.set_keys = set_keys, a.nsize = nsize;
-    a.walks = cfg->emit_walks ? walks : nullptr;
-    a.flags = flags;
+    a.rng_pos = w.rng_pos, a.rng_seed = w.rng_seed;
+    a.set_ids = w.ids, a.set_keys = w.keys, a.nsize = w.nsize;
+    a.walks = cfg->emit_walks ? w.walks : nullptr;
+    a.flags = w.flags;
     a.M = M, a.m = m, a.stride = stride, a.shift = shift;
     // rows may lie further apart than they are long (row_pitch: every row on a 128-byte line); tags count in the same unit
     SG_REQUIRE(cfg->row_pitch == 0 || cfg->row_pitch >= stride, SUBGACC_ERR_BADARG, "walk: row_pitch %d < the row capacity %d",
@@ -812,12 +839,12 @@ static int launch_walk(const subgacc_walk_cfg *cfg, const void *indptr, const in
     a.wo = cfg->first_hop_wo ? 1 : 0;
     a.step_major = cfg->order == SUBGACC_ORDER_STEP_MAJOR ? 1 : 0;
     a.cap_root = cfg->cap_root_degree ? 1 : 0;
-    a.set_slot = set_slot;
+    a.set_slot = w.slot;
     // key rows leave four members per store where every row begins on a 16-byte boundary (walk_rows_kernel)
-    a.wide_rows = (a.pitch % 4 == 0 && (((uintptr_t)set_ids | (uintptr_t)set_slot) & 15u) == 0) ? 1 : 0;
-    a.table = (spg && uniq_table) ? uniq_view(uniq_table, uniq_capacity) : UniqTable{nullptr, nullptr, nullptr, 0};
-    a.keyrows = (spg && !uniq_table) ? 1 : 0;
-    a.root_base = root_base;
+    a.wide_rows = (a.pitch % 4 == 0 && (((uintptr_t)a.set_ids | (uintptr_t)a.set_slot) & 15u) == 0) ? 1 : 0;
+    a.table = table ? uniq_view(w.uniq_table, w.uniq_capacity) : UniqTable{nullptr, nullptr, nullptr, 0};
+    a.keyrows = (w.form == kRowsKeys32 || w.form == kRowsKeys64) ? 1 : 0;
+    a.root_base = w.root_base;
     a.recs = (const unsigned long long *)cfg->hop_records;
     a.rec.id_bits = cfg->rec_id_bits, a.rec.beg_bits = cfg->rec_beg_bits;
     SG_REQUIRE(!a.recs || (a.rec.id_bits == 0 && a.rec.beg_bits == 0) ||
@@ -832,7 +859,7 @@ static int launch_walk(const subgacc_walk_cfg *cfg, const void *indptr, const in
     SG_REQUIRE(lds <= (size_t)kLdsBytes, SUBGACC_ERR_LDS,
                "walk: per-root tables need %zu B of LDS (> %d): M*m+1 = %d is too large", lds, kLdsBytes, Q);
 
-    hipStream_t s = (hipStream_t)stream;
+    hipStream_t s = (hipStream_t)w.stream;
     // the persistent, software-pipelined form takes every launch it supports (dev builds: -DSG_DEV_NO_WALK_PIPE forces this file's)
 #ifdef SG_DEV_NO_WALK_PIPE
     const bool use_pipe = false;
@@ -840,7 +867,7 @@ static int launch_walk(const subgacc_walk_cfg *cfg, const void *indptr, const in
     const bool use_pipe = true;
 #endif
     // (replayed stream positions, walk_pos: only the general kernel below reads them)
-    if (use_pipe && !holes && !a.walk_pos && launch_walk_pipe(a, cfg->indptr64 != 0, cfg->rng_mode, spg, lds, s)) {
+    if (use_pipe && w.list == kListNone && !a.walk_pos && launch_walk_pipe(a, cfg->indptr64 != 0, cfg->rng_mode, spg, lds, s)) {
         SG_LAUNCH_CHECK();
         return SUBGACC_OK;
     }
@@ -851,11 +878,8 @@ static int launch_walk(const subgacc_walk_cfg *cfg, const void *indptr, const in
     SG_REQUIRE(!tags_only, SUBGACC_ERR_BADARG,
                "walk_tags: only the fused-row kernel registers tags alone (2..4 hops, M <= 256, a 512- or 1,024-slot table, no "
                "bucket); M = %d, m = %d", M, m);
-    if (holes && order_only_list) {      // a list that names EVERY row only says in which order to take them (subgacc_walk_spg_list): the
-        holes = false;                   // general kernel, which reads no list, takes the rows in batch order -- the same rows
-        a.worklist = nullptr, a.n_work = nullptr;
-    }
-    SG_REQUIRE(!holes, SUBGACC_ERR_BADARG,
+    if (w.list == kListOrder) a.worklist = nullptr, a.n_work = nullptr;   // the general kernel reads no list: batch order, the same rows
+    SG_REQUIRE(w.list != kListSelect, SUBGACC_ERR_BADARG,
                "walk_spg_sparse: rows without a root are passed over by the fused-row kernel only (2..4 hops, M <= 256, a 512- or "
                "1,024-slot table, no bucket); M = %d, m = %d", M, m);
     SG_REQUIRE(!a.keyrows, SUBGACC_ERR_BADARG,
@@ -894,8 +918,9 @@ extern "C" int subgacc_walk_sets(const subgacc_walk_cfg *cfg, const void *indptr
                                  const uint32_t *rng_seed, int32_t *set_ids, uint64_t *set_keys, int32_t *nsize,
                                  int32_t *walks, int32_t *flags, void *stream) {
     SG_REQUIRE(set_keys, SUBGACC_ERR_BADARG, "walk_sets: null set_keys");
-    return launch_walk(cfg, indptr, indices, num_nodes, query, n, rng_pos, rng_seed, set_ids, set_keys, nullptr, nullptr,
-                       0, 0, nsize, walks, flags, stream);
+    WalkLaunch w{cfg, indptr, indices, num_nodes, query, n, rng_pos, rng_seed, flags, stream, kRowsSets};
+    w.ids = set_ids, w.keys = set_keys, w.nsize = nsize, w.walks = walks;
+    return launch_walk(w);
 }
 
 extern "C" int subgacc_walk_spg(const subgacc_walk_cfg *cfg, const void *indptr, const int32_t *indices,
@@ -906,8 +931,10 @@ extern "C" int subgacc_walk_spg(const subgacc_walk_cfg *cfg, const void *indptr,
     SG_REQUIRE(row_slot, SUBGACC_ERR_BADARG, "walk_spg: null row_slot");
     SG_REQUIRE(cfg && !cfg->emit_walks && cfg->order == SUBGACC_ORDER_WALK_MAJOR, SUBGACC_ERR_BADARG,
                "walk_spg: set_sampler order only, no raw walks");
-    return launch_walk(cfg, indptr, indices, num_nodes, query, n, rng_pos, rng_seed, row_ids, nullptr, row_slot,
-                       uniq_table, uniq_capacity, root_base, nsize, nullptr, flags, stream);
+    WalkLaunch w{cfg, indptr, indices, num_nodes, query, n, rng_pos, rng_seed, flags, stream, uniq_table ? kRowsTable : kRowsKeys32};
+    w.ids = row_ids, w.slot = row_slot, w.nsize = nsize, w.uniq_table = uniq_table, w.uniq_capacity = uniq_capacity;
+    w.root_base = root_base;
+    return launch_walk(w);
 }
 
 extern "C" int subgacc_walk_spg_sparse(const subgacc_walk_cfg *cfg, const void *indptr, const int32_t *indices, int64_t num_nodes,
@@ -918,8 +945,10 @@ extern "C" int subgacc_walk_spg_sparse(const subgacc_walk_cfg *cfg, const void *
                "walk_spg_sparse: null row_slot, or a work list without its length (or the reverse)");
     SG_REQUIRE(cfg && !cfg->emit_walks && cfg->order == SUBGACC_ORDER_WALK_MAJOR && cfg->rng_mode == SUBGACC_RNG_PHILOX,
                SUBGACC_ERR_BADARG, "walk_spg_sparse: set_sampler order, Philox mode (a root's set must not depend on its place in the batch)");
-    return launch_walk(cfg, indptr, indices, num_nodes, query, n, nullptr, nullptr, row_ids, nullptr, row_slot, uniq_table,
-                       uniq_capacity, 0, nsize, nullptr, flags, stream, true, worklist, n_work);
+    WalkLaunch w{cfg, indptr, indices, num_nodes, query, n, nullptr, nullptr, flags, stream, uniq_table ? kRowsTable : kRowsKeys32};
+    w.ids = row_ids, w.slot = row_slot, w.nsize = nsize, w.uniq_table = uniq_table, w.uniq_capacity = uniq_capacity;
+    w.list = kListSelect, w.worklist = worklist, w.n_work = n_work;
+    return launch_walk(w);
 }
 
 extern "C" int subgacc_walk_spg_list(const subgacc_walk_cfg *cfg, const void *indptr, const int32_t *indices, int64_t num_nodes,
@@ -932,8 +961,10 @@ extern "C" int subgacc_walk_spg_list(const subgacc_walk_cfg *cfg, const void *in
     // (the list of this entry point is an ORDER over all n rows, not a selection: when the fused-row kernel declines the shape --
     //  a dev build without it, a predicate of the caller that drifted from launch_walk_rows' -- the general kernel takes the rows
     //  in batch order instead of refusing the call)
-    return launch_walk(cfg, indptr, indices, num_nodes, query, n, rng_pos, rng_seed, row_ids, nullptr, row_slot, uniq_table,
-                       uniq_capacity, 0, nsize, nullptr, flags, stream, true, worklist, n_work, false, 0, true);
+    WalkLaunch w{cfg, indptr, indices, num_nodes, query, n, rng_pos, rng_seed, flags, stream, uniq_table ? kRowsTable : kRowsKeys32};
+    w.ids = row_ids, w.slot = row_slot, w.nsize = nsize, w.uniq_table = uniq_table, w.uniq_capacity = uniq_capacity;
+    w.list = kListOrder, w.worklist = worklist, w.n_work = n_work;
+    return launch_walk(w);
 }
 
 extern "C" int subgacc_walk_keyrows64(const subgacc_walk_cfg *cfg, const void *indptr, const int32_t *indices, int64_t num_nodes,
@@ -949,9 +980,11 @@ extern "C" int subgacc_walk_keyrows64(const subgacc_walk_cfg *cfg, const void *i
     SG_REQUIRE(cfg->num_steps * shift + 1 > 31, SUBGACC_ERR_BADARG,
                "walk_keyrows64: the keys of M = %d, m = %d fit 32 bits -- subgacc_walk_spg(uniq_table = NULL) writes those",
                cfg->num_walks, cfg->num_steps);
-    // (row_slot only has to be non-null: rows of 64-bit keys leave through set_keys; launch_walk_rows takes the launch or nobody does)
-    return launch_walk(cfg, indptr, indices, num_nodes, query, n, rng_pos, rng_seed, row_ids, row_keys, (int32_t *)row_keys, nullptr,
-                       0, 0, nsize, nullptr, flags, stream, worklist != nullptr, worklist, n_work);
+    // (launch_walk_rows takes the launch or nobody does)
+    WalkLaunch w{cfg, indptr, indices, num_nodes, query, n, rng_pos, rng_seed, flags, stream, kRowsKeys64};
+    w.ids = row_ids, w.keys = row_keys, w.nsize = nsize;
+    if (worklist) w.list = kListSelect, w.worklist = worklist, w.n_work = n_work;
+    return launch_walk(w);
 }
 
 extern "C" int subgacc_walk_tags(const subgacc_walk_cfg *cfg, const void *indptr, const int32_t *indices, int64_t num_nodes,
@@ -961,10 +994,10 @@ extern "C" int subgacc_walk_tags(const subgacc_walk_cfg *cfg, const void *indptr
     SG_REQUIRE(worklist && n_work && uniq_table && work_cap >= 0, SUBGACC_ERR_BADARG, "walk_tags: needs a work list, its length and a table");
     SG_REQUIRE(cfg && !cfg->emit_walks && cfg->order == SUBGACC_ORDER_WALK_MAJOR && cfg->bucket <= 0, SUBGACC_ERR_BADARG,
                "walk_tags: set_sampler order, no raw walks, no bucket");
-    // no row is written in this mode: the kernel's row arguments only have to be non-null
-    int32_t *none = (int32_t *)flags;
-    return launch_walk(cfg, indptr, indices, num_nodes, query, n, rng_pos, rng_seed, none, nullptr, none, uniq_table, uniq_capacity,
-                       root_base, none, nullptr, flags, stream, true, worklist, n_work, true, work_cap);
+    WalkLaunch w{cfg, indptr, indices, num_nodes, query, n, rng_pos, rng_seed, flags, stream, kRowsTagsOnly};
+    w.uniq_table = uniq_table, w.uniq_capacity = uniq_capacity, w.root_base = root_base;
+    w.list = kListSelect, w.worklist = worklist, w.n_work = n_work, w.work_cap = work_cap;
+    return launch_walk(w);
 }
 
 extern "C" int subgacc_compact_sets(const int32_t *set_ids, const uint64_t *set_keys, const int32_t *nsize,

@@ -402,8 +402,8 @@ class SampledSets:
             check(L.subgacc_keyrows_register(ptr(self.slot), ptr(self.nsize), n, self.stride, 0, ptr(table), cap, ptr(cand),
                                              ccap, ptr(words[2:3]), ptr(flags), st))
             nc = int(words[2].item())
-            check(L.subgacc_walk_tags(cfg, ptr(csr.indptr), ptr(csr.indices), csr.num_nodes, ptr(q), n, 0, ptr(ctx["rng_pos"]),
-                                      ptr(ctx["rng_seed"]), ptr(cand), ptr(words[2:3]), max(min(nc, n), 1), ptr(table), cap, ptr(flags), st))
+            _walk(cfg, csr, q, n, flags, st, "tags", rng=(ctx["rng_pos"], ctx["rng_seed"]), table=table, capacity=cap,
+                  work=(cand, words[2:3]), work_cap=max(min(nc, n), 1))
             max_unique = min(cap, RANK_LIMIT)
             ukeys = torch.empty(max_unique, dtype=torch.int64, device=dev)
             ws = torch.empty(L.subgacc_uniq_number_workspace_bytes(cap, 0), dtype=torch.uint8, device=dev)
@@ -609,6 +609,46 @@ def _rng_positions(L, cfg, csr, q, n, rng_streams, calls_before, st):
     return rng_pos, rng_seed
 
 
+def _walk(cfg, csr, roots, n, flags, st, form, ids=None, payload=None, nsize=None, walks=None, rng=(None, None), table=None,
+          capacity=0, work=None, select=False, root_base=0, work_cap=0):
+    """The subgacc_walk_* call of every walk (csrc/walk.hip).  form: "sets" (ids + LP keys in first-visit order, the raw walks with
+    cfg.emit_walks), "fused" (ids sorted + table slots, without a table 32-bit LP keys), "keys64" (ids sorted + 64-bit LP keys) or
+    "tags" (no rows: the listed roots' LP keys go into `table` with their first-visit tags).  rng = (rng_pos, rng_seed) under rand_r;
+    work = (list, its length on the device): the rows to sample with select=True, "keys64" and "tags", else an order over all rows."""
+    L, g = lib(), (cfg, ptr(csr.indptr), ptr(csr.indices), csr.num_nodes, ptr(roots), n)
+    rp, rs, tab = ptr(rng[0]), ptr(rng[1]), (ptr(table), capacity)
+    wl, nwl = (ptr(work[0]), ptr(work[1])) if work is not None else (None, None)
+    rows = (ptr(ids), ptr(payload), ptr(nsize), ptr(flags), st)
+    if form == "sets":
+        return check(L.subgacc_walk_sets(*g, rp, rs, *rows[:3], ptr(walks), *rows[3:]))
+    if form == "tags":
+        return check(L.subgacc_walk_tags(*g, root_base, rp, rs, wl, nwl, work_cap, *tab, *rows[3:]))
+    if form == "keys64":
+        return check(L.subgacc_walk_keyrows64(*g, rp, rs, wl, nwl, *rows))
+    if work is None:
+        return check(L.subgacc_walk_spg(*g, root_base, rp, rs, *tab, *rows))
+    if select:
+        return check(L.subgacc_walk_spg_sparse(*g, wl, nwl, *tab, *rows))
+    return check(L.subgacc_walk_spg_list(*g, rp, rs, wl, nwl, *tab, *rows))
+
+
+def worklist_buffers(n, dev):
+    """(list, its length, workspace) for sorted_worklist -- the workspace zeroed once: every call leaves it so"""
+    return (torch.empty(n, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int64, device=dev),
+            torch.zeros(lib().subgacc_worklist_workspace_bytes(n), dtype=torch.uint8, device=dev))
+
+
+def sorted_worklist(csr, roots, n, rank, bufs, st):
+    """the rows of a batch as a work list in ascending order of their root's id -- of its rank, given one (csrc/worklist.hip); rows
+    whose root is SUBGACC_NO_ROOT are left out.  bufs = worklist_buffers(n); returns (list, its length on the device)"""
+    L, (wl, nwl, ws) = lib(), bufs
+    if rank is None:
+        check(L.subgacc_worklist_by_root(ptr(roots), n, csr.num_nodes, ptr(wl), ptr(nwl), ptr(ws), ws.numel(), st))
+    else:
+        check(L.subgacc_worklist_by_rank(ptr(roots), n, ptr(rank), csr.num_nodes, ptr(wl), ptr(nwl), ptr(ws), ws.numel(), st))
+    return wl, nwl
+
+
 def walk_kernel_name(csr, num_walks, hops, fused_rows, bucket=-1):
     """which kernel a sample_sets(...) launch of this shape runs (set_sampler form; csrc/walk.hip:launch_walk decides):
     bench.py labels its roofline block with it, and the callers that hand the kernel a work list ask it first (only
@@ -681,18 +721,22 @@ def sample_sets(csr, query, num_walks=100, num_steps=3, bucket=-1, seed=111413, 
     in ascending rank of their root (subgacc_worklist_by_rank; the query over all nodes in id order walks the order itself) instead
     of ascending id -- the rows, and everything computed from them, are the same.  (`order` is the reference's first-visit order.)
     sets.walk_order says which order ran."""
-    root_order = as_rank(csr, root_order)
-    p = types.SimpleNamespace(**locals())
+    args = dict(locals())
+    p = types.SimpleNamespace(**args)
+    p.root_order = as_rank(csr, root_order)
     if not _plan_sets(p):              # shapes, kernel form, chunking, the rand_r stream positions, the table of distinct rows
         return None
     res = _launch_sets(p)              # per chunk: walk -> sizes -> (finish rows | register | number) -> packed copy
     res = _finish_sets(p) if res is _PACKED else res        # packed forms: global row offsets, numbering of the distinct LP rows
+    if res is _GROW:                   # the table of distinct LP rows overflowed: the same call with a 4x larger one (and the
+        return sample_sets(**dict(args, query=p.q, staging_bytes=p.staging_bytes, uniq_capacity=p.uniq_capacity * 4))   # same chunks)
     if res is not None and res.walk_order is None:
         res.walk_order = p.walk_order
     return res
 
 
 _PACKED = object()      # _launch_sets: the chunks were packed, _finish_sets takes over (the strided forms return their sets themselves)
+_GROW = object()        # _launch_sets / _finish_sets: the table of distinct LP rows overflowed, sample_sets walks again
 
 
 def _plan_sets(p):
@@ -721,7 +765,6 @@ def _plan_sets(p):
     if p.fused_rows:
         p.keep_keys = False
     p.limit = p.uniq_small_limit if p.uniq_small_limit > 0 else RANK_LIMIT
-    p.key_rows_arg = p.key_rows          # (what the caller asked for: a retry with a larger table asks for the same)
     p.kform = key_rows_form(p.M, p.m) if (p.key_rows and p.strided and p.fused_rows and not p.number_rows and p.bucket <= 0 and not p.walk_replay) else 0
     p.per_member = (12 if p.kform == 64 else 8) if p.fused_rows else 12
     if p.staging_bytes is None:     # 288 GB of HBM: one chunk of roots wherever a third of the free memory holds its staging rows
@@ -797,45 +840,19 @@ def _launch_sets(p):
         p.by_root = (not p.by_rank and p.fused_rows and p.chunk == p.n and SORT_ROOTS_MIN <= p.cn <= SORT_ROOTS_MAX and p.sort_roots and
                    p.walk_pos is None and rows_kernel_takes(p.M, p.m, p.bucket))
         p.walk_order = "rank" if p.by_rank else "id" if p.by_root else "batch"
+        p.work = None
         if p.by_rank and p.root_order.order is not None and _is_all_nodes(p.query, p.csr.num_nodes):
-            p.wl = p.root_order.order
-            p.nwl = torch.full((1,), p.cn, dtype=torch.int64, device=p.dev)
+            p.work = (p.root_order.order, torch.full((1,), p.cn, dtype=torch.int64, device=p.dev))
         elif p.by_root or p.by_rank:
-            p.wl = torch.empty(p.cn, dtype=torch.int32, device=p.dev)
-            p.nwl = torch.zeros(1, dtype=torch.int64, device=p.dev)
-            p.wws = torch.zeros(p.L.subgacc_worklist_workspace_bytes(p.cn), dtype=torch.uint8, device=p.dev)
+            p.wbufs = worklist_buffers(p.cn, p.dev)
             p.nsize.zero_()           # (a row that is not listed -- a root equal to SUBGACC_NO_ROOT -- reads as an empty set)
-            if p.by_rank:
-                check(p.L.subgacc_worklist_by_rank(ptr(p.q), p.cn, ptr(p.root_order.rank), p.csr.num_nodes, ptr(p.wl), ptr(p.nwl),
-                                                   ptr(p.wws), p.wws.numel(), p.st))
-            else:
-                check(p.L.subgacc_worklist_by_root(ptr(p.q), p.cn, p.csr.num_nodes, ptr(p.wl), ptr(p.nwl), ptr(p.wws), p.wws.numel(), p.st))
-        p.listed = p.by_root or p.by_rank
-        with _timed("walk_sets"):
-            if p.kform == 64:       # rows of 64-bit LP keys (4 hops, M >= 128): one chunk, optionally in work-list order
-                check(p.L.subgacc_walk_keyrows64(p.cfg, ptr(p.csr.indptr), ptr(p.csr.indices), p.csr.num_nodes, ptr(p.q), p.cn,
-                                               ptr(p.rng_pos) if p.rng_pos is not None else None,
-                                               ptr(p.rng_seed) if p.rng_seed is not None else None,
-                                               ptr(p.wl) if p.listed else None, ptr(p.nwl) if p.listed else None,
-                                               ptr(p.st_ids), ptr(p.st_aux), ptr(p.nsize), ptr(p.flags), p.st))
-            elif p.listed:
-                check(p.L.subgacc_walk_spg_list(p.cfg, ptr(p.csr.indptr), ptr(p.csr.indices), p.csr.num_nodes, ptr(p.q), p.cn,
-                                              ptr(p.rng_pos) if p.rng_pos is not None else None,
-                                              ptr(p.rng_seed) if p.rng_seed is not None else None, ptr(p.wl), ptr(p.nwl),
-                                              None if p.batched else ptr(p.table), 0 if (p.key_rows or p.batched) else p.uniq_capacity,
-                                              ptr(p.st_ids), ptr(p.st_aux), ptr(p.nsize), ptr(p.flags), p.st))
-            elif p.fused_rows:
-                check(p.L.subgacc_walk_spg(p.cfg, ptr(p.csr.indptr), ptr(p.csr.indices), p.csr.num_nodes, ptr(p.q[p.lo:]), p.cn, p.lo,
-                                         ptr(p.rng_pos[p.lo:]) if p.rng_pos is not None else None,
-                                         ptr(p.rng_seed[p.lo:]) if p.rng_seed is not None else None,
-                                         None if p.batched else ptr(p.table), 0 if (p.key_rows or p.batched) else p.uniq_capacity,
-                                         ptr(p.st_ids), ptr(p.st_aux), ptr(p.nsize[p.lo:]), ptr(p.flags), p.st))
-            else:
-                check(p.L.subgacc_walk_sets(p.cfg, ptr(p.csr.indptr), ptr(p.csr.indices), p.csr.num_nodes, ptr(p.q[p.lo:]), p.cn,
-                                          ptr(p.rng_pos[p.lo:]) if p.rng_pos is not None else None,
-                                          ptr(p.rng_seed[p.lo:]) if p.rng_seed is not None else None,
-                                          ptr(p.st_ids), ptr(p.st_aux), ptr(p.nsize[p.lo:]),
-                                          ptr(p.walks[p.lo:]) if p.walks is not None else None, ptr(p.flags), p.st))
+            p.work = sorted_worklist(p.csr, p.q, p.cn, p.root_order.rank if p.by_rank else None, p.wbufs, p.st)
+        p.rng_chunk = (p.rng_pos[p.lo:], p.rng_seed[p.lo:]) if p.rng_pos is not None else (None, None)
+        with _timed("walk_sets"):          # (a work list only with one chunk: p.lo = 0)
+            _walk(p.cfg, p.csr, p.q[p.lo:], p.cn, p.flags, p.st, "keys64" if p.kform == 64 else "fused" if p.fused_rows else "sets",
+                  ids=p.st_ids, payload=p.st_aux, nsize=p.nsize[p.lo:],
+                  walks=p.walks[p.lo:] if p.walks is not None else None, rng=p.rng_chunk, table=None if p.batched else p.table,
+                  capacity=0 if (p.key_rows or p.batched) else p.uniq_capacity, work=p.work, root_base=p.lo)
         if not p.strided:
             check(p.L.subgacc_exclusive_scan_i32(ptr(p.nsize[p.lo:]), p.cn, ptr(p.off_chunk), ptr(p.scan_ws), p.scan_ws.numel(), p.st))
         if p.finish:            # (ids in first-visit order, keys) -> (ids sorted, table slots), in place: finished rows
@@ -851,7 +868,6 @@ def _launch_sets(p):
             p.ccap = p.L.subgacc_keyrows_cand_capacity(p.cn)
             p.cand = torch.empty(p.ccap, dtype=torch.int32, device=p.dev)
             p.ncand = torch.zeros(1, dtype=torch.int64, device=p.dev)
-            p.rp, p.rs = (ptr(p.rng_pos[p.lo:]), ptr(p.rng_seed[p.lo:])) if p.rng_pos is not None else (None, None)
             if p.numbered_early:      # one chunk: register -> exact tags for the candidates -> number (below) -> copy with SFptr+1
                 with _timed("register_rows"):
                     check(p.L.subgacc_keyrows_register(ptr(p.st_aux), ptr(p.nsize[p.lo:]), p.cn, p.stride, p.lo, ptr(p.table), p.uniq_capacity,
@@ -859,10 +875,10 @@ def _launch_sets(p):
                     if p.lazy:
                         p.total, p.wcap = p.cn * p.stride, 0
                     else:           # the one host read of the chunk carries the candidate count along
-                        p.total, p.wcap = (int(p.v) for p.v in torch.cat([p.off_chunk[p.cn:p.cn + 1], p.ncand]).tolist())
+                        p.total, p.wcap = torch.cat([p.off_chunk[p.cn:p.cn + 1], p.ncand]).tolist()
                         p.wcap = max(min(p.wcap, p.cn), 1)
-                    check(p.L.subgacc_walk_tags(p.cfg, ptr(p.csr.indptr), ptr(p.csr.indices), p.csr.num_nodes, ptr(p.q[p.lo:]), p.cn, p.lo, p.rp, p.rs,
-                                              ptr(p.cand), ptr(p.ncand), p.wcap, ptr(p.table), p.uniq_capacity, ptr(p.flags), p.st))
+                    _walk(p.cfg, p.csr, p.q[p.lo:], p.cn, p.flags, p.st, "tags", rng=p.rng_chunk, table=p.table, capacity=p.uniq_capacity,
+                          work=(p.cand, p.ncand), root_base=p.lo, work_cap=p.wcap)
         if p.strided and not p.numbered_early:
             p.ukeys, p.max_unique = None, p.uniq_capacity
         if p.numbered_early:    # one chunk: the table is complete -> number it now and let the copy emit SFptr+1
@@ -884,11 +900,7 @@ def _launch_sets(p):
             if not p.lazy:      # eager: same recovery as the packed forms below
                 p.st_host = unpack_status(p.status.tolist())
                 if p.st_host[2]:                    # the table of distinct LP rows overflowed: walk again with a larger one
-                    return sample_sets(p.csr, p.q, p.num_walks, p.num_steps, p.bucket, p.seed, p.rng, p.first_hop_wo, p.order,
-                                       p.cap_root_degree, p.emit_walks, p.rng_streams, p.calls_before, p.dedup, p.keep_keys,
-                                       p.staging_bytes, p.uniq_capacity * 4, p.uniq_small_limit, p.fused_rows, p.lazy, p.strided,
-                                       p.number_rows, key_rows=p.key_rows_arg, walk_replay=p.walk_replay,
-                                       batched_registration=p.batched_registration, sort_roots=p.sort_roots, rng_state=p.rng_state, root_order=p.root_order)
+                    return _GROW
                 if p.st_host[4] > p.max_unique:       # more distinct rows than the direct ranking numbers: the caller
                     return None                   # (sample_spg) falls through to the packed forms
                 p.sets.resolve()
@@ -906,8 +918,8 @@ def _launch_sets(p):
                                                 ptr(p.count) if p.numbered_early else None, p.max_unique if p.numbered_early else 0,
                                                 ptr(p.ids_c), ptr(p.slot_c), ptr(p.cand), p.ccap, ptr(p.ncand), ptr(p.flags), p.st))
                 if not p.numbered_early:    # the pass registered this chunk's keys itself: now the candidates' exact tags
-                    check(p.L.subgacc_walk_tags(p.cfg, ptr(p.csr.indptr), ptr(p.csr.indices), p.csr.num_nodes, ptr(p.q[p.lo:]), p.cn, p.lo, p.rp, p.rs,
-                                              ptr(p.cand), ptr(p.ncand), 0, ptr(p.table), p.uniq_capacity, ptr(p.flags), p.st))
+                    _walk(p.cfg, p.csr, p.q[p.lo:], p.cn, p.flags, p.st, "tags", rng=p.rng_chunk, table=p.table, capacity=p.uniq_capacity,
+                          work=(p.cand, p.ncand), root_base=p.lo)
             elif p.fused_rows:
                 check(p.L.subgacc_compact_rows(ptr(p.st_ids), ptr(p.st_aux), ptr(p.nsize[p.lo:]), ptr(p.off_chunk), p.cn, p.stride,
                                              ptr(p.ids_c), ptr(p.slot_c), ptr(p.table) if p.numbered_early else None,
@@ -982,10 +994,7 @@ def _finish_sets(p):
     if p.fused_rows and not p.st_host[2] and p.st_host[4] > p.max_unique:
         return None           # more distinct rows than the direct ranking handles: the caller takes the general path
     if p.st_host[2]:
-        return sample_sets(p.csr, p.q, p.num_walks, p.num_steps, p.bucket, p.seed, p.rng, p.first_hop_wo, p.order, p.cap_root_degree,
-                           p.emit_walks, p.rng_streams, p.calls_before, p.dedup, p.keep_keys, p.staging_bytes, p.uniq_capacity * 4,
-                           p.uniq_small_limit, p.fused_rows, p.lazy, p.strided, p.number_rows, key_rows=p.key_rows_arg, walk_replay=p.walk_replay,
-                           batched_registration=p.batched_registration, sort_roots=p.sort_roots, rng_state=p.rng_state, root_order=p.root_order)
+        return _GROW
     p.sets.resolve()
     p.sets.ukeys = p.sets.ukeys.clone()
     return p.sets

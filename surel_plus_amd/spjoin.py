@@ -584,25 +584,9 @@ def _dedup_tick(bufs):
         bufs.dedup_steps = 0
 
 
-def _sorted_list(bufs, csr, n, L, st):
-    """the rows of the step as a work list in ascending order of root id (csrc/worklist.hip) -- of rank, with StepBuffers(order=);
-    rows whose root is SUBGACC_NO_ROOT are left out.  Its buffers are made on first use"""
-    if not hasattr(bufs, "sorted_list"):
-        dev = csr.device
-        bufs.sorted_list = torch.empty(n, dtype=torch.int32, device=dev)
-        bufs.n_all = torch.zeros(1, dtype=torch.int64, device=dev)
-        bufs.sort_ws = torch.zeros(L.subgacc_worklist_workspace_bytes(n), dtype=torch.uint8, device=dev)      # (zeroed once: every call leaves it so)
-    if bufs.order is not None:
-        check(L.subgacc_worklist_by_rank(ptr(bufs.roots), n, ptr(bufs.order.rank), csr.num_nodes, ptr(bufs.sorted_list), ptr(bufs.n_all),
-                                         ptr(bufs.sort_ws), bufs.sort_ws.numel(), st))
-    else:
-        check(L.subgacc_worklist_by_root(ptr(bufs.roots), n, csr.num_nodes, ptr(bufs.sorted_list), ptr(bufs.n_all), ptr(bufs.sort_ws),
-                                         bufs.sort_ws.numel(), st))
-
-
 def _buffered_step(csr, e, bufs, seed, out):
     """sample_and_gather through a StepBuffers: six launches, nothing allocated, nothing read back"""
-    from .sampler import SampledSets, _timed, make_cfg, walk_kernel_name
+    from .sampler import SampledSets, _timed, _walk, make_cfg, sorted_worklist, walk_kernel_name, worklist_buffers
     L, st, dev = lib(), stream_ptr(), csr.device
     B, M, m, k, n = bufs.B, bufs.M, bufs.m, bufs.k, 2 * bufs.B
     PB = bufs.batch              # pairs per mirrored block of the segment list
@@ -614,7 +598,6 @@ def _buffered_step(csr, e, bufs, seed, out):
     cfg = make_cfg(csr, M, m, -1, seed, bufs.rng, records=(2 <= m <= 4),     # (only the fused-row kernel of 2..4 hops reads hop records)
                    row_pitch=bufs.stride if bufs.stride != bufs.Q else 0)
     rr = bufs.rng == "rand_r"
-    rp, rs = (ptr(bufs.rng_pos), ptr(bufs.rng_seed)) if rr else (None, None)
     check(L.subgacc_key_shift(cfg.num_walks, cfg.num_steps))
     kr = bufs.keyrows
     bufs.step_id = step_id = getattr(bufs, "step_id", 0) + 1
@@ -634,27 +617,22 @@ def _buffered_step(csr, e, bufs, seed, out):
     # (or rank): roots that are neighbours in id space -- the same community of a graph with id locality -- are walked at the same
     # time on the same XCD and share its L2
     if bufs.dedup and bufs.order is None:
-        wl, nwl, bufs.walk_order = bufs.worklist, bufs.n_distinct, "batch"
+        work, bufs.walk_order = (bufs.worklist, bufs.n_distinct), "batch"
     elif bufs.dedup or (((bufs.order is not None) or (bufs.sort_roots and n >= SORT_ROOTS_MIN))
                         and walk_kernel_name(csr, M, m, True) == "walk_rows_kernel"):
-        _sorted_list(bufs, csr, n, L, st)
-        wl, nwl, bufs.walk_order = bufs.sorted_list, bufs.n_all, ("rank" if bufs.order is not None else "id")
+        if not hasattr(bufs, "sort_bufs"):        # (made on first use)
+            bufs.sort_bufs = worklist_buffers(n, dev)
+        work = sorted_worklist(csr, bufs.roots, n, bufs.order.rank if bufs.order is not None else None, bufs.sort_bufs, st)
+        bufs.walk_order = "rank" if bufs.order is not None else "id"
     else:
-        wl, nwl, bufs.walk_order = None, None, "batch"
+        work, bufs.walk_order = None, "batch"
     if rr:
         check(L.subgacc_rng_positions(cfg, ptr(csr.indptr), csr.num_nodes, ptr(bufs.roots), n, 1, 0, ptr(bufs.rng_pos),
                                       ptr(bufs.rng_seed), ptr(bufs.rng_ws), bufs.rng_ws.numel(), st))
-    graph = (cfg, ptr(csr.indptr), ptr(csr.indices), csr.num_nodes, ptr(bufs.roots), n)
-    rows = (ptr(bufs.ids), ptr(bufs.slot), ptr(bufs.nsize), ptr(flags), st)
-    with _timed("walk_sets"):
-        if bufs.key64:
-            check(L.subgacc_walk_keyrows64(*graph, rp, rs, ptr(wl), ptr(nwl), *rows))
-        elif bufs.dedup:
-            check(L.subgacc_walk_spg_sparse(*graph, ptr(wl), ptr(nwl), *tab, *rows))
-        elif wl is not None:
-            check(L.subgacc_walk_spg_list(*graph, rp, rs, ptr(wl), ptr(nwl), *tab, *rows))
-        else:
-            check(L.subgacc_walk_spg(*graph, 0, rp, rs, *tab, *rows))
+    with _timed("walk_sets"):         # (root dedup: the list selects the first occurrences, the other rows are passed over)
+        _walk(cfg, csr, bufs.roots, n, flags, st, "keys64" if bufs.key64 else "fused", ids=bufs.ids, payload=bufs.slot,
+              nsize=bufs.nsize, rng=(bufs.rng_pos, bufs.rng_seed) if rr else (None, None), table=bufs.table,
+              capacity=0 if kr else bufs.capacity, work=work, select=bufs.dedup)
     own, partner = (bufs.own, bufs.partner) if bufs.dedup else _arange_segments(B, dev, PB)
     check(L.subgacc_sjoin_sizes_rows(ptr(bufs.nsize), n, ptr(own), ptr(partner), n, ptr(bufs.seg), ptr(flags), ptr(bufs.ws),
                                      bufs.ws.numel(), st))

@@ -145,3 +145,75 @@ def test_headed_sizes_only_call_needs_ids(L):
     assert b"ids" in L.subgacc_last_error()
     d.ids = here                                                                # with ids: on to the missing state, as before
     assert L.subgacc_sjoin_fill_v2(C.byref(d), None) == _lib.ERR_WORKSPACE
+
+
+def test_walk_entry_points_refuse_before_launching(L):
+    """Each of the six subgacc_walk_* entry points refuses an argument fault before anything is launched (no GPU needed): one fault
+    per call, its return code and a piece of subgacc_last_error()'s text."""
+    import ctypes as C
+    from surel_plus_amd import _lib
+    buf = (C.c_int64 * 64)()
+    here = C.addressof(buf)               # any non-null pointer: nothing is read through it before the refusal
+
+    def cfg(M=100, m=3, **kw):            # philox, set_sampler order, no bucket: every entry point accepts it
+        c = _lib.WalkCfg(M, m, -1, _lib.RNG_PHILOX, 111413, 1, _lib.ORDER_WALK_MAJOR, 1, 0, 0, None, 0, 0, None, 0)
+        for k, v in kw.items():
+            setattr(c, k, v)
+        return C.byref(c)
+
+    graph = (here, here, 10)              # indptr, indices, num_nodes
+
+    def sets(c=None, num_nodes=10, query=here, n=4, rng=(None, None), keys=here, walks=None, flags=here):
+        return L.subgacc_walk_sets(c or cfg(), here, here, num_nodes, query, n, *rng, here, keys, here, walks, flags, None)
+
+    def spg(c=None, root_base=0, table=here, cap=1024, ids=here, slot=here):
+        return L.subgacc_walk_spg(c or cfg(), *graph, here, 4, root_base, None, None, table, cap, ids, slot, here, here, None)
+
+    def sparse(c=None, wl=here, nwl=here):
+        return L.subgacc_walk_spg_sparse(c or cfg(), *graph, here, 4, wl, nwl, here, 1024, here, here, here, here, None)
+
+    def listed(c=None, wl=here, nwl=here):
+        return L.subgacc_walk_spg_list(c or cfg(), *graph, here, 4, None, None, wl, nwl, here, 1024, here, here, here, here, None)
+
+    def keys64(c=None, keys=here, flags=here):
+        return L.subgacc_walk_keyrows64(c or cfg(200, 4), *graph, here, 4, None, None, here, here, here, keys, here, flags, None)
+
+    def tags(c=None, work_cap=0, table=here, cap=1024, flags=here):
+        return L.subgacc_walk_tags(c or cfg(), *graph, here, 4, 0, None, None, here, here, work_cap, table, cap, flags, None)
+
+    cases = [
+        (lambda: sets(keys=None), _lib.ERR_BADARG, b"null set_keys"),
+        (lambda: sets(flags=None), _lib.ERR_BADARG, b"null argument"),
+        (lambda: sets(n=-1), _lib.ERR_BADARG, b"negative size"),
+        (lambda: sets(cfg(rng_mode=7)), _lib.ERR_BADARG, b"unknown rng_mode"),
+        (lambda: sets(cfg(200, 8)), _lib.ERR_KEYWIDTH, b"hasing key"),
+        (lambda: sets(cfg(emit_walks=1)), _lib.ERR_BADARG, b"emit_walks without a walks buffer"),
+        (lambda: sets(cfg(rng_mode=_lib.RNG_RAND_R)), _lib.ERR_BADARG, b"RAND_R mode needs rng_pos"),
+        (lambda: sets(query=None), _lib.ERR_BADARG, b"null query"),
+        (lambda: sets(num_nodes=0), _lib.ERR_BADARG, b"a graph without nodes"),
+        (lambda: sets(cfg(row_pitch=10)), _lib.ERR_BADARG, b"row_pitch 10 < the row capacity 301"),
+        (lambda: sets(cfg(hop_records=here, rec_id_bits=40, rec_beg_bits=30)), _lib.ERR_BADARG, b"hop records with field widths 40 / 30"),
+        (lambda: spg(slot=None), _lib.ERR_BADARG, b"null row_slot"),
+        (lambda: spg(cfg(emit_walks=1)), _lib.ERR_BADARG, b"walk_spg: set_sampler order only, no raw walks"),
+        (lambda: spg(cfg(order=_lib.ORDER_STEP_MAJOR)), _lib.ERR_BADARG, b"walk_spg: set_sampler order only"),
+        (lambda: spg(ids=None), _lib.ERR_BADARG, b"null argument"),
+        (lambda: spg(cfg(256, 4)), _lib.ERR_LDS, b"needs a per-root table above 1024 slots"),
+        (lambda: spg(cap=1000), _lib.ERR_BADARG, b"power-of-two table"),
+        (lambda: spg(root_base=-1), _lib.ERR_BADARG, b"power-of-two table"),
+        (lambda: sparse(cfg(rng_mode=_lib.RNG_RAND_R)), _lib.ERR_BADARG, b"Philox mode"),
+        (lambda: sparse(nwl=None), _lib.ERR_BADARG, b"a work list without its length"),
+        (lambda: listed(wl=None), _lib.ERR_BADARG, b"null row_slot / work list / length"),
+        (lambda: listed(cfg(emit_walks=1)), _lib.ERR_BADARG, b"walk_spg_list: set_sampler order only, no raw walks"),
+        (lambda: keys64(cfg(100, 3)), _lib.ERR_BADARG, b"fit 32 bits"),
+        (lambda: keys64(cfg(200, 4, bucket=50)), _lib.ERR_BADARG, b"no bucket"),
+        (lambda: keys64(keys=None), _lib.ERR_BADARG, b"null row_keys"),
+        (lambda: keys64(flags=None), _lib.ERR_BADARG, b"null argument"),
+        (lambda: tags(table=None), _lib.ERR_BADARG, b"needs a work list, its length and a table"),
+        (lambda: tags(work_cap=-1), _lib.ERR_BADARG, b"needs a work list, its length and a table"),
+        (lambda: tags(cfg(bucket=50)), _lib.ERR_BADARG, b"walk_tags: set_sampler order, no raw walks, no bucket"),
+        (lambda: tags(flags=None), _lib.ERR_BADARG, b"null argument"),
+        (lambda: tags(cap=1000), _lib.ERR_BADARG, b"power-of-two table"),
+    ]
+    for i, (call, want, text) in enumerate(cases):
+        rc = call()
+        assert rc == want and text in L.subgacc_last_error(), (i, rc, L.subgacc_last_error())
