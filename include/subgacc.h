@@ -413,6 +413,40 @@ int subgacc_sjoin_relu_attn_backward(const subgacc_join_desc *d, const float *w1
                                      const float *g, const float *a, const float *max, const float *den, float *out_dw, float *out_db,
                                      float *out_du, void *stream);
 
+/* The LP encoder's first stage with attentional aggregation (--aggr attn: model.py:59-62,78-81, one-Linear gate_nn (wg, bg) and nn)
+ * fused with the count form of the join.  Member t of segment j is the index pair (p_t, q_t) -- SFptr+1 of the member in its own row,
+ * in the partner row or 0 (SUBGACC_JOIN_COUNTS) -- and its row is E[p_t] + E[q_t] with E = pe_embedding(Z_SF) [T, H], so with
+ * g = E wg (f32 [T]; the gate bias is a constant the softmax drops) the gate logit is l_t = g[p_t] + g[q_t] and, the weights summing to
+ * 1, out_j = nn(W[j] @ E) [n_j > 0] with the softmax-weighted count row
+ *     W[j, r] = (sum_t e_t ([p_t = r] + [q_t = r])) / den_j,   e_t = expf(l_t - m_j),  m_j = max_t l_t,  den_j = sum_t e_t
+ * written densely (f32 [S, T], zeros where r does not occur in segment j); out_max / out_den (both or neither; f32 [S]) receive m_j
+ * and den_j for the backward.  Neither xz, nor the [R,2,H] activations, nor the pair rows exist.
+ * Summation order, the same on every path (either row of a pair staged, every run): l_t = one fp32 add; m_j a max (order-free); expf,
+ * never __expf; den_j an fp32 chain over the own row's members in ascending id order from 0; for each r, sum_t e_t c_t(r) an fp32 chain
+ * over the same members in the same order, adding e_t if p_t = r and then again if q_t = r; then one IEEE division by den_j.  No float
+ * is added atomically.  An empty segment (n_j = 0, or a row outside the store) gives a zero row and m_j = den_j = 0.
+ *   d        a count-form descriptor: form = SUBGACC_JOIN_COUNTS, payload SUBGACC_JOIN_SFPTR, packed rows (row_off, max_len), own /
+ *            partner (partner may be NULL), pair_block = P > 0, S = 2*P*nb, table_rows = T, flags (int32[4], caller zeroes); no out_*
+ *            field, no seg, no option bit.
+ *   g        f32 [T].
+ * Flags as the count form: flags[3] |= 1 a packed row longer than max_len, |= 2 an SFptr outside the table (read as row 0, never out of
+ * bounds), |= 4 a list that is not mirrored (the segments of such a pair are not written), |= 16 a row number outside the store.
+ * Refused with SUBGACC_ERR_BADARG before anything is launched: form != COUNTS or any option bit, a payload other than SFPTR, strided or
+ * headed rows, pair_block <= 0 or S not a multiple of 2*pair_block, own = NULL with S > 0, table_rows outside [1, 2^31), any out_* or
+ * seg field of the descriptor set, g / out_w NULL, exactly one of out_max / out_den.  LDS: 4 (7 max_len + 2 T + 2 D + 8) bytes,
+ * D = min(2 max_len, T) (the backward: 6 D) <= 160 KiB, else SUBGACC_ERR_LDS (the pair form, attn_stage, has no such bound). */
+int subgacc_sjoin_counts_attn(const subgacc_join_desc *d, const float *g, float *out_w, float *out_max, float *out_den, void *stream);
+
+/* The backward of subgacc_sjoin_counts_attn over the same descriptor: dw = dL/dW, w = W, max / den = m, den as the forward wrote them.
+ * The pair is joined again and e_t recomputed bit for bit; dw is read only at the segment's own LP rows.  With
+ *     kappa_j = sum_r W[j, r] dW[j, r]   an fmaf chain over the rows r that occur in segment j, r ascending, from 0,
+ *     beta_t = alpha_t ((dW[j, p_t] + dW[j, q_t]) - kappa_j),   alpha_t = e_t / den_j  (one add, one subtraction, one product),
+ * out_dg (f32 [S, T]) receives per segment  Dg_j[r] = sum_t beta_t ([p_t = r] + [q_t = r])  in the forward's order (members in ascending
+ * id order from 0, beta_t if p_t = r, then again if q_t = r), zeros elsewhere; dL/dg = sum_j Dg_j (no atomics).  An empty segment gives
+ * a zero row.  Flags and refusals as the forward's; g, dw, w, max, den and out_dg are required. */
+int subgacc_sjoin_counts_attn_backward(const subgacc_join_desc *d, const float *g, const float *dw, const float *w, const float *max,
+                                       const float *den, float *out_dg, void *stream);
+
 
 /* Packed rows -> headed rows (ABI 7): the resident store of a serving loop laid out on whole lines -- the rows random_walks.py:79-81
  * builds as a SciPy CSR and train.py:17-18 / :39-43 slice one by one (x[edge[0]]), in the layout the pair kernels read with one

@@ -37,7 +37,7 @@ SYMBOLS = (
     "subgacc_keyrows_register", "subgacc_keyrows_cand_capacity", "subgacc_walk_tags", "subgacc_keyrows_compact", "subgacc_keyrows_translate", "subgacc_rng_replay", "subgacc_walk_keyrows64", "subgacc_worklist_workspace_bytes", "subgacc_worklist_by_root", "subgacc_walk_spg_list",
     "subgacc_locality_round", "subgacc_worklist_by_rank",
     "subgacc_sjoin_fill_v2", "subgacc_publish_words", "subgacc_rows_to_headed", "subgacc_sjoin_star_sizes", "subgacc_sjoin_relu_mean",
-    "subgacc_sjoin_relu_attn", "subgacc_sjoin_relu_attn_backward",
+    "subgacc_sjoin_relu_attn", "subgacc_sjoin_relu_attn_backward", "subgacc_sjoin_counts_attn", "subgacc_sjoin_counts_attn_backward",
 )
 
 
@@ -162,6 +162,8 @@ def lib():
     sig["subgacc_sjoin_relu_mean"] = (C.c_int, [C.POINTER(JoinDesc), vp, vp, i32, vp, vp, vp, vp])
     sig["subgacc_sjoin_relu_attn"] = (C.c_int, [C.POINTER(JoinDesc), vp, vp, vp, i32, vp, vp, vp, vp])
     sig["subgacc_sjoin_relu_attn_backward"] = (C.c_int, [C.POINTER(JoinDesc), vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp])
+    sig["subgacc_sjoin_counts_attn"] = (C.c_int, [C.POINTER(JoinDesc), vp, vp, vp, vp, vp])
+    sig["subgacc_sjoin_counts_attn_backward"] = (C.c_int, [C.POINTER(JoinDesc), vp, vp, vp, vp, vp, vp, vp])
     assert set(sig) == set(SYMBOLS)
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -18,8 +18,10 @@
 //   sjoin_fill_kernel                   any other list: one wave per segment, the partner row in LDS (or searched in place when it
 //                                       does not fit)
 //   sjoin_counts_kernel / sjoin_pairs_kernel   the count and pair forms of the join
+//   sjoin_counts_attn_kernel<BWD>       the count form with attentional aggregation (model.py:59-62,78-81, LP encoder): per segment the
+//                                       softmax-weighted count row W, and its backward (subgacc_sjoin_counts_attn[_backward])
 // One entry point for every form of the join, subgacc_sjoin_fill_v2(descriptor), and subgacc_sjoin_relu_mean / _relu_attn /
-// _relu_attn_backward for the fused stages, at the end of the file.
+// _relu_attn_backward / _counts_attn / _counts_attn_backward for the fused stages, at the end of the file.
 // The [R,2] index array of the reference never exists in memory unless asked for (out_idx).
 #include <cstdlib>
 #include "common.hpp"
@@ -1759,6 +1761,215 @@ __global__ __launch_bounds__(kPairThreads) void sjoin_counts_kernel(const JoinAr
     }
 }
 
+// Count form with attentional aggregation (model.py:59-62,78-81 for the LP encoder; include/subgacc.h: subgacc_sjoin_counts_attn).
+// Member t of segment j is the index pair (p_t, q_t) -- own LP row, partner LP row or 0 -- and its gate logit is l_t = g[p_t] + g[q_t]
+// with g = embed(encode) . wg, so the softmax-weighted sum of the rows collapses to W[j] @ embed(encode) with the softmax-weighted count
+// row W[j, r] = sum_t alpha_t ([p_t = r] + [q_t = r]).  The plan of sjoin_counts_kernel (the longer row staged, the shorter searched in
+// it once, a hit serving both blocks); every member's pair goes to LDS, the partner of a staged member from the hits (0 without one).
+// Then per block: the distinct LP rows are marked in a table-indexed array (integer writes and CAS: their LDS slots may come in any
+// order, nothing summed depends on it), and one lane per distinct row walks the block's members in ascending id order -- the documented
+// chain -- so no float is ever added atomically.  BWD: the same join, e_t recomputed from the forward's m_j, dW read at the block's
+// distinct rows only, kappa_j in ascending r (the distinct rows ranked by counting), beta_t per member, Dg_j[r] per distinct row.
+struct CountsAttnArgs {
+    const float *g;
+    float *out_w, *out_max, *out_den;           // forward
+    const float *dw, *w, *max, *den;            // backward
+    float *out_dg;
+};
+
+__device__ __forceinline__ int32_t ord_of(float f) {     // a float as an int of the same order (max by integer atomics: exact)
+    const int32_t b = __float_as_int(f);
+    return b >= 0 ? b : b ^ 0x7FFFFFFF;
+}
+__device__ __forceinline__ float float_of(int32_t o) { return __int_as_float(o >= 0 ? o : o ^ 0x7FFFFFFF); }
+
+// LDS of sjoin_counts_attn_kernel in 4-byte words: ids of the staged row, own / partner values and l / e / beta of both blocks, the
+// two table-indexed arrays, the distinct rows of both blocks (the backward: with W and dW in ascending r), 8 words of block state
+static size_t counts_attn_lds(int64_t max_len, int64_t rows, int64_t dcap, bool bwd) {
+    return 4 * ((size_t)max_len * 7 + (size_t)rows * 2 + (size_t)dcap * (bwd ? 6 : 2) + 8);
+}
+
+template <bool BWD>
+__global__ __launch_bounds__(kPairThreads) void sjoin_counts_attn_kernel(const JoinArgs a, int64_t pb, int32_t dcap, const CountsAttnArgs c) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    const int L = a.max_len, rows = (int)a.table_rows;
+    int32_t *idsT = (int32_t *)lds_raw;                     // [L]
+    int32_t *val = idsT + L;                                // [2][L] own LP row of every member: block 0 = S, block 1 = T
+    int32_t *par = val + 2 * L;                             // [2][L] partner LP row (0 = absent)
+    float *ex = (float *)(par + 2 * L);                     // [2][L] l_t, then e_t (BWD: then beta_t)
+    int32_t *mark = (int32_t *)(ex + 2 * L);                // [2][rows] 0 / 1 = occurs / 2 = listed; then the row's float
+    float *accf = (float *)mark;
+    int32_t *dist = mark + 2 * rows;                        // [2][dcap] the block's distinct rows, in slot order
+    float *srtW = (float *)(dist + 2 * dcap);               // BWD: [2][dcap] W[j, r] and dW[j, r] in ascending r
+    float *srtD = srtW + 2 * dcap;
+    int32_t *st = BWD ? (int32_t *)(srtD + 2 * dcap) : (int32_t *)srtW;   // [8]: distinct count, max (ordered), den, kappa per block
+    float *stf = (float *)st;
+
+    const int64_t p = xcd_item(blockIdx.x, gridDim.x);
+    if (p >= a.S / 2) return;
+    const int64_t j = (p / pb) * 2 * pb + (p % pb), j2 = j + pb;
+    const int tid = threadIdx.x;
+    const int64_t ra = a.own[j], rb = join_partner(a, j);
+    if (a.own[j2] != rb || join_partner(a, j2) != ra) {
+        if (tid == 0) atomicOr(&a.flags[3], 4);
+        return;
+    }
+    if (tid == 0 && ((uint64_t)ra >= (uint64_t)a.n_rows || (uint64_t)rb >= (uint64_t)a.n_rows)) atomicOr(&a.flags[3], 16);
+    int64_t ab, na64, bb, nb64;
+    join_row(a, ra, ab, na64);
+    join_row(a, rb, bb, nb64);
+    if (na64 > a.max_len || nb64 > a.max_len) {
+        if (tid == 0) atomicOr(&a.flags[3], 1);
+        return;
+    }
+    const bool swap = na64 > nb64;
+    const int ns = (int)(swap ? nb64 : na64), nt = (int)(swap ? na64 : nb64);
+    const int64_t sb = swap ? bb : ab, tb = swap ? ab : bb, jS = swap ? j2 : j, jT = swap ? j : j2;
+    const int32_t *data = (const int32_t *)a.data;
+    constexpr int kTrips = 2;
+    int32_t sid[kTrips], sval[kTrips];
+#pragma unroll
+    for (int u = 0; u < kTrips; ++u) {
+        const int r = tid + u * kPairThreads;
+        sid[u] = 0, sval[u] = 0;
+        if (r < ns) sid[u] = stream_load(&a.indices[sb + r]), sval[u] = stream_load(&data[sb + r]);
+    }
+    for (int x = tid; x < 2 * rows; x += kPairThreads) mark[x] = 0;
+    if (tid < 8) st[tid] = (tid == 2 || tid == 3) ? INT32_MIN : 0;
+    for (int r = tid; r < nt; r += kPairThreads) {
+        idsT[r] = stream_load(&a.indices[tb + r]);
+        int32_t v = stream_load(&data[tb + r]);
+        if ((uint32_t)v >= (uint32_t)rows) atomicOr(&a.flags[3], 2), v = 0;     // SFptr outside the table: never read out of bounds
+        val[L + r] = v, par[L + r] = 0;
+    }
+    __syncthreads();
+    for (int r0 = 0; r0 < ns; r0 += kPairThreads) {     // S: search T once; a hit gives each block its partner value
+        const int r = r0 + tid, u = r0 / kPairThreads;
+        if (r >= ns) break;
+        int32_t id, v;
+        if (u < kTrips) {
+            id = u == 0 ? sid[0] : sid[1];
+            v = u == 0 ? sval[0] : sval[1];
+        } else {
+            id = stream_load(&a.indices[sb + r]);
+            v = stream_load(&data[sb + r]);
+        }
+        if ((uint32_t)v >= (uint32_t)rows) atomicOr(&a.flags[3], 2), v = 0;
+        int b = 0, n = nt;
+        while (n > 1) {
+            const int h = n >> 1;
+            b = idsT[b + h] <= id ? b + h : b;
+            n -= h;
+        }
+        const bool hit = n == 1 && idsT[b] == id;
+        val[r] = v;
+        par[r] = hit ? val[L + b] : 0;
+        if (hit) par[L + b] = v;
+    }
+    __syncthreads();
+    const int ntot = ns + nt;
+    int32_t mo0 = INT32_MIN, mo1 = INT32_MIN;
+    for (int i = tid; i < ntot; i += kPairThreads) {    // logits, the rows that occur, the block max
+        const int blk = i >= ns, k = blk ? i - ns + L : i;
+        const int32_t pv = val[k], qv = par[k];
+        const float l = c.g[pv] + c.g[qv];
+        ex[k] = l;
+        mark[blk * rows + pv] = 1, mark[blk * rows + qv] = 1;
+        if (blk) mo1 = max(mo1, ord_of(l));
+        else mo0 = max(mo0, ord_of(l));
+    }
+    if (!BWD) {
+        if (mo0 != INT32_MIN) atomicMax(&st[2], mo0);
+        if (mo1 != INT32_MIN) atomicMax(&st[3], mo1);
+    }
+    __syncthreads();
+    const float m0 = BWD ? (ns ? c.max[jS] : 0.f) : (ns ? float_of(st[2]) : 0.f);
+    const float m1 = BWD ? (nt ? c.max[jT] : 0.f) : (nt ? float_of(st[3]) : 0.f);
+    for (int i = tid; i < ntot; i += kPairThreads) {    // e_t, and every distinct row listed once
+        const int blk = i >= ns, k = blk ? i - ns + L : i;
+        ex[k] = expf(ex[k] - (blk ? m1 : m0));
+        const int32_t rr[2] = {val[k], par[k]};
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+            if (atomicCAS(&mark[blk * rows + rr[s]], 1, 2) == 1) dist[blk * dcap + atomicAdd(&st[blk], 1)] = rr[s];
+    }
+    __syncthreads();
+    const int c0 = st[0], c1 = st[1];
+    if (!BWD) {
+        // one lane per distinct row of a block: den_j and sum_t e_t c_t(r), each an fp32 chain over the members in ascending id order
+        // (every lane of a block computes den_j in the same order: the same bits), then one division
+        for (int x = tid; x < c0 + c1; x += kPairThreads) {
+            const int blk = x >= c0, off = blk ? L : 0, n = blk ? nt : ns;
+            const int32_t r = dist[blk ? dcap + x - c0 : x];
+            float den = 0.f, s = 0.f;
+            for (int i = 0; i < n; ++i) {
+                const float e = ex[off + i];
+                den += e;
+                s += val[off + i] == r ? e : 0.f;
+                s += par[off + i] == r ? e : 0.f;
+            }
+            accf[blk * rows + r] = s / den;
+            if (x == (blk ? c0 : 0)) stf[4 + blk] = den;
+        }
+        __syncthreads();
+        float *outS = c.out_w + jS * (int64_t)rows, *outT = c.out_w + jT * (int64_t)rows;
+        for (int x = tid; x < rows; x += kPairThreads) {
+            __builtin_nontemporal_store(accf[x], outS + x);
+            __builtin_nontemporal_store(accf[rows + x], outT + x);
+        }
+        if (tid == 0 && c.out_max) {
+            c.out_max[jS] = m0, c.out_max[jT] = m1;
+            c.out_den[jS] = ns ? stf[4] : 0.f, c.out_den[jT] = nt ? stf[5] : 0.f;
+        }
+        return;
+    }
+    // ---- backward: dW and W at the distinct rows, each row's rank among them by counting (no sort; the ranks are distinct)
+    for (int x = tid; x < c0 + c1; x += kPairThreads) {
+        const int blk = x >= c0, cb = blk ? c1 : c0;
+        const int32_t *d = dist + blk * dcap;
+        const int32_t r = d[blk ? x - c0 : x];
+        const int64_t row = (blk ? jT : jS) * (int64_t)rows + r;
+        const float dwv = c.dw[row], wv = c.w[row];
+        int rank = 0;
+        for (int y = 0; y < cb; ++y) rank += d[y] < r;
+        srtW[blk * dcap + rank] = wv, srtD[blk * dcap + rank] = dwv;
+        accf[blk * rows + r] = dwv;
+    }
+    __syncthreads();
+    if (tid == 0 || tid == kWave) {       // kappa_j = sum_r W[j, r] dW[j, r]: an fmaf chain over the block's rows, r ascending
+        const int blk = tid == kWave, cb = blk ? c1 : c0;
+        float kap = 0.f;
+        for (int y = 0; y < cb; ++y) kap = fmaf(srtW[blk * dcap + y], srtD[blk * dcap + y], kap);
+        stf[6 + blk] = kap;
+    }
+    __syncthreads();
+    const float den0 = ns ? c.den[jS] : 1.f, den1 = nt ? c.den[jT] : 1.f;
+    for (int i = tid; i < ntot; i += kPairThreads) {    // beta_t = alpha_t (dW[p_t] + dW[q_t] - kappa_j), alpha_t = e_t / den_j
+        const int blk = i >= ns, k = blk ? i - ns + L : i;
+        const float alpha = ex[k] / (blk ? den1 : den0);
+        const float sdw = accf[blk * rows + val[k]] + accf[blk * rows + par[k]];
+        ex[k] = alpha * (sdw - stf[6 + blk]);
+    }
+    __syncthreads();
+    for (int x = tid; x < c0 + c1; x += kPairThreads) {  // Dg_j[r]: an fp32 chain over the members in ascending id order
+        const int blk = x >= c0, off = blk ? L : 0, n = blk ? nt : ns;
+        const int32_t r = dist[blk ? dcap + x - c0 : x];
+        float s = 0.f;
+        for (int i = 0; i < n; ++i) {
+            const float bt = ex[off + i];
+            s += val[off + i] == r ? bt : 0.f;
+            s += par[off + i] == r ? bt : 0.f;
+        }
+        accf[blk * rows + r] = s;
+    }
+    __syncthreads();
+    float *outS = c.out_dg + jS * (int64_t)rows, *outT = c.out_dg + jT * (int64_t)rows;
+    for (int x = tid; x < rows; x += kPairThreads) {
+        __builtin_nontemporal_store(accf[x], outS + x);
+        __builtin_nontemporal_store(accf[rows + x], outT + x);
+    }
+}
+
 
 // ---------------------------------------------------------------------------------------------------------
 // Pair form of the join (SURVEY.md 8(f).1 for the aggregations that are NOT linear in the rows -- the attention gate of
@@ -2453,4 +2664,85 @@ extern "C" int subgacc_sjoin_relu_attn_backward(const subgacc_join_desc *d, cons
                        (uint32_t)d->pair_block, (uint32_t)(d->S / 2), cap, m);
     SG_LAUNCH_CHECK();
     return SUBGACC_OK;
+}
+
+// The LP encoder's first stage with attentional aggregation fused with the count form (include/subgacc.h): the descriptor of a mirrored
+// count-form join of a packed SFptr store, no output of the descriptor's own.  Every refusal comes before anything is launched.
+static int counts_attn_check(const char *name, const subgacc_join_desc *d) {
+    SG_REQUIRE(d, SUBGACC_ERR_BADARG, "%s: null descriptor", name);
+    SG_REQUIRE(d->struct_bytes == (int32_t)sizeof(subgacc_join_desc), SUBGACC_ERR_BADARG,
+               "%s: descriptor of %d bytes, this library's is %d (set struct_bytes = sizeof(subgacc_join_desc))", name,
+               (int)d->struct_bytes, (int)sizeof(subgacc_join_desc));
+    const int64_t S = d->S, pb = d->pair_block;
+    SG_REQUIRE(d->form == SUBGACC_JOIN_COUNTS && d->options == 0, SUBGACC_ERR_BADARG,
+               "%s: form must be COUNTS and options 0 (form %d, options %d)", name, (int)d->form, (int)d->options);
+    SG_REQUIRE(d->payload_kind == SUBGACC_JOIN_SFPTR, SUBGACC_ERR_BADARG,
+               "%s: the count form joins an SFptr payload (SFPTR), not payload kind %d", name, (int)d->payload_kind);
+    SG_REQUIRE(d->row_off && !d->row_len, SUBGACC_ERR_BADARG, "%s: joins packed rows (row_off set, row_len NULL), not strided or headed rows",
+               name);
+    SG_REQUIRE(pb > 0, SUBGACC_ERR_BADARG, "%s: needs a mirrored list, pair_block > 0 (pair_block = %lld)", name, (long long)pb);
+    SG_REQUIRE(S >= 0 && S % (2 * pb) == 0, SUBGACC_ERR_BADARG,
+               "%s: S = %lld is not a multiple of 2*pair_block = %lld", name, (long long)S, (long long)(2 * pb));
+    SG_REQUIRE(d->own || S == 0, SUBGACC_ERR_BADARG, "%s: own = NULL with S = %lld segments", name, (long long)S);
+    SG_REQUIRE(d->table_rows > 0 && d->table_rows < (1ll << 31), SUBGACC_ERR_BADARG, "%s: table_rows = %lld", name,
+               (long long)d->table_rows);
+    SG_REQUIRE(!d->out_xz && !d->out_idx && !d->out_segid && !d->out_counts && !d->out_pairs && !d->out_mult && !d->out_cnt &&
+                   !d->out_seg && !d->seg,
+               SUBGACC_ERR_BADARG, "%s: writes its own outputs only: the descriptor's out_* and seg fields must be NULL", name);
+    SG_REQUIRE(d->n_rows >= 0 && d->max_len >= 0, SUBGACC_ERR_BADARG, "%s: bad arguments", name);
+    return SUBGACC_OK;
+}
+
+static int counts_attn_launch(const char *name, const subgacc_join_desc *d, const CountsAttnArgs &c, bool bwd, void *stream) {
+    SG_REQUIRE(d->flags && d->ids && d->payload, SUBGACC_ERR_BADARG, "%s: null argument (flags / ids / payload)", name);
+    JoinArgs a;
+    a.indptr = d->row_off, a.indices = d->ids, a.data = d->payload;
+    a.row_len = nullptr, a.row_stride = 0, a.row_head = nullptr;
+    a.pb = d->pair_block, a.own = d->own, a.partner = d->partner, a.seg = nullptr, a.S = d->S, a.n_rows = d->n_rows;
+    a.table = nullptr, a.table_rows = d->table_rows, a.k = 0;
+    a.out_xz = nullptr, a.out_idx = nullptr, a.out_segid = nullptr;
+    a.max_len = d->max_len > 0 ? d->max_len : 1;
+    a.flags = d->flags;
+    a.slot_id = nullptr, a.val_add = 0;
+    a.key_M = a.key_m = a.key_shift = 0;
+    const int64_t dcap = 2 * (int64_t)a.max_len < a.table_rows ? 2 * (int64_t)a.max_len : a.table_rows;   // distinct rows of a block
+    const size_t lds = counts_attn_lds(a.max_len, a.table_rows, dcap, bwd);
+    SG_REQUIRE(lds <= (size_t)kLdsBytes, SUBGACC_ERR_LDS,
+               "%s: %lld distinct LP rows and rows of %d members need %zu B of LDS; use attn_stage (the pair form)", name,
+               (long long)a.table_rows, (int)a.max_len, lds);
+    const void *fn = bwd ? (const void *)sjoin_counts_attn_kernel<true> : (const void *)sjoin_counts_attn_kernel<false>;
+    if (lds > 64 * 1024) SG_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const int64_t grid = xcd_grid(d->S / 2);
+    SG_REQUIRE(grid < (1ll << 31), SUBGACC_ERR_BADARG, "%s: too many segments in one call", name);
+    if (bwd)
+        hipLaunchKernelGGL(sjoin_counts_attn_kernel<true>, dim3((unsigned)grid), dim3(kPairThreads), lds, (hipStream_t)stream, a,
+                           d->pair_block, (int32_t)dcap, c);
+    else
+        hipLaunchKernelGGL(sjoin_counts_attn_kernel<false>, dim3((unsigned)grid), dim3(kPairThreads), lds, (hipStream_t)stream, a,
+                           d->pair_block, (int32_t)dcap, c);
+    SG_LAUNCH_CHECK();
+    return SUBGACC_OK;
+}
+
+extern "C" int subgacc_sjoin_counts_attn(const subgacc_join_desc *d, const float *g, float *out_w, float *out_max, float *out_den,
+                                         void *stream) {
+    const char *name = "sjoin_counts_attn";
+    if (int rc = counts_attn_check(name, d)) return rc;
+    SG_REQUIRE(g && out_w, SUBGACC_ERR_BADARG, "sjoin_counts_attn: g and out_w are required (a NULL one given)");
+    SG_REQUIRE((out_max == nullptr) == (out_den == nullptr), SUBGACC_ERR_BADARG,
+               "sjoin_counts_attn: out_max and out_den go together (one is NULL)");
+    if (d->S == 0) return SUBGACC_OK;
+    CountsAttnArgs c{g, out_w, out_max, out_den, nullptr, nullptr, nullptr, nullptr, nullptr};
+    return counts_attn_launch(name, d, c, false, stream);
+}
+
+extern "C" int subgacc_sjoin_counts_attn_backward(const subgacc_join_desc *d, const float *g, const float *dw, const float *w,
+                                                  const float *max, const float *den, float *out_dg, void *stream) {
+    const char *name = "sjoin_counts_attn_backward";
+    if (int rc = counts_attn_check(name, d)) return rc;
+    SG_REQUIRE(g && dw && w && max && den && out_dg, SUBGACC_ERR_BADARG,
+               "sjoin_counts_attn_backward: g, dw, w, max, den and out_dg are required (a NULL one given)");
+    if (d->S == 0) return SUBGACC_OK;
+    CountsAttnArgs c{g, nullptr, nullptr, nullptr, dw, w, max, den, out_dg};
+    return counts_attn_launch(name, d, c, true, stream);
 }

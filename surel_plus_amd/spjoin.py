@@ -1087,14 +1087,15 @@ def float_mean_stage(edge, x, embed):
     return out
 
 
-def _one_linear(mod, what, d_in, d_out=None):
-    """the nn.Linear of `mod` = Linear(d_in, d_out) or Sequential(Linear(d_in, d_out)) (d_out None: any), or TypeError"""
+def _one_linear(mod, what, d_in, d_out=None, stage="float_attn_stage", other="xz, ind = gather(edge, x) and the modules on xz"):
+    """the nn.Linear of `mod` = Linear(d_in, d_out) or Sequential(Linear(d_in, d_out)) (d_out None: any; d_in None: any), or TypeError
+    naming `stage` and, for any other module, `other`"""
     nn = torch.nn
     lin = mod[0] if isinstance(mod, nn.Sequential) and len(mod) == 1 else mod
-    if not (isinstance(lin, nn.Linear) and lin.in_features == d_in and (d_out is None or lin.out_features == d_out)):
-        shape = f"({d_in}, {d_out if d_out is not None else 'H2'})"
-        raise TypeError(f"float_attn_stage fuses {what} = Linear{shape} (or a Sequential of that one Linear; PyG's MLP([...]) as its "
-                        f".lins[0]) only; for any other module use xz, ind = gather(edge, x) and the modules on xz")
+    if not (isinstance(lin, nn.Linear) and (d_in is None or lin.in_features == d_in) and (d_out is None or lin.out_features == d_out)):
+        shape = f"({d_in if d_in is not None else 'H'}, {d_out if d_out is not None else 'H2'})"
+        raise TypeError(f"{stage} fuses {what} = Linear{shape} (or a Sequential of that one Linear; PyG's MLP([...]) as its "
+                        f".lins[0]) only; for any other module use {other}")
     return lin
 
 
@@ -1187,4 +1188,138 @@ def float_attn_stage(edge, x, embed, gate_nn, value_nn=None):
         h = torch.nn.functional.linear(h, val.weight, val.bias)
     out = (h * st.nonempty().to(h.dtype)[:, None]).view(2, B, h.shape[-1])
     out.join_flags = st.flags
+    return out
+
+
+class _CountsAttn(torch.autograd.Function):
+    """W [S, T] of subgacc_sjoin_counts_attn as a function of g = embed(encode) wg -- and of the gate bias, whose gradient is exactly
+    zero (softmax drops a constant); backward: subgacc_sjoin_counts_attn_backward's per-segment rows Dg, summed over the segments"""
+
+    @staticmethod
+    def forward(ctx, g, bg, join):
+        ctx.join = join
+        ctx.has_bg = bg is not None
+        g = g.detach().contiguous()
+        W, mx, den = join.forward(g, True)
+        ctx.save_for_backward(g, W, mx, den)
+        return W
+
+    @staticmethod
+    def backward(ctx, dW):
+        g, W, mx, den = ctx.saved_tensors
+        Dg = ctx.join.backward(g, dW.contiguous(), W, mx, den)
+        bg = torch.zeros((1,), dtype=dW.dtype, device=dW.device) if ctx.has_bg else None
+        return Dg.sum(0), bg, None
+
+
+class _CountsAttnJoin:
+    """the two library calls of counts_attn_stage: the mirrored count-form descriptor over a packed SFptr store, its status words"""
+
+    def __init__(self, x, rows, own, B, T):
+        self.x, self.rows, self.own, self.B, self.T = x, rows, own, B, T
+        self.dev = x.device
+        self.flags = torch.zeros(4, dtype=torch.int32, device=self.dev)
+
+    def desc(self):
+        return _lib.join_desc(JOIN_COUNTS, JOIN_SFPTR, **self.rows, own=self.own, S=2 * self.B, pair_block=self.B, table_rows=self.T,
+                              flags=self.flags)
+
+    def checked(self):
+        status = int(self.flags[3].item())
+        if status & 16:
+            raise IndexError(f"row index out of range for an SpG with {self.x.n_rows} rows")
+        if status & 2:
+            raise IndexError(f"index {self.x.max_data} is out of bounds for the encode table with {self.T} rows")
+        if status & 1:
+            raise _lib.SubgAccError("SpG row longer than SpG.max_len")
+
+    def forward(self, g, keep):
+        S, dev = 2 * self.B, self.dev
+        W = torch.empty((S, self.T), dtype=torch.float32, device=dev)
+        mx, den = (torch.empty(S, dtype=torch.float32, device=dev), torch.empty(S, dtype=torch.float32, device=dev)) if keep \
+            else (None, None)
+        if self.B == 0:     # (an empty list has no pair_block the library would accept)
+            return W, mx, den
+        with _timed("sjoin_counts_attn"):
+            d = self.desc()
+            check(lib().subgacc_sjoin_counts_attn(ctypes.byref(d), ptr(g), ptr(W), ptr(mx), ptr(den), stream_ptr()))
+        self.checked()
+        return W, mx, den
+
+    def backward(self, g, dW, W, mx, den):
+        Dg = torch.zeros_like(W)
+        if self.B == 0:
+            return Dg
+        with _timed("sjoin_counts_attn_backward"):
+            d = self.desc()
+            check(lib().subgacc_sjoin_counts_attn_backward(ctypes.byref(d), ptr(g), ptr(dW), ptr(W), ptr(mx), ptr(den), ptr(Dg),
+                                                           stream_ptr()))
+        return Dg
+
+
+def counts_attn_stage(edge, x, encode, embed, gate_nn, value_nn=None):
+    """The reference's first model stage of the LP encoder for --aggr attn, fused with the count form of the join:  model.py:59-62,78-81
+        x = pe_embedding(xz).sum(dim=-2);  xl, xr = AttentionalAggregation(gate_nn, nn)(x, ptr=ptr).view(2, -1, H'')
+    Row t of segment j is E[p_t] + E[q_t] with E = embed(encode) [T, H] (T = c+1 LP rows, row 0 = partner absent) and (p_t, q_t) its
+    index pair, so with one-Linear gate_nn (wg, bg) and nn the gate is g[p_t] + g[q_t] plus a constant the softmax drops (g = (E - mean
+    of E's rows) wg),
+    and, the weights summing to 1,
+        out_j = nn(W[j] @ E) [n_j > 0],   W[j, r] = sum_t softmax_j(l)_t ([p_t = r] + [q_t = r])
+    The library's kernels (subgacc_sjoin_counts_attn / _backward) join the pairs and write the softmax-weighted count rows W [2B, T] --
+    neither xz, nor the [R,2,H] activations, nor the pair rows of attn_stage exist -- and the per-segment rows of dL/dg; the GEMM, nn
+    and the gradients into embed and gate_nn are ordinary torch ops.  Every parameter receives a gradient; the gate bias's is exactly
+    zero, as the reference's is analytically.  Results do not depend on the order of the pairs or on run-to-run timing.
+    embed: any row-wise module (the reference's pe_embedding MLP), applied to the [T, k] table as in mean_stage; gate_nn: nn.Linear(H, 1)
+    or a one-Linear Sequential; value_nn: None or nn.Linear(H, H'') (PyG 2.2's MLP([H, 1]) / MLP([H, H]) is that Linear, .lins[0]).
+    edge: [2, B] integer (torch or NumPy); x: a packed SFptr SpG.  Returns float32 [2, B, H''] (H without value_nn), empty segments
+    giving zero rows, with the join's status words as .join_flags.  W, dW and Dg are 4 T bytes per segment each: a store with many LP
+    rows, or any other gate / value module, takes attn_stage."""
+    name = "counts_attn_stage"
+    if isinstance(x, StridedSpG):
+        raise TypeError(f"{name} needs a packed SFptr (integer) SpG, not a StridedSpG (join its to_csr())")
+    if isinstance(x, HeadedSpG):
+        raise ValueError(f"{name} joins the packed store: keep it, or join z.to_spg() (the headed layout is for gather / hgather)")
+    if not isinstance(x, SpG):
+        raise TypeError(f"{name} joins a packed SFptr (integer) SpG, not {type(x).__name__}")
+    if x.keyrows or x.data.dtype != torch.int32:
+        raise TypeError(f"{name} needs a packed SFptr (integer) SpG (not a keyed() one); a float (PPR / SPD / DEG) store has "
+                        "float_attn_stage(edge, x, embed, gate_nn, value_nn)")
+    other = "attn_stage(edge, x, encode, embed, gate_nn, value_nn)"
+    gate = _one_linear(gate_nn, "gate_nn", None, 1, name, other)
+    H = gate.in_features
+    val = _one_linear(value_nn, "value_nn", H, None, name, other) if value_nn is not None else None
+    dev = x.device
+    for mod in (gate, val, embed):
+        for prm in (mod.parameters() if mod is not None else ()):
+            if prm.device != dev or prm.dtype != torch.float32:
+                raise ValueError(f"{name}: embed, gate_nn and value_nn must hold float32 parameters on the store's device ({dev})")
+    table = encode if torch.is_tensor(encode) else torch.as_tensor(np.asarray(encode))
+    if table.ndim != 2 or table.shape[0] < 1 or table.dtype.is_complex or table.dtype == torch.bool:
+        raise ValueError(f"{name}: encode must be the [T, k] real LP table, got {table.dtype} of shape {tuple(table.shape)}")
+    if table.is_cuda and table.device != dev:
+        raise ValueError(f"{name}: encode lies on {table.device}, the store on {dev}")
+    e = _edge_rows(edge, name)
+    if e.shape[1] and (int(e.min()) < 0 or int(e.max()) >= x.n_rows):
+        raise IndexError(f"row index out of range for an SpG with {x.n_rows} rows")
+    T = int(table.shape[0])
+    e = _as_rows(e, dev)
+    B = int(e.shape[1])
+    join = _CountsAttnJoin(x, x.join_rows()[1], e.contiguous().view(-1), B, T)
+    E = embed(table.to(device=dev, dtype=torch.float32))
+    if E.ndim != 2 or E.shape[0] != T or E.shape[1] != H:
+        raise ValueError(f"{name}: embed(encode) is {tuple(E.shape)}, gate_nn takes rows of {H}")
+    # the gate's logit of every LP row, its bias left out and E centred first: softmax drops the constant 2 mean(E) . wg, and with it the
+    # cancellation of E's common offset in dL/dwg = (E - mean)^T dg (the centre is a constant of autograd: sum_r dg[r] = 0)
+    g = (E - E.detach().mean(0)) @ gate.weight.view(-1)
+    if torch.is_grad_enabled() and (g.requires_grad or (gate.bias is not None and gate.bias.requires_grad)):
+        W = _CountsAttn.apply(g, gate.bias, join)
+    else:
+        W = join.forward(g.detach().contiguous(), False)[0]
+    h = W @ E
+    if val is not None:
+        h = torch.nn.functional.linear(h, val.weight, val.bias)
+    own = join.own
+    nonempty = (x.indptr[own + 1] - x.indptr[own]) > 0
+    out = (h * nonempty.to(h.dtype)[:, None]).view(2, B, h.shape[-1])
+    out.join_flags = join.flags
     return out
