@@ -434,7 +434,8 @@ int subgacc_sjoin_relu_attn_backward(const subgacc_join_desc *d, const float *w1
  * Refused with SUBGACC_ERR_BADARG before anything is launched: form != COUNTS or any option bit, a payload other than SFPTR, strided or
  * headed rows, pair_block <= 0 or S not a multiple of 2*pair_block, own = NULL with S > 0, table_rows outside [1, 2^31), any out_* or
  * seg field of the descriptor set, g / out_w NULL, exactly one of out_max / out_den.  LDS: 4 (7 max_len + 2 T + 2 D + 8) bytes,
- * D = min(2 max_len, T) (the backward: 6 D) <= 160 KiB, else SUBGACC_ERR_LDS (the pair form, attn_stage, has no such bound). */
+ * D = min(2 max_len, T) (the backward: 6 D) <= 160 KiB, else SUBGACC_ERR_LDS (the pair form, attn_stage, has no such bound); with
+ * out_max / out_den given a backward follows, so the backward's LDS must fit too, else SUBGACC_ERR_LDS before anything is launched. */
 int subgacc_sjoin_counts_attn(const subgacc_join_desc *d, const float *g, float *out_w, float *out_max, float *out_den, void *stream);
 
 /* The backward of subgacc_sjoin_counts_attn over the same descriptor: dw = dL/dW, w = W, max / den = m, den as the forward wrote them.

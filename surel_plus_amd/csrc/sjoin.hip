@@ -2710,6 +2710,11 @@ static int counts_attn_launch(const char *name, const subgacc_join_desc *d, cons
     SG_REQUIRE(lds <= (size_t)kLdsBytes, SUBGACC_ERR_LDS,
                "%s: %lld distinct LP rows and rows of %d members need %zu B of LDS; use attn_stage (the pair form)", name,
                (long long)a.table_rows, (int)a.max_len, lds);
+    // a forward that keeps m / den is followed by the backward, which needs more LDS: refused here, not in the middle of a training step
+    const size_t lds_bwd = counts_attn_lds(a.max_len, a.table_rows, dcap, true);
+    SG_REQUIRE(bwd || !c.out_max || lds_bwd <= (size_t)kLdsBytes, SUBGACC_ERR_LDS,
+               "%s: %lld distinct LP rows and rows of %d members: the backward needs %zu B of LDS; use attn_stage (the pair form)", name,
+               (long long)a.table_rows, (int)a.max_len, lds_bwd);
     const void *fn = bwd ? (const void *)sjoin_counts_attn_kernel<true> : (const void *)sjoin_counts_attn_kernel<false>;
     if (lds > 64 * 1024) SG_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const int64_t grid = xcd_grid(d->S / 2);

@@ -109,3 +109,31 @@ def _reference_style_lstm(xz, ptr, embed, lstm):
     for j in range(S):
         dense[j, : int(lens[j])] = x[int(ptr[j]): int(ptr[j + 1])]
     return lstm(dense)[0][:, -1]
+
+
+# ------------------------------------------- the float encoders' fused first stages (float_mean_stage / float_attn_stage)
+def _reference_mean_from_xz(xz, ind, mlp):
+    """model.py:78-83 as the reference runs it: x = pe_embedding(xz).sum(-2), then MeanAggregation(x, ptr) ([2, B, H'])"""
+    x = mlp(xz.to(mlp[0].weight.dtype)).sum(dim=-2)
+    n = ind[1:] - ind[:-1]
+    S = n.numel()
+    seg = torch.repeat_interleave(torch.arange(S, device=xz.device), n)
+    out = torch.zeros(S, x.shape[-1], device=xz.device, dtype=x.dtype).index_add_(0, seg, x) / n.clamp(min=1)[:, None]
+    return out.view(2, -1, x.shape[-1])
+
+
+def _reference_attn_from_xz(xz, ind, nets):
+    """model.py:78-81 as the reference runs it, AttentionalAggregation written out as _reference_style_attn does (PyG's softmax:
+    exp(g - max) / (sum + 1e-16)), with a value net of any width; nets = (embed, gate_nn, value_nn or None)"""
+    embed, gate, val = nets
+    x = embed(xz.to(embed[0].weight.dtype)).sum(dim=-2)
+    S = ind.numel() - 1
+    seg = torch.repeat_interleave(torch.arange(S, device=xz.device), ind[1:] - ind[:-1])
+    g = gate(x).reshape(-1)
+    gmax = torch.full((S,), float("-inf"), device=g.device, dtype=g.dtype).scatter_reduce(0, seg, g.detach(), "amax")
+    w = torch.exp(g - gmax[seg])
+    den = torch.zeros(S, device=g.device, dtype=g.dtype).index_add_(0, seg, w)
+    alpha = w / (den[seg] + 1e-16)
+    v = val(x) if val is not None else x
+    out = torch.zeros((S, v.shape[-1]), device=g.device, dtype=g.dtype).index_add_(0, seg, alpha[:, None] * v)
+    return out.view(2, -1, out.shape[-1])

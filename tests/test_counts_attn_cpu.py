@@ -122,6 +122,18 @@ def test_counts_attn_refuses_what_lds_does_not_hold(L, name, change):
 
 
 @pytest.mark.parametrize("name", NAMES)
+def test_counts_attn_refuses_a_forward_whose_backward_lds_does_not_fit(L, name):
+    """max_len 1,500 and 10,000 LP rows: the forward needs 4 (7 L + 2 T + 2 D + 8) = 146,032 B, the backward 4 (7 L + 2 T + 6 D + 8) =
+    194,032 B of the 160 KiB.  A forward that keeps m / den is followed by the backward, so both refuse with SUBGACC_ERR_LDS before any
+    launch -- not the backward alone, in the middle of a training step.  (The forward without out_max / out_den fits and would launch:
+    the GPU suite runs it, test_gpu_stage_shapes.py.)"""
+    from surel_plus_amd import _lib
+    rc, msg = _call(L, name, dict(max_len=1500, table_rows=10000))
+    assert rc == _lib.ERR_LDS
+    assert b"LDS" in msg and b"attn_stage" in msg and b"194032" in msg, msg
+
+
+@pytest.mark.parametrize("name", NAMES)
 def test_counts_attn_refuses_a_foreign_descriptor(L, name):
     from surel_plus_amd import _lib
     buf = (C.c_int64 * 64)()

@@ -8,6 +8,7 @@ import torch
 
 import surel_plus_amd as spm
 from gpu_helpers import _load, _spg_from_golden, sp, sym_graph  # noqa: F401
+from gpu_helpers import _reference_attn_from_xz as _reference_from_xz
 
 pytestmark = pytest.mark.gpu
 
@@ -29,23 +30,6 @@ def _nets(H, H2=16, H3=None, dtype=torch.float32, seed=1, bias=True):
 
 def _params(nets):
     return [p for m in nets if m is not None for p in m.parameters()]
-
-
-def _reference_from_xz(xz, ind, nets):
-    """model.py:78-81 as the reference runs it, AttentionalAggregation written out as gpu_helpers._reference_style_attn does (PyG's
-    softmax: exp(g - max) / (sum + 1e-16)), with a value net of any width"""
-    embed, gate, val = nets
-    x = embed(xz.to(embed[0].weight.dtype)).sum(dim=-2)
-    S = ind.numel() - 1
-    seg = torch.repeat_interleave(torch.arange(S, device=xz.device), ind[1:] - ind[:-1])
-    g = gate(x).reshape(-1)
-    gmax = torch.full((S,), float("-inf"), device=g.device, dtype=g.dtype).scatter_reduce(0, seg, g.detach(), "amax")
-    w = torch.exp(g - gmax[seg])
-    den = torch.zeros(S, device=g.device, dtype=g.dtype).index_add_(0, seg, w)
-    alpha = w / (den[seg] + 1e-16)
-    v = val(x) if val is not None else x
-    out = torch.zeros((S, v.shape[-1]), device=g.device, dtype=g.dtype).index_add_(0, seg, alpha[:, None] * v)
-    return out.view(2, -1, out.shape[-1])
 
 
 def _reference(edge, x, nets):

@@ -7,6 +7,7 @@ import torch
 
 import surel_plus_amd as spm
 from gpu_helpers import _load, _spg_from_golden, sp, sym_graph  # noqa: F401
+from gpu_helpers import _reference_mean_from_xz as _reference_from_xz
 
 pytestmark = pytest.mark.gpu
 
@@ -27,16 +28,6 @@ def _twin(mlp, dtype=torch.float64):
     other = _mlp(mlp[0].out_features, mlp[2].out_features, bias=mlp[0].bias is not None)
     other.load_state_dict(mlp.state_dict())
     return other.to(dtype)
-
-
-def _reference_from_xz(xz, ind, mlp):
-    """model.py:78-83 as the reference runs it: x = pe_embedding(xz).sum(-2), then MeanAggregation(x, ptr) ([2, B, H'])"""
-    x = mlp(xz.to(mlp[0].weight.dtype)).sum(dim=-2)
-    n = ind[1:] - ind[:-1]
-    S = n.numel()
-    seg = torch.repeat_interleave(torch.arange(S, device=xz.device), n)
-    out = torch.zeros(S, x.shape[-1], device=xz.device, dtype=x.dtype).index_add_(0, seg, x) / n.clamp(min=1)[:, None]
-    return out.view(2, -1, x.shape[-1])
 
 
 def _reference(edge, x, mlp):
