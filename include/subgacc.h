@@ -448,6 +448,46 @@ int subgacc_sjoin_counts_attn(const subgacc_join_desc *d, const float *g, float 
 int subgacc_sjoin_counts_attn_backward(const subgacc_join_desc *d, const float *g, const float *dw, const float *w, const float *max,
                                        const float *den, float *out_dg, void *stream);
 
+/* The LP encoder's first stage with LSTM aggregation (--aggr lstm: model.py:63-65,78-83, PyG's LSTMAggregation: to_dense_batch, a
+ * one-layer batch_first nn.LSTM, the output at the last position), folded over the index form of the join (ABI 7, backward compatible
+ * additions).  Segment j is the rows [indptr[j], indptr[j+1]) of pairs (p_t, q_t) -- SFptr+1 of the member in its own row, in the
+ * partner row or 0 -- and row t's input is E[p_t] + E[q_t] with E = pe_embedding(Z_SF) [T, H].  The input projection folds into the
+ * table G = E W_ih^T (f32 [T, 4H'], gate order i, f, g, o as nn.LSTM's) and b = b_ih + b_hh (f32 [4H'], NULL = zero).  Every segment
+ * runs exactly L steps from h = c = 0, as the reference's zero padding makes it: step t < n_j takes G[p_t] + G[q_t], steps
+ * n_j <= t < L take zero input (an empty segment runs L padded steps).  out_h (f32 [S, H']) receives h_{L-1}.  Per step and element:
+ *     a = ((G[p_t] + G[q_t]) + b) as the accumulator's initial value (0 + b on a padded step), then + W_hh[row] . h_{t-1} as an fmaf
+ *         chain over k ascending (v_mfma_f32_16x16x4_f32, bit for bit such a chain);
+ *     i = 1 / (1 + expf(-a_i)), f, o likewise, g = tanhf(a_g) (accurate expf / tanhf, never the fast intrinsics);
+ *     c_t = (f c_{t-1}) + (i g),  h_t = o tanhf(c_t)   (each product rounded, no fma).
+ * A segment's bits depend only on its own rows and on L: not on the segments that share its tile, the pair order or the store layout.
+ * h_state / c_state (both or neither; f32 [S, L, H']) receive every h_t, c_t for the backward ([j][t][k]; 8 S L H' bytes).
+ * A pair index outside [0, T) reads row 0 and sets flags[3] |= 2 (flags int32[4], caller zeroes); nothing is read out of bounds.
+ * Refused with SUBGACC_ERR_BADARG before anything is launched: pairs / indptr / G / w_hh / out_h / flags NULL, S < 0, L < 1 with S > 0,
+ * H' not a multiple of 16 or outside [16, 128], T < 1, exactly one of h_state / c_state. */
+int subgacc_lstm_aggr(const int32_t *pairs, const int64_t *indptr, int64_t S, int32_t L, int64_t T, int32_t H, const float *G,
+                      const float *b, const float *w_hh, float *out_h, float *h_state, float *c_state, int32_t *flags, void *stream);
+
+/* The backward of subgacc_lstm_aggr (BPTT, t = L-1 .. 0): dh = dL/dh_{L-1} (f32 [S, H']), h_state / c_state as the forward wrote them.
+ * The gates are recomputed bit for bit (the forward's order); dh_{t-1} = W_hh^T dgates_t is an fmaf chain over the 4H' gate rows
+ * ascending.  No float is added atomically:
+ *   out_dw (f32 [ceil(S/16), 4H', H']) / out_db (f32 [ceil(S/16), 4H']): one partial per tile of 16 segments (dL/dW_hh, dL/db = their
+ *            sums over tiles); inside a tile dW_hh[n][k] is an fmaf chain over t descending and, per step, the tile's segments in the
+ *            order 4i + s (MFMA i = 0..3, s = 0..3); db per lane quad over t descending of (((d_0 + d_1) + d_2) + d_3), the 4 quads added
+ *            in order.  Padded steps contribute here only.
+ *   ws_rows (f32 [R, 4H'], R = indptr[S]): dgates of every real row, in row order.
+ *   out_dg (f32 [T, 4H']): dL/dG[r] = the sum of ws_rows over the 2R index entries (row, side) with index r, in the order `order`
+ *            lists them: order (int32 [2R]) holds the row of every entry of a stable sort of the 2R indices; piece_off (int64
+ *            [n_pieces + 1]) cuts it into pieces inside one index's run; run_piece (int64 [T + 1]): the pieces of index r are
+ *            [run_piece[r], run_piece[r+1]).  Each piece is summed from 0 in order into ws_pieces (f32 [n_pieces, 4H']), then each
+ *            index's pieces are summed from 0 in order.
+ * Flags and refusals as the forward's; h_state, c_state, dh, order, piece_off, run_piece, ws_rows, out_dg, out_dw and out_db are
+ * required, ws_pieces when n_pieces > 0; n_pieces outside [0, 2^31) is refused. */
+int subgacc_lstm_aggr_backward(const int32_t *pairs, const int64_t *indptr, int64_t S, int32_t L, int64_t T, int32_t H, const float *G,
+                               const float *b, const float *w_hh, const float *h_state, const float *c_state, const float *dh,
+                               const int32_t *order, const int64_t *piece_off, int64_t n_pieces, const int64_t *run_piece,
+                               float *ws_rows, float *ws_pieces, float *out_dg, float *out_dw, float *out_db, int32_t *flags,
+                               void *stream);
+
 
 /* Packed rows -> headed rows (ABI 7): the resident store of a serving loop laid out on whole lines -- the rows random_walks.py:79-81
  * builds as a SciPy CSR and train.py:17-18 / :39-43 slice one by one (x[edge[0]]), in the layout the pair kernels read with one

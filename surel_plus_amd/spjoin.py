@@ -1323,3 +1323,177 @@ def counts_attn_stage(edge, x, encode, embed, gate_nn, value_nn=None):
     out = (h * nonempty.to(h.dtype)[:, None]).view(2, B, h.shape[-1])
     out.join_flags = join.flags
     return out
+
+
+LSTM_WIDTHS = tuple(range(16, 129, 16))     # H' the recurrent kernel takes (include/subgacc.h: subgacc_lstm_aggr)
+_LSTM_PIECE = 1024                           # entries of one piece of dG's ordered sum (a table row's run is cut into such pieces)
+
+
+def _lstm_layer(lstm, dev, name="index_lstm_stage"):
+    """(W_ih, W_hh, b_ih, b_hh) of a one-layer, unidirectional, batch_first, proj_size = 0, float32 nn.LSTM on `dev`, or TypeError /
+    ValueError naming lstm_stage as the general path"""
+    other = "lstm_stage(edge, x, encode, embed, lstm)"
+    if not isinstance(lstm, torch.nn.LSTM):
+        raise TypeError(f"{name} fuses a torch.nn.LSTM only, not {type(lstm).__name__}; for any other module use {other}")
+    if lstm.num_layers != 1 or lstm.bidirectional or not lstm.batch_first or getattr(lstm, "proj_size", 0) != 0:
+        raise ValueError(f"{name} fuses a one-layer, unidirectional, batch_first nn.LSTM without projection (num_layers "
+                         f"{lstm.num_layers}, bidirectional {lstm.bidirectional}, batch_first {lstm.batch_first}, proj_size "
+                         f"{getattr(lstm, 'proj_size', 0)}); for any other use {other}")
+    H2 = lstm.hidden_size
+    if H2 not in LSTM_WIDTHS:
+        raise ValueError(f"{name}: hidden_size {H2} is not a multiple of 16 in [16, 128]; for any other width use {other}")
+    for p in lstm.parameters():
+        if p.device != dev or p.dtype != torch.float32:
+            raise ValueError(f"{name}: the LSTM must hold float32 parameters on the store's device ({dev}); otherwise use {other}")
+    return lstm.weight_ih_l0, lstm.weight_hh_l0, getattr(lstm, "bias_ih_l0", None), getattr(lstm, "bias_hh_l0", None)
+
+
+def _nonnull(t):
+    """t, or one element of its dtype when t is empty (the library takes no NULL for an array it is told holds nothing)"""
+    return t if t.numel() else torch.zeros(1, dtype=t.dtype, device=t.device)
+
+
+class _LstmJoin:
+    """the two library calls of index_lstm_stage over one batch's index form (pairs, indptr) padded to L steps"""
+
+    def __init__(self, pairs, indptr, L, T, H2):
+        self.pairs, self.indptr, self.L, self.T, self.H2 = pairs, indptr, L, T, H2
+        self.S = indptr.numel() - 1
+        self.dev = pairs.device
+        self.flags = torch.zeros(4, dtype=torch.int32, device=self.dev)
+
+    def checked(self):
+        if int(self.flags[3].item()) & 2:
+            raise IndexError(f"an index of the join is out of bounds for the encode table with {self.T} rows")
+
+    def forward(self, G, b, w_hh, keep):
+        S, L, H2, dev = self.S, self.L, self.H2, self.dev
+        h = torch.empty((S, H2), dtype=torch.float32, device=dev)
+        hs, cs = (torch.empty((S, L, H2), dtype=torch.float32, device=dev), torch.empty((S, L, H2), dtype=torch.float32, device=dev)) \
+            if keep else (None, None)
+        with _timed("lstm_aggr"):
+            check(lib().subgacc_lstm_aggr(ptr(_nonnull(self.pairs)), ptr(self.indptr), S, L, self.T, H2, ptr(G), ptr(b), ptr(w_hh), ptr(h), ptr(hs),
+                                          ptr(cs), ptr(self.flags), stream_ptr()))
+        return h, hs, cs
+
+    def grouping(self):
+        """dG's ordered sum: the row of every index entry in a stable sort of the 2R indices, cut into pieces of at most _LSTM_PIECE
+        entries inside one index's run, and the pieces of every index"""
+        idx = self.pairs.view(-1).long()
+        srt, perm = torch.sort(idx, stable=True)
+        order = (perm // 2).to(torch.int32)
+        cnt = torch.bincount(idx, minlength=self.T)
+        start = torch.zeros(self.T + 1, dtype=torch.int64, device=self.dev)
+        torch.cumsum(cnt, 0, out=start[1:])
+        npc = (cnt + _LSTM_PIECE - 1) // _LSTM_PIECE
+        run_piece = torch.zeros(self.T + 1, dtype=torch.int64, device=self.dev)
+        torch.cumsum(npc, 0, out=run_piece[1:])
+        P = int(run_piece[-1].item())
+        owner = torch.repeat_interleave(torch.arange(self.T, device=self.dev), npc, output_size=P)
+        k = torch.arange(P, device=self.dev) - run_piece[:-1][owner]
+        piece_off = torch.empty(P + 1, dtype=torch.int64, device=self.dev)
+        piece_off[:-1] = start[:-1][owner] + k * _LSTM_PIECE
+        piece_off[-1] = idx.numel()
+        return order, piece_off.contiguous(), P, run_piece
+
+    def backward(self, G, b, w_hh, hs, cs, dh):
+        S, H2, dev = self.S, self.H2, self.dev
+        tiles = (S + 15) // 16
+        R = self.pairs.shape[0]
+        order, piece_off, P, run_piece = self.grouping()
+        rows = torch.empty((R, 4 * H2), dtype=torch.float32, device=dev)
+        pieces = torch.empty((P, 4 * H2), dtype=torch.float32, device=dev) if P else None
+        dG = torch.empty((self.T, 4 * H2), dtype=torch.float32, device=dev)
+        dw = torch.empty((tiles, 4 * H2, H2), dtype=torch.float32, device=dev)
+        db = torch.empty((tiles, 4 * H2), dtype=torch.float32, device=dev)
+        with _timed("lstm_aggr_backward"):
+            check(lib().subgacc_lstm_aggr_backward(ptr(_nonnull(self.pairs)), ptr(self.indptr), S, self.L, self.T, H2, ptr(G), ptr(b),
+                                                   ptr(w_hh), ptr(hs), ptr(cs), ptr(dh), ptr(_nonnull(order)), ptr(piece_off), P, ptr(run_piece),
+                                                   ptr(_nonnull(rows)),
+                                                   ptr(pieces), ptr(dG), ptr(dw), ptr(db), ptr(self.flags), stream_ptr()))
+        return dG, db.sum(0), dw.sum(0)
+
+
+class _LstmAggr(torch.autograd.Function):
+    """h_{L-1} [S, H'] of subgacc_lstm_aggr as a function of (G, b, W_hh); backward: subgacc_lstm_aggr_backward's dG, and the sums over
+    tiles of its dW_hh / db partials"""
+
+    @staticmethod
+    def forward(ctx, G, b, w_hh, join):
+        ctx.join = join
+        ctx.has_b = b is not None
+        G, w_hh = G.detach().contiguous(), w_hh.detach().contiguous()
+        b = b.detach().contiguous() if b is not None else None
+        h, hs, cs = join.forward(G, b, w_hh, True)
+        ctx.save_for_backward(G, b, w_hh, hs, cs)
+        return h
+
+    @staticmethod
+    def backward(ctx, dh):
+        G, b, w_hh, hs, cs = ctx.saved_tensors
+        dG, db, dw = ctx.join.backward(G, b if ctx.has_b else None, w_hh, hs, cs, dh.contiguous())
+        return dG, (db if ctx.has_b else None), dw, None
+
+
+def index_lstm_stage(edge, x, encode, embed, lstm):
+    """The reference's first model stage of the LP encoder for --aggr lstm, folded into one recurrent kernel:  model.py:63-65,78-83
+        x = pe_embedding(xz).sum(dim=-2);  xl, xr = LSTMAggregation(H, H')(x, index=ptr).view(2, -1, H')
+    Same arguments and result as lstm_stage.  Row t of segment j is E[p_t] + E[q_t] with E = embed(encode) [T, H] and (p_t, q_t) the index
+    pair gather_index returns, so the LSTM's input projection is a lookup into G = E W_ih^T [T, 4H'] plus b = b_ih + b_hh; the library's
+    kernel (subgacc_lstm_aggr) runs the recurrence gates = G[p_t] + G[q_t] + b + W_hh h_{t-1} over every segment for the batch's L steps
+    (zero input past a segment's rows, as the reference's padding) on the MFMA -- neither xz, nor the dense [S, L, H] batch, nor the LSTM's
+    [S, L, H'] output exist.  Under autograd the forward keeps h_t, c_t ([S, L, H'] each) and the backward (subgacc_lstm_aggr_backward)
+    returns dG, db and dW_hh; torch carries dG into embed and W_ih, so every parameter receives a gradient.  A segment's result does not
+    depend on the other segments of the batch, the order of its pairs' neighbours or the store layout.
+    lstm: a one-layer, unidirectional, batch_first, proj_size = 0, float32 nn.LSTM on the store's device with hidden_size in 16, 32, ..,
+    128; x: an integer (LP) SpG or StridedSpG (packed, on-demand or key-row batches).  Returns float32 [2, B, H'] (left endpoints, right
+    endpoints) with the status words as .join_flags.  Any other LSTM, width or store takes lstm_stage."""
+    name = "index_lstm_stage"
+    if isinstance(x, HeadedSpG):
+        raise ValueError(f"{name} joins the packed store: keep it, or join z.to_spg() (the headed layout is for gather / hgather); "
+                         "lstm_stage(edge, x, encode, embed, lstm) takes the same")
+    if not isinstance(x, (SpG, StridedSpG)):
+        raise TypeError(f"{name} joins an integer (LP) SpG or StridedSpG, not {type(x).__name__}")
+    if isinstance(x, SpG) and not x.keyrows and x.data.dtype != torch.int32:
+        raise TypeError(f"{name} joins an integer (LP) store; a float (PPR / SPD / DEG) store has no fused LSTM stage: use "
+                        "lstm_stage(edge, x, encode, embed, lstm) on its gather()")
+    dev = x.device
+    w_ih, w_hh, b_ih, b_hh = _lstm_layer(lstm, dev, name)
+    H2 = lstm.hidden_size
+    table = encode if torch.is_tensor(encode) else torch.as_tensor(np.asarray(encode))
+    if table.ndim != 2 or table.shape[0] < 1 or table.dtype.is_complex or table.dtype == torch.bool:
+        raise ValueError(f"{name}: encode must be the [T, k] real LP table, got {table.dtype} of shape {tuple(table.shape)}")
+    if table.is_cuda and table.device != dev:
+        raise ValueError(f"{name}: encode lies on {table.device}, the store on {dev}")
+    e = _edge_rows(edge, name)
+    T = int(table.shape[0])
+    er = _as_rows(e, dev)
+    own = er.reshape(-1)
+    if own.numel() and bool(((own < 0) | (own >= x.n_rows)).any()):
+        raise IndexError(f"row index out of range for an SpG with {x.n_rows} rows")
+    sizes = x.nsize[own] if isinstance(x, StridedSpG) else x.indptr[own + 1] - x.indptr[own]
+    if own.numel() and int(sizes.sum().item()) == 0:     # no rows at all (the join asks for none): L = 1 padded step per segment
+        pairs, indptr = torch.zeros((0, 2), dtype=torch.int32, device=dev), torch.zeros(own.numel() + 1, dtype=torch.int64, device=dev)
+    else:
+        pairs, indptr = gather_index(er, x)
+    if pairs.numel() and int(pairs.max().item()) >= T:
+        raise IndexError(f"index {int(pairs.max().item())} is out of bounds for the encode table with {T} rows")
+    S = indptr.numel() - 1
+    L = max(int((indptr[1:] - indptr[:-1]).max().item()), 1) if S else 1
+    E = embed(table.to(device=dev, dtype=torch.float32))
+    if E.ndim != 2 or E.shape[0] != T or E.shape[1] != lstm.input_size:
+        raise ValueError(f"{name}: embed(encode) is {tuple(E.shape)}, the LSTM takes rows of {lstm.input_size}")
+    G = E @ w_ih.t()
+    b = (b_ih + b_hh) if b_ih is not None else None
+    join = _LstmJoin(pairs.contiguous(), indptr.contiguous(), L, T, H2)
+    if S == 0:
+        h = G.new_zeros((0, H2))
+    elif torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (G, b, w_hh)):
+        h = _LstmAggr.apply(G, b, w_hh, join)
+    else:
+        h = join.forward(G.detach().contiguous(), b.detach().contiguous() if b is not None else None, w_hh.detach().contiguous(), False)[0]
+    if S:
+        join.checked()
+    out = h.view(2, -1, H2)
+    out.join_flags = join.flags
+    return out
