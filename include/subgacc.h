@@ -322,8 +322,13 @@ int subgacc_sjoin_star_sizes(const int64_t *spg_indptr, int64_t n_rows, const in
  *              once per workgroup of targets; a source too long for that (packed rows: ~13k members with a table, ~8k float members)
  *              is joined by the one-segment-per-wave kernel on the same list instead, with the same result.  flags[1] |= 1 when the
  *              star kernel ran, |= 2 when a source took that fallback.
- *   struct_bytes = sizeof(subgacc_join_desc): a descriptor of another size is refused (SUBGACC_ERR_BADARG); fields a form does not
- *   read must be zero / NULL. */
+ *   struct_bytes = sizeof(subgacc_join_desc); fields a form does not read must be zero / NULL.
+ * Every entry point that takes this descriptor (subgacc_sjoin_fill_v2 and the fused stages below) refuses with SUBGACC_ERR_BADARG,
+ * before anything is launched and with a message that starts with its name less the subgacc_ prefix ("sjoin_fill_v2: ..."): a NULL
+ * descriptor; a descriptor of another size (struct_bytes); not exactly one row layout (both row_off and row_len, or neither with
+ * row_stride <= 0); row_stride outside [1, 2^31) for strided rows or [2, 2^31) for headed rows; a negative S, n_rows or max_len.  The
+ * fused stages, which join a mirrored list and write only outputs of their own, also refuse pair_block <= 0, S not a multiple of
+ * 2*pair_block, own = NULL with S > 0, and any out_* or seg field of the descriptor set. */
 enum { SUBGACC_JOIN_SFPTR = 0, SUBGACC_JOIN_F64 = 1, SUBGACC_JOIN_KEY32 = 2, SUBGACC_JOIN_KEY64 = 3 };
 enum { SUBGACC_JOIN_ROWS = 0, SUBGACC_JOIN_COUNTS = 1, SUBGACC_JOIN_PAIRS = 2 };
 enum { SUBGACC_JOIN_OPT_SIZES = 1, SUBGACC_JOIN_OPT_STAR = 2 };
@@ -373,9 +378,9 @@ int subgacc_sjoin_fill_v2(const subgacc_join_desc *d, void *stream);
  *   w1, b1   f32 [H]: Linear(1, H)'s weight and bias (a zero b1 for a Linear without bias); 1 <= H <= 1024.
  * Flags as the row form: flags[3] |= 16 a row number outside the store, |= 1 a packed row longer than max_len, |= 4 a list that is
  * not mirrored (the segments of such a pair are not written); flags[1] |= 2 when a pair had a row too long to stage (1,024 members)
- * and streamed.  Refused with SUBGACC_ERR_BADARG before anything is launched: a payload other than F64, strided rows, form != ROWS or
- * any option bit, pair_block <= 0 or S not a multiple of 2*pair_block, own = NULL with S > 0, w1 / b1 / out_mean NULL, H outside
- * [1, 1024], exactly one of out_p / out_q, any out_* or seg field of the descriptor set, headed rows the row form refuses. */
+ * and streamed.  Refused with SUBGACC_ERR_BADARG before anything is launched, besides the descriptor refusals of every fused stage
+ * (subgacc_join_desc): a payload other than F64, strided rows, form != ROWS or any option bit, w1 / b1 / out_mean NULL, H outside
+ * [1, 1024], exactly one of out_p / out_q, headed rows the row form refuses. */
 int subgacc_sjoin_relu_mean(const subgacc_join_desc *d, const float *w1, const float *b1, int32_t H, float *out_mean,
                             float *out_p, float *out_q, void *stream);
 
@@ -395,9 +400,9 @@ int subgacc_sjoin_relu_mean(const subgacc_join_desc *d, const float *w1, const f
  *   w1, b1   f32 [H]: Linear(1, H)'s weight and bias (a zero b1 for a Linear without bias); u f32 [H]; 1 <= H <= 1024.
  * Flags as subgacc_sjoin_relu_mean's: flags[3] |= 16 a row outside the store, |= 1 a packed row longer than max_len, |= 4 a list that is
  * not mirrored; flags[1] |= 2 a pair with a row longer than 1,024 members streamed (one pass for m_j, one for den_j and A_j).
- * Refused with SUBGACC_ERR_BADARG before anything is launched: a payload other than F64, strided rows, form != ROWS or any option bit,
- * pair_block <= 0 or S not a multiple of 2*pair_block, own = NULL with S > 0, w1 / b1 / u / out_a NULL, H outside [1, 1024],
- * exactly one of out_max / out_den, any out_* or seg field of the descriptor set, headed rows the row form refuses. */
+ * Refused with SUBGACC_ERR_BADARG before anything is launched, besides the descriptor refusals of every fused stage (subgacc_join_desc):
+ * a payload other than F64, strided rows, form != ROWS or any option bit, w1 / b1 / u / out_a NULL, H outside [1, 1024], exactly one
+ * of out_max / out_den, headed rows the row form refuses. */
 int subgacc_sjoin_relu_attn(const subgacc_join_desc *d, const float *w1, const float *b1, const float *u, int32_t H, float *out_a,
                             float *out_max, float *out_den, void *stream);
 
@@ -431,11 +436,11 @@ int subgacc_sjoin_relu_attn_backward(const subgacc_join_desc *d, const float *w1
  *   g        f32 [T].
  * Flags as the count form: flags[3] |= 1 a packed row longer than max_len, |= 2 an SFptr outside the table (read as row 0, never out of
  * bounds), |= 4 a list that is not mirrored (the segments of such a pair are not written), |= 16 a row number outside the store.
- * Refused with SUBGACC_ERR_BADARG before anything is launched: form != COUNTS or any option bit, a payload other than SFPTR, strided or
- * headed rows, pair_block <= 0 or S not a multiple of 2*pair_block, own = NULL with S > 0, table_rows outside [1, 2^31), any out_* or
- * seg field of the descriptor set, g / out_w NULL, exactly one of out_max / out_den.  LDS: 4 (7 max_len + 2 T + 2 D + 8) bytes,
- * D = min(2 max_len, T) (the backward: 6 D) <= 160 KiB, else SUBGACC_ERR_LDS (the pair form, attn_stage, has no such bound); with
- * out_max / out_den given a backward follows, so the backward's LDS must fit too, else SUBGACC_ERR_LDS before anything is launched. */
+ * Refused with SUBGACC_ERR_BADARG before anything is launched, besides the descriptor refusals of every fused stage (subgacc_join_desc):
+ * form != COUNTS or any option bit, a payload other than SFPTR, strided or headed rows, table_rows outside [1, 2^31), g / out_w NULL,
+ * exactly one of out_max / out_den.  LDS: 4 (7 max_len + 2 T + 2 D + 8) bytes, D = min(2 max_len, T) (the backward: 6 D) <= 160 KiB,
+ * else SUBGACC_ERR_LDS (the pair form, attn_stage, has no such bound); with out_max / out_den given a backward follows, so the
+ * backward's LDS must fit too, else SUBGACC_ERR_LDS before anything is launched. */
 int subgacc_sjoin_counts_attn(const subgacc_join_desc *d, const float *g, float *out_w, float *out_max, float *out_den, void *stream);
 
 /* The backward of subgacc_sjoin_counts_attn over the same descriptor: dw = dL/dW, w = W, max / den = m, den as the forward wrote them.

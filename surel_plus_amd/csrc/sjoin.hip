@@ -2110,6 +2110,88 @@ __global__ __launch_bounds__(kPairThreads) void sjoin_pairs_kernel(const JoinArg
 
 using namespace subgacc;
 
+// Every kernel of this file is launched here: the dynamic-LDS limit is raised only for a kernel that asks for more than the 64 KiB it
+// gets by default, and the launch is checked
+template <typename Kernel, typename... Args>
+static int launch(Kernel kernel, int64_t grid, int threads, size_t lds, hipStream_t s, const Args &...args) {
+    if (lds > 64 * 1024)
+        SG_CHECK_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(threads), lds, s, args...);
+    SG_LAUNCH_CHECK();
+    return SUBGACC_OK;
+}
+
+// xcd_grid(n) workgroups, refused (`who` leads the message) when they do not fit one launch: xcd_grid(n) < 2^31
+static int grid_of(int64_t n, const char *who, int64_t &grid) {
+    SG_REQUIRE(n <= (1ll << 31) - kXcds, SUBGACC_ERR_BADARG, "%s: too many segments in one call", who);
+    grid = xcd_grid(n);
+    return SUBGACC_OK;
+}
+
+// The store's row layout (include/subgacc.h, subgacc_join_desc), decided by decode_desc alone
+enum class RowLayout { Packed, Strided, Headed };
+
+// What every descriptor entry point checks first, `name` leading each message: the descriptor, its row layout -- row_off (packed),
+// row_len (strided) or neither with 1 < row_stride < 2^31 (headed) -- and S, n_rows, max_len >= 0.  A fused stage (fused = true) joins
+// a mirrored list (pair_block > 0, S a multiple of 2*pair_block, own for S > 0) and writes no output of the descriptor.
+static int decode_desc(const char *name, const subgacc_join_desc *d, bool fused, RowLayout &layout) {
+    SG_REQUIRE(d, SUBGACC_ERR_BADARG, "%s: null descriptor", name);
+    SG_REQUIRE(d->struct_bytes == (int32_t)sizeof(subgacc_join_desc), SUBGACC_ERR_BADARG,
+               "%s: descriptor of %d bytes, this library's is %d (set struct_bytes = sizeof(subgacc_join_desc))", name,
+               (int)d->struct_bytes, (int)sizeof(subgacc_join_desc));
+    layout = d->row_off ? RowLayout::Packed : d->row_len ? RowLayout::Strided : RowLayout::Headed;
+    SG_REQUIRE(!(d->row_off && d->row_len) && (layout != RowLayout::Headed || d->row_stride > 0), SUBGACC_ERR_BADARG,
+               "%s: exactly one of row_off (packed rows) / row_len (strided rows) / neither, with row_stride (headed rows)", name);
+    SG_REQUIRE(layout == RowLayout::Packed || (d->row_stride > (layout == RowLayout::Headed ? 1 : 0) && d->row_stride < (1ll << 31)),
+               SUBGACC_ERR_BADARG, "%s: row_stride = %lld", name, (long long)d->row_stride);
+    SG_REQUIRE(d->S >= 0 && d->n_rows >= 0 && d->max_len >= 0, SUBGACC_ERR_BADARG,
+               "%s: bad arguments (S = %lld, n_rows = %lld, max_len = %d: none may be negative)", name, (long long)d->S,
+               (long long)d->n_rows, (int)d->max_len);
+    if (!fused) return SUBGACC_OK;
+    const int64_t S = d->S, pb = d->pair_block;
+    SG_REQUIRE(pb > 0, SUBGACC_ERR_BADARG, "%s: needs a mirrored list, pair_block > 0 (pair_block = %lld)", name, (long long)pb);
+    SG_REQUIRE(S % (2 * pb) == 0, SUBGACC_ERR_BADARG, "%s: S = %lld is not a multiple of 2*pair_block = %lld", name, (long long)S,
+               (long long)(2 * pb));
+    SG_REQUIRE(d->own || S == 0, SUBGACC_ERR_BADARG, "%s: own = NULL with S = %lld segments", name, (long long)S);
+    SG_REQUIRE(!d->out_xz && !d->out_idx && !d->out_segid && !d->out_counts && !d->out_pairs && !d->out_mult && !d->out_cnt &&
+                   !d->out_seg && !d->seg,
+               SUBGACC_ERR_BADARG, "%s: writes its own outputs only: the descriptor's out_* and seg fields must be NULL", name);
+    return SUBGACC_OK;
+}
+
+// The kernels' arguments from a decoded descriptor: the store (the row pointers of its layout, the longest row; for strided / headed
+// float rows, the members asked for before a row's length is known), the segment list and flags.  Every other field is neutral -- no
+// segment pointers, feature table, output or keys: each launcher sets what its form reads.
+static JoinArgs join_args(const subgacc_join_desc *d, RowLayout layout) {
+    const bool packed = layout == RowLayout::Packed, headed = layout == RowLayout::Headed;
+    JoinArgs a;
+    a.indptr = packed ? d->row_off : nullptr, a.indices = headed ? d->ids + 1 : d->ids, a.data = d->payload;
+    a.row_len = layout == RowLayout::Strided ? d->row_len : nullptr, a.row_stride = packed ? 0 : d->row_stride;
+    a.row_head = headed ? d->ids : nullptr;
+    a.pb = d->pair_block, a.own = d->own, a.partner = d->partner, a.seg = nullptr, a.S = d->S, a.n_rows = d->n_rows;
+    a.table = nullptr, a.table_rows = 0, a.k = 0;
+    a.out_xz = nullptr, a.out_idx = nullptr, a.out_segid = nullptr;
+    // the longest row: the caller's bound for packed rows, what a row's slot holds otherwise
+    a.max_len = packed ? (d->max_len > 0 ? d->max_len : 1) : (int32_t)(headed ? d->row_stride - 1 : d->row_stride);
+    a.flags = d->flags;
+    a.slot_id = nullptr, a.val_add = 0;
+    a.key_M = a.key_m = a.key_shift = 0;
+    if (d->payload_kind == SUBGACC_JOIN_F64 && !packed)      // (strided / headed float rows: max_len is the hint, 0 = min(slot, 128))
+        a.spec_len = d->max_len > 0 ? d->max_len : (int32_t)(a.max_len < 128 ? a.max_len : 128);
+    return a;
+}
+
+// The size pass's view of a segment list over rows of ONE layout: only that layout's row pointer is set (ids: the lengths of headed
+// rows), so SegLen::len() reads the layout that was decided.  The caller has refused a NULL row pointer with S > 0.
+static SegLen seg_len(RowLayout layout, const int64_t *row_off, const int32_t *row_len, const int32_t *ids, int64_t row_stride,
+                      int64_t n_rows, const int64_t *own, const int64_t *partner, int32_t *flags, int64_t S, int64_t star_k) {
+    SegLen L{layout == RowLayout::Packed ? row_off : nullptr, layout == RowLayout::Strided ? row_len : nullptr, n_rows, own, partner,
+             flags, S};
+    if (layout == RowLayout::Headed) L.row_head = ids, L.row_stride = row_stride;
+    L.star_k = star_k;
+    return L;
+}
+
 static size_t onepass_state_bytes(int64_t S);
 extern "C" size_t subgacc_sjoin_workspace_bytes(int64_t S) {
     if (S < 0) S = 0;
@@ -2118,31 +2200,21 @@ extern "C" size_t subgacc_sjoin_workspace_bytes(int64_t S) {
     return two_step > one_call ? two_step : one_call;
 }
 
-static int join_sizes(const int64_t *spg_indptr, const int32_t *row_len, int64_t n_rows, const int64_t *own,
-                      const int64_t *partner, int64_t S, int64_t *out_seg, int32_t *flags, void *workspace,
-                      size_t workspace_bytes, void *stream, int64_t star_k = 0) {
-    SG_REQUIRE(S >= 0 && out_seg && n_rows >= 0, SUBGACC_ERR_BADARG, "sjoin_sizes: bad arguments");
+static int join_sizes(const SegLen &L, int64_t *out_seg, void *workspace, size_t workspace_bytes, void *stream) {
+    SG_REQUIRE(L.S >= 0 && out_seg && L.n_rows >= 0, SUBGACC_ERR_BADARG, "sjoin_sizes: bad arguments");
     hipStream_t s = (hipStream_t)stream;
-    if (S == 0) return exclusive_scan_i64(nullptr, 0, out_seg, nullptr, 0, s);
-    SG_REQUIRE((spg_indptr || row_len) && own, SUBGACC_ERR_BADARG, "sjoin_sizes: null argument");
-    SG_REQUIRE(workspace && workspace_bytes >= subgacc_sjoin_workspace_bytes(S), SUBGACC_ERR_WORKSPACE,
+    if (L.S == 0) return exclusive_scan_i64(nullptr, 0, out_seg, nullptr, 0, s);
+    SG_REQUIRE(L.own, SUBGACC_ERR_BADARG, "sjoin_sizes: null argument");
+    SG_REQUIRE(workspace && workspace_bytes >= subgacc_sjoin_workspace_bytes(L.S), SUBGACC_ERR_WORKSPACE,
                "sjoin_sizes: workspace too small");
-    SegLen L{spg_indptr, row_len, n_rows, own, partner, flags, S};
-    L.star_k = star_k;
-    const int64_t nb = ceil_div(S, kSegTile);
+    const int64_t nb = ceil_div(L.S, kSegTile);
     SG_REQUIRE(nb < (1ll << 31), SUBGACC_ERR_BADARG, "sjoin_sizes: too many segments");
-    if (nb == 1) {
-        hipLaunchKernelGGL(sjoin_seg_scan_kernel<kSegItems>, dim3(1), dim3(kScanThreads), 0, s, L, (const int64_t *)nullptr, out_seg);
-    } else if (S <= (int64_t)kScanThreads * kSegItemsSmall) {
-        hipLaunchKernelGGL(sjoin_seg_scan_kernel<kSegItemsSmall>, dim3(1), dim3(kScanThreads), 0, s, L, (const int64_t *)nullptr, out_seg);
-    } else {
-        int64_t *partial = (int64_t *)workspace;     // nb words <= S words
-        hipLaunchKernelGGL(sjoin_seg_reduce_kernel, dim3((unsigned)nb), dim3(kScanThreads), 0, s, L, partial);
-        hipLaunchKernelGGL(sjoin_seg_scan_kernel<kSegItems>, dim3((unsigned)nb), dim3(kScanThreads), 0, s, L, (const int64_t *)partial,
-                           out_seg);
-    }
-    SG_LAUNCH_CHECK();
-    return SUBGACC_OK;
+    if (nb == 1) return launch(sjoin_seg_scan_kernel<kSegItems>, 1, kScanThreads, 0, s, L, (const int64_t *)nullptr, out_seg);
+    if (L.S <= (int64_t)kScanThreads * kSegItemsSmall)
+        return launch(sjoin_seg_scan_kernel<kSegItemsSmall>, 1, kScanThreads, 0, s, L, (const int64_t *)nullptr, out_seg);
+    int64_t *partial = (int64_t *)workspace;     // nb words <= S words
+    if (int rc = launch(sjoin_seg_reduce_kernel, nb, kScanThreads, 0, s, L, partial)) return rc;
+    return launch(sjoin_seg_scan_kernel<kSegItems>, nb, kScanThreads, 0, s, L, (const int64_t *)partial, out_seg);
 }
 
 // the size pass of subgacc_sjoin_fill_v2(options & SUBGACC_JOIN_OPT_SIZES): one launch, see sjoin_sizes_onepass_kernel
@@ -2151,28 +2223,28 @@ static size_t onepass_state_bytes(int64_t S) {      // the header and one word p
 }
 
 
-static int join_sizes_onepass(const subgacc_join_desc *d, hipStream_t s) {
-    SG_REQUIRE(d->S >= 0 && d->n_rows >= 0 && d->out_seg && !d->seg, SUBGACC_ERR_BADARG,
-               "sjoin_fill_v2: OPT_SIZES writes out_seg [S+1] and reads no seg");
+static int join_sizes_onepass(const subgacc_join_desc *d, RowLayout layout, hipStream_t s) {
+    // headed rows keep their lengths in `ids`: the size pass reads them (the sizes-only call included)
+    SG_REQUIRE(layout != RowLayout::Headed || d->S == 0 || d->ids, SUBGACC_ERR_BADARG,
+               "sjoin_fill_v2: null argument (ids: the lengths of headed rows)");
+    SG_REQUIRE(d->out_seg && !d->seg, SUBGACC_ERR_BADARG, "sjoin_fill_v2: OPT_SIZES writes out_seg [S+1] and reads no seg");
     SG_REQUIRE(d->own || d->S == 0, SUBGACC_ERR_BADARG, "sjoin_fill_v2: null segment list");
     const int64_t nb = d->S > 0 ? ceil_div(d->S, (int64_t)kScanThreads * kOnePassItems) : 1;
     SG_REQUIRE(nb < (1ll << 31), SUBGACC_ERR_BADARG, "sjoin_fill_v2: too many segments");
     SG_REQUIRE(d->size_state && (size_t)d->size_state_bytes >= onepass_state_bytes(d->S), SUBGACC_ERR_WORKSPACE,
                "sjoin_fill_v2: size_state too small (subgacc_sjoin_workspace_bytes(S) bytes, zeroed once)");
-    SegLen L{d->row_off, d->row_len, d->n_rows, d->own, d->partner, d->flags, d->S};
-    if (!d->row_off && !d->row_len) L.row_head = d->ids, L.row_stride = d->row_stride;      // headed rows
-    if (d->options & SUBGACC_JOIN_OPT_STAR) L.star_k = d->pair_block;
-    hipLaunchKernelGGL(sjoin_sizes_onepass_kernel<kOnePassItems>, dim3((unsigned)nb), dim3(kScanThreads), 0, s, L, d->out_seg,
-                       (unsigned long long *)d->size_state, d->host_tail, (int)nb);
-    SG_LAUNCH_CHECK();
-    return SUBGACC_OK;
+    const SegLen L = seg_len(layout, d->row_off, d->row_len, d->ids, d->row_stride, d->n_rows, d->own, d->partner, d->flags, d->S,
+                             (d->options & SUBGACC_JOIN_OPT_STAR) ? d->pair_block : 0);
+    return launch(sjoin_sizes_onepass_kernel<kOnePassItems>, nb, kScanThreads, 0, s, L, d->out_seg, (unsigned long long *)d->size_state,
+                  d->host_tail, (int)nb);
 }
 
 extern "C" int subgacc_sjoin_sizes(const int64_t *spg_indptr, int64_t n_rows, const int64_t *own, const int64_t *partner,
                                    int64_t S, int64_t *out_seg, int32_t *flags, void *workspace, size_t workspace_bytes,
                                    void *stream) {
     SG_REQUIRE(spg_indptr || S == 0, SUBGACC_ERR_BADARG, "sjoin_sizes: null argument");
-    return join_sizes(spg_indptr, nullptr, n_rows, own, partner, S, out_seg, flags, workspace, workspace_bytes, stream);
+    return join_sizes(seg_len(RowLayout::Packed, spg_indptr, nullptr, nullptr, 0, n_rows, own, partner, flags, S, 0), out_seg, workspace,
+                      workspace_bytes, stream);
 }
 
 extern "C" int subgacc_sjoin_star_sizes(const int64_t *spg_indptr, int64_t n_rows, const int64_t *own, const int64_t *partner,
@@ -2182,14 +2254,16 @@ extern "C" int subgacc_sjoin_star_sizes(const int64_t *spg_indptr, int64_t n_row
                "sjoin_star_sizes: P = %lld sources x K = %lld targets (P*K < 2^31)", (long long)P, (long long)K);
     const int64_t S = 2 * P * K;
     SG_REQUIRE(S == 0 || (spg_indptr && own && partner), SUBGACC_ERR_BADARG, "sjoin_star_sizes: null argument");
-    return join_sizes(spg_indptr, nullptr, n_rows, own, partner, S, out_seg, flags, workspace, workspace_bytes, stream, K);
+    return join_sizes(seg_len(RowLayout::Packed, spg_indptr, nullptr, nullptr, 0, n_rows, own, partner, flags, S, K), out_seg, workspace,
+                      workspace_bytes, stream);
 }
 
 extern "C" int subgacc_sjoin_sizes_rows(const int32_t *row_len, int64_t n_rows, const int64_t *own, const int64_t *partner,
                                         int64_t S, int64_t *out_seg, int32_t *flags, void *workspace,
                                         size_t workspace_bytes, void *stream) {
     SG_REQUIRE(row_len || S == 0, SUBGACC_ERR_BADARG, "sjoin_sizes_rows: null argument");
-    return join_sizes(nullptr, row_len, n_rows, own, partner, S, out_seg, flags, workspace, workspace_bytes, stream);
+    return join_sizes(seg_len(RowLayout::Strided, nullptr, row_len, nullptr, 0, n_rows, own, partner, flags, S, 0), out_seg, workspace,
+                      workspace_bytes, stream);
 }
 
 // LDS of the per-wave staging areas of emit_key_span: [4 + 64 x 2k] floats per wave + the round-up to a 16-byte boundary
@@ -2203,24 +2277,14 @@ static int launch_table_pairs(JoinArgs &a, int64_t S, int64_t pair_block, bool v
     const size_t lds = (size_t)a.max_len * 12 + key_stage_bytes(kPairEmit / kWave, k);
     SG_REQUIRE(lds <= (size_t)kLdsBytes, SUBGACC_ERR_LDS, "%s: rows of %d members do not fit LDS", who, (int)a.max_len);
     a.split = pair_split(S / 2);
-    const int64_t grid = xcd_grid(S / 2 * a.split);
-    SG_REQUIRE(grid < (1ll << 31) && S / 2 < (1ll << 31), SUBGACC_ERR_BADARG, "%s: too many segments in one call", who);
-    const uint32_t pairs = (uint32_t)(S / 2), pb = (uint32_t)pair_block;
-    hipStream_t s = (hipStream_t)stream;
-#define SG_TAB_LAUNCH(KVV)                                                                                                     \
-    do {                                                                                                                        \
-        if (lds > 64 * 1024)                                                                                                    \
-            SG_CHECK_HIP(hipFuncSetAttribute((const void *)sjoin_keypair_kernel<KVV, kPairEmit, false, true>,                   \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                            \
-        hipLaunchKernelGGL((sjoin_keypair_kernel<KVV, kPairEmit, false, true>), dim3((unsigned)grid), dim3(kPairEmit), lds, s, a, pb, pairs); \
-    } while (0)
-    if (vec4) SG_TAB_LAUNCH(4);
-    else if (a.out_xz && a.k == 3) SG_TAB_LAUNCH(3);      // the 2-hop configurations (collab-like)
-    else if (a.out_xz && a.k == 5) SG_TAB_LAUNCH(5);      // 4 hops
-    else SG_TAB_LAUNCH(0);
-#undef SG_TAB_LAUNCH
-    SG_LAUNCH_CHECK();
-    return SUBGACC_OK;
+    int64_t grid;
+    if (int rc = grid_of(S / 2 * a.split, who, grid)) return rc;
+    void (*kernel)(JoinArgs, uint32_t, uint32_t);
+    if (vec4) kernel = sjoin_keypair_kernel<4, kPairEmit, false, true>;
+    else if (a.out_xz && a.k == 3) kernel = sjoin_keypair_kernel<3, kPairEmit, false, true>;      // the 2-hop configurations (collab-like)
+    else if (a.out_xz && a.k == 5) kernel = sjoin_keypair_kernel<5, kPairEmit, false, true>;      // 4 hops
+    else kernel = sjoin_keypair_kernel<0, kPairEmit, false, true>;
+    return launch(kernel, grid, kPairEmit, lds, (hipStream_t)stream, a, (uint32_t)pair_block, (uint32_t)(S / 2));
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2233,9 +2297,7 @@ static int key_args(JoinArgs &a, int32_t num_walks, int32_t num_steps, const cha
     if (shift < 0) return shift;
     SG_REQUIRE(num_steps * shift + 1 <= (wide ? 63 : 31) && num_steps + 1 <= 16, SUBGACC_ERR_KEYWIDTH,
                "%s: LP keys of %d steps x %d bits do not fit %d bits", who, num_steps, shift, wide ? 64 : 32);
-    a.table = nullptr, a.table_rows = 0, a.k = num_steps + 1;
-    a.out_idx = nullptr;
-    a.slot_id = nullptr, a.val_add = 0;
+    a.k = num_steps + 1;
     a.key_M = num_walks, a.key_m = num_steps, a.key_shift = shift;
     return SUBGACC_OK;
 }
@@ -2252,29 +2314,21 @@ static int launch_key_join(JoinArgs &a, int32_t num_walks, int32_t num_steps, in
     const size_t lds = (size_t)a.max_len * (wide ? 20 : 12) + key_stage_bytes(nt / kWave, a.k);
     SG_REQUIRE(lds <= (size_t)kLdsBytes, SUBGACC_ERR_LDS, "%s: rows of %d members do not fit LDS", who, (int)a.max_len);
     a.split = pair_split(S / 2);
-    const int64_t grid = xcd_grid(S / 2 * a.split);
-    SG_REQUIRE(grid < (1ll << 31) && S / 2 < (1ll << 31), SUBGACC_ERR_BADARG, "%s: too many segments in one call", who);
-    hipStream_t s = (hipStream_t)stream;
-    const uint32_t pairs = (uint32_t)(S / 2), pb = (uint32_t)pair_block;
-#define SG_KEY_LAUNCH(KVV, NTT, W)                                                                                             \
-    do {                                                                                                                        \
-        if (lds > 64 * 1024)                                                                                                    \
-            SG_CHECK_HIP(hipFuncSetAttribute((const void *)sjoin_keypair_kernel<KVV, NTT, W>,                                   \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                            \
-        hipLaunchKernelGGL((sjoin_keypair_kernel<KVV, NTT, W>), dim3((unsigned)grid), dim3(NTT), lds, s, a, pb, pairs);         \
-    } while (0)
+    int64_t grid;
+    if (int rc = grid_of(S / 2 * a.split, who, grid)) return rc;
+    void (*kernel)(JoinArgs, uint32_t, uint32_t);
+    int threads = kPairEmit;
     if (wide) {
-        if (a.k == 5 && nt == 256) SG_KEY_LAUNCH(5, 256, true);
-        else if (a.k == 5) SG_KEY_LAUNCH(5, kPairEmit, true);
-        else SG_KEY_LAUNCH(0, kPairEmit, true);
-    } else if (a.k == 4 && nt == 256) SG_KEY_LAUNCH(4, 256, false);
-    else if (a.k == 4) SG_KEY_LAUNCH(4, kPairEmit, false);      // 3 hops
-    else if (a.k == 3) SG_KEY_LAUNCH(3, kPairEmit, false);      // 2 hops (the collab-like configurations)
-    else if (a.k == 5) SG_KEY_LAUNCH(5, kPairEmit, false);      // 4 hops with 32-bit keys (M <= 127: the reference's own citation2 setting)
-    else SG_KEY_LAUNCH(0, kPairEmit, false);
-#undef SG_KEY_LAUNCH
-    SG_LAUNCH_CHECK();
-    return SUBGACC_OK;
+        if (a.k == 5 && nt == 256) kernel = sjoin_keypair_kernel<5, 256, true>, threads = 256;
+        else if (a.k == 5) kernel = sjoin_keypair_kernel<5, kPairEmit, true>;
+        else kernel = sjoin_keypair_kernel<0, kPairEmit, true>;
+    } else if (a.k == 4 && nt == 256) kernel = sjoin_keypair_kernel<4, 256, false>, threads = 256;
+    else if (a.k == 4) kernel = sjoin_keypair_kernel<4, kPairEmit, false>;      // 3 hops
+    else if (a.k == 3) kernel = sjoin_keypair_kernel<3, kPairEmit, false>;      // 2 hops (the collab-like configurations)
+    // 4 hops with 32-bit keys (M <= 127: the reference's own citation2 setting)
+    else if (a.k == 5) kernel = sjoin_keypair_kernel<5, kPairEmit, false>;
+    else kernel = sjoin_keypair_kernel<0, kPairEmit, false>;
+    return launch(kernel, grid, threads, lds, (hipStream_t)stream, a, (uint32_t)pair_block, (uint32_t)(S / 2));
 }
 
 
@@ -2287,19 +2341,12 @@ static int launch_f64_pairs(JoinArgs &a, int64_t S, int64_t pair_block, void *st
     const size_t flds = (size_t)a.max_len * 20 + 16;
     SG_REQUIRE(flds <= (size_t)kLdsBytes, SUBGACC_ERR_LDS, "sjoin_fill: float rows of %d members do not fit LDS", (int)a.max_len);
     a.split = pair_split(S / 2);
-    const int64_t grid = xcd_grid(S / 2 * a.split);
-    SG_REQUIRE(grid < (1ll << 31) && S / 2 < (1ll << 31), SUBGACC_ERR_BADARG, "sjoin_fill: too many segments in one call");
+    int64_t grid;
+    if (int rc = grid_of(S / 2 * a.split, "sjoin_fill", grid)) return rc;
     const uint32_t pairs = (uint32_t)(S / 2), pb32 = (uint32_t)pair_block;
     hipStream_t s = (hipStream_t)stream;
-    if (a.max_len <= 2 * kWave) {
-        hipLaunchKernelGGL((sjoin_f64pair_kernel<kWave>), dim3((unsigned)grid), dim3(kWave), flds, s, a, pb32, pairs);
-    } else {
-        if (flds > 64 * 1024)
-            SG_CHECK_HIP(hipFuncSetAttribute((const void *)sjoin_f64pair_kernel<kPairEmit>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flds));
-        hipLaunchKernelGGL((sjoin_f64pair_kernel<kPairEmit>), dim3((unsigned)grid), dim3(kPairEmit), flds, s, a, pb32, pairs);
-    }
-    SG_LAUNCH_CHECK();
-    return SUBGACC_OK;
+    if (a.max_len <= 2 * kWave) return launch(sjoin_f64pair_kernel<kWave>, grid, kWave, flds, s, a, pb32, pairs);
+    return launch(sjoin_f64pair_kernel<kPairEmit>, grid, kPairEmit, flds, s, a, pb32, pairs);
 }
 
 // any list that is not made of mirrored pairs (or whose two rows do not fit LDS together): one wave per segment
@@ -2307,26 +2354,17 @@ static int launch_segments(JoinArgs &a, bool f64, bool vec4, void *stream) {
     size_t lds = (size_t)a.max_len * (f64 ? 12 : 8);
     const bool staged = lds <= (size_t)kLdsBytes;   // else: rows longer than LDS, searched in place (sjoin_fill_kernel<.., false>)
     if (!staged) lds = 0;
-    const int64_t grid = xcd_grid(a.S);
-    SG_REQUIRE(grid < (1ll << 31), SUBGACC_ERR_BADARG, "sjoin_fill: too many segments in one call");
-    hipStream_t s = (hipStream_t)stream;
-#define SG_JOIN_LAUNCH(F, KVV)                                                                                   \
-    do {                                                                                                          \
-        if (lds > 64 * 1024)                                                                                      \
-            SG_CHECK_HIP(hipFuncSetAttribute((const void *)sjoin_fill_kernel<F, KVV>,                             \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));              \
-        hipLaunchKernelGGL((sjoin_fill_kernel<F, KVV>), dim3((unsigned)grid), dim3(kJoinThreads), lds, s, a);     \
-    } while (0)
+    int64_t grid;
+    if (int rc = grid_of(a.S, "sjoin_fill", grid)) return rc;
+    void (*kernel)(JoinArgs);
     if (!staged) {
-        if (f64) hipLaunchKernelGGL((sjoin_fill_kernel<true, 0, false>), dim3((unsigned)grid), dim3(kJoinThreads), 0, s, a);
-        else if (vec4) hipLaunchKernelGGL((sjoin_fill_kernel<false, 4, false>), dim3((unsigned)grid), dim3(kJoinThreads), 0, s, a);
-        else hipLaunchKernelGGL((sjoin_fill_kernel<false, 0, false>), dim3((unsigned)grid), dim3(kJoinThreads), 0, s, a);
-    } else if (f64) SG_JOIN_LAUNCH(true, 0);
-    else if (vec4) SG_JOIN_LAUNCH(false, 4);
-    else SG_JOIN_LAUNCH(false, 0);
-#undef SG_JOIN_LAUNCH
-    SG_LAUNCH_CHECK();
-    return SUBGACC_OK;
+        if (f64) kernel = sjoin_fill_kernel<true, 0, false>;
+        else if (vec4) kernel = sjoin_fill_kernel<false, 4, false>;
+        else kernel = sjoin_fill_kernel<false, 0, false>;
+    } else if (f64) kernel = sjoin_fill_kernel<true, 0>;
+    else if (vec4) kernel = sjoin_fill_kernel<false, 4>;
+    else kernel = sjoin_fill_kernel<false, 0>;
+    return launch(kernel, grid, kJoinThreads, lds, (hipStream_t)stream, a);
 }
 
 // Star lists (SUBGACC_JOIN_OPT_STAR): a workgroup per source and chunk of its K targets.  The chunk is chosen so that the grid holds
@@ -2355,30 +2393,22 @@ static int launch_star(JoinArgs &a, int mode, bool vec4, bool packed, int64_t K,
     if (chunks > K) chunks = K;
     const int64_t chunk = ceil_div(K, chunks);
     chunks = ceil_div(K, chunk);
-    const int64_t grid = xcd_grid(P * chunks);
-    SG_REQUIRE(grid < (1ll << 31), SUBGACC_ERR_BADARG, "sjoin_fill_v2: too many segments in one call");
+    int64_t grid;
+    if (int rc = grid_of(P * chunks, "sjoin_fill_v2", grid)) return rc;
     const size_t lds = (((size_t)cap * per + 15) & ~(size_t)15) + stage;
-    hipStream_t s = (hipStream_t)stream;
-#define SG_STAR_LAUNCH(KVV, NTT, M)                                                                                            \
-    do {                                                                                                                        \
-        if (lds > 64 * 1024)                                                                                                    \
-            SG_CHECK_HIP(hipFuncSetAttribute((const void *)sjoin_star_kernel<KVV, NTT, M>,                                      \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                            \
-        hipLaunchKernelGGL((sjoin_star_kernel<KVV, NTT, M>), dim3((unsigned)grid), dim3(NTT), lds, s, a, (uint32_t)P, (uint32_t)K, \
-                           (uint32_t)chunk, (uint32_t)chunks);                                                                   \
-    } while (0)
-    if (f64 && nt == kWave) SG_STAR_LAUNCH(0, kWave, 2);
-    else if (f64) SG_STAR_LAUNCH(0, kPairEmit, 2);
-    else if (mode == 1 && vec4) SG_STAR_LAUNCH(4, kPairEmit, 1);
-    else if (mode == 1 && a.k == 3) SG_STAR_LAUNCH(3, kPairEmit, 1);
-    else if (mode == 1 && a.k == 5) SG_STAR_LAUNCH(5, kPairEmit, 1);
-    else if (mode == 1) SG_STAR_LAUNCH(0, kPairEmit, 1);
-    else if (a.k == 4) SG_STAR_LAUNCH(4, kPairEmit, 0);
-    else if (a.k == 3) SG_STAR_LAUNCH(3, kPairEmit, 0);
-    else if (a.k == 5) SG_STAR_LAUNCH(5, kPairEmit, 0);
-    else SG_STAR_LAUNCH(0, kPairEmit, 0);
-#undef SG_STAR_LAUNCH
-    SG_LAUNCH_CHECK();
+    void (*kernel)(JoinArgs, uint32_t, uint32_t, uint32_t, uint32_t);
+    if (f64 && nt == kWave) kernel = sjoin_star_kernel<0, kWave, 2>;
+    else if (f64) kernel = sjoin_star_kernel<0, kPairEmit, 2>;
+    else if (mode == 1 && vec4) kernel = sjoin_star_kernel<4, kPairEmit, 1>;
+    else if (mode == 1 && a.k == 3) kernel = sjoin_star_kernel<3, kPairEmit, 1>;
+    else if (mode == 1 && a.k == 5) kernel = sjoin_star_kernel<5, kPairEmit, 1>;
+    else if (mode == 1) kernel = sjoin_star_kernel<0, kPairEmit, 1>;
+    else if (a.k == 4) kernel = sjoin_star_kernel<4, kPairEmit, 0>;
+    else if (a.k == 3) kernel = sjoin_star_kernel<3, kPairEmit, 0>;
+    else if (a.k == 5) kernel = sjoin_star_kernel<5, kPairEmit, 0>;
+    else kernel = sjoin_star_kernel<0, kPairEmit, 0>;
+    if (int rc = launch(kernel, grid, nt, lds, (hipStream_t)stream, a, (uint32_t)P, (uint32_t)K, (uint32_t)chunk, (uint32_t)chunks))
+        return rc;
     if (cap < a.max_len) return launch_segments(a, f64, vec4, stream);      // the sources longer than cap
     return SUBGACC_OK;
 }
@@ -2388,13 +2418,9 @@ static int launch_counts(JoinArgs &a, int64_t pair_block, float *out_counts, voi
     SG_REQUIRE(lds <= (size_t)kLdsBytes, SUBGACC_ERR_LDS,
                "sjoin_counts: %lld distinct LP rows and rows of %d members need %zu B of LDS; use the row form",
                (long long)a.table_rows, (int)a.max_len, lds);
-    if (lds > 64 * 1024)
-        SG_CHECK_HIP(hipFuncSetAttribute((const void *)sjoin_counts_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int64_t grid = xcd_grid(a.S / 2);
-    SG_REQUIRE(grid < (1ll << 31), SUBGACC_ERR_BADARG, "sjoin_counts: too many segments in one call");
-    hipLaunchKernelGGL(sjoin_counts_kernel, dim3((unsigned)grid), dim3(kPairThreads), lds, (hipStream_t)stream, a, pair_block, out_counts);
-    SG_LAUNCH_CHECK();
-    return SUBGACC_OK;
+    int64_t grid;
+    if (int rc = grid_of(a.S / 2, "sjoin_counts", grid)) return rc;
+    return launch(sjoin_counts_kernel, grid, kPairThreads, lds, (hipStream_t)stream, a, pair_block, out_counts);
 }
 
 static int launch_pair_form(JoinArgs &a, int64_t pair_block, int32_t *out_pairs, int32_t *out_mult, int32_t *out_cnt, void *stream) {
@@ -2404,28 +2430,15 @@ static int launch_pair_form(JoinArgs &a, int64_t pair_block, int32_t *out_pairs,
     while ((1 << ts_log2) < a.max_len + a.max_len / 4 + 1) ++ts_log2;
     const size_t lds = (size_t)2 * (1u << ts_log2) * 12 + (size_t)a.max_len * 16;
     SG_REQUIRE(lds + 64 <= (size_t)kLdsBytes, SUBGACC_ERR_LDS, "sjoin_pairs: %zu B of LDS needed", lds);
-    if (lds > 64 * 1024)
-        SG_CHECK_HIP(hipFuncSetAttribute((const void *)sjoin_pairs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int64_t grid = xcd_grid(a.S / 2);
-    SG_REQUIRE(grid < (1ll << 31), SUBGACC_ERR_BADARG, "sjoin_pairs: too many segments in one call");
-    hipLaunchKernelGGL(sjoin_pairs_kernel, dim3((unsigned)grid), dim3(kPairThreads), lds, (hipStream_t)stream, a, pair_block, ts_log2,
-                       out_pairs, out_mult, out_cnt);
-    SG_LAUNCH_CHECK();
-    return SUBGACC_OK;
+    int64_t grid;
+    if (int rc = grid_of(a.S / 2, "sjoin_pairs", grid)) return rc;
+    return launch(sjoin_pairs_kernel, grid, kPairThreads, lds, (hipStream_t)stream, a, pair_block, ts_log2, out_pairs, out_mult, out_cnt);
 }
 
 extern "C" int subgacc_sjoin_fill_v2(const subgacc_join_desc *d, void *stream) {
-    SG_REQUIRE(d, SUBGACC_ERR_BADARG, "sjoin_fill_v2: null descriptor");
-    SG_REQUIRE(d->struct_bytes == (int32_t)sizeof(subgacc_join_desc), SUBGACC_ERR_BADARG,
-               "sjoin_fill_v2: descriptor of %d bytes, this library's is %d (set struct_bytes = sizeof(subgacc_join_desc))",
-               (int)d->struct_bytes, (int)sizeof(subgacc_join_desc));
-    // the store's layout: packed rows (row_off), strided rows (row_len + row_stride), headed rows (neither; row_stride)
-    const bool packed = d->row_off != nullptr, strided = d->row_len != nullptr;
-    const bool headed = !packed && !strided && d->row_stride > 0;
-    SG_REQUIRE((int)packed + (int)strided + (int)headed == 1, SUBGACC_ERR_BADARG,
-               "sjoin_fill_v2: exactly one of row_off (packed rows) / row_len (strided rows) / neither, with row_stride (headed rows)");
-    SG_REQUIRE(packed || (d->row_stride > (headed ? 1 : 0) && d->row_stride < (1ll << 31)), SUBGACC_ERR_BADARG,
-               "sjoin_fill_v2: row_stride = %lld", (long long)d->row_stride);
+    RowLayout layout;
+    if (int rc = decode_desc("sjoin_fill_v2", d, false, layout)) return rc;
+    const bool packed = layout == RowLayout::Packed, strided = layout == RowLayout::Strided;
     SG_REQUIRE((d->options & ~(SUBGACC_JOIN_OPT_SIZES | SUBGACC_JOIN_OPT_STAR)) == 0, SUBGACC_ERR_BADARG,
                "sjoin_fill_v2: unknown option bits %d", (int)d->options);
     SG_REQUIRE(d->form >= SUBGACC_JOIN_ROWS && d->form <= SUBGACC_JOIN_PAIRS, SUBGACC_ERR_BADARG, "sjoin_fill_v2: unknown form %d", (int)d->form);
@@ -2440,7 +2453,6 @@ extern "C" int subgacc_sjoin_fill_v2(const subgacc_join_desc *d, void *stream) {
     const int64_t S = d->S, pb = d->pair_block;
     // ---- what the kernels would not survive is refused here, before anything is launched (with OPT_SIZES: before the size pass has
     //      written out_seg / host_tail)
-    SG_REQUIRE(S >= 0 && d->n_rows >= 0 && d->max_len >= 0, SUBGACC_ERR_BADARG, "sjoin_fill_v2: bad arguments");
     SG_REQUIRE(!sized || d->form == SUBGACC_JOIN_ROWS, SUBGACC_ERR_BADARG, "sjoin_fill_v2: OPT_SIZES goes with the row form");
     if (star) {      // one source against K targets: the scope of include/subgacc.h, refused here before the size pass runs
         SG_REQUIRE(d->form == SUBGACC_JOIN_ROWS, SUBGACC_ERR_BADARG, "sjoin_fill_v2: the star option (OPT_STAR) goes with the row form (not the count or pair form)");
@@ -2448,7 +2460,7 @@ extern "C" int subgacc_sjoin_fill_v2(const subgacc_join_desc *d, void *stream) {
         SG_REQUIRE(kind != SUBGACC_JOIN_KEY64, SUBGACC_ERR_BADARG, "sjoin_fill_v2: the star option (OPT_STAR) does not join 64-bit keys (KEY64)");
         SG_REQUIRE(pb > 0, SUBGACC_ERR_BADARG, "sjoin_fill_v2: the star option (OPT_STAR) needs pair_block = K > 0 targets per source (pair_block = %lld)",
                    (long long)pb);
-        SG_REQUIRE(S >= 0 && S % (2 * pb) == 0, SUBGACC_ERR_BADARG, "sjoin_fill_v2: the star option (OPT_STAR) needs S = 2*P*K (S = %lld, K = %lld)",
+        SG_REQUIRE(S % (2 * pb) == 0, SUBGACC_ERR_BADARG, "sjoin_fill_v2: the star option (OPT_STAR) needs S = 2*P*K (S = %lld, K = %lld)",
                    (long long)S, (long long)pb);
         SG_REQUIRE(S == 0 || d->own, SUBGACC_ERR_BADARG, "sjoin_fill_v2: the star option (OPT_STAR) needs own (the P sources); own = NULL");
         SG_REQUIRE(S == 0 || d->partner, SUBGACC_ERR_BADARG,
@@ -2467,10 +2479,8 @@ extern "C" int subgacc_sjoin_fill_v2(const subgacc_join_desc *d, void *stream) {
             if (d->form == SUBGACC_JOIN_ROWS) SG_REQUIRE(d->out_xz || d->out_idx, SUBGACC_ERR_BADARG, "sjoin_fill_v2: no output requested");
         }
     }
-    // headed rows keep their lengths in `ids`: the size pass reads them too (the sizes-only call included)
-    SG_REQUIRE(!headed || S == 0 || d->ids, SUBGACC_ERR_BADARG, "sjoin_fill_v2: null argument (ids: the lengths of headed rows)");
     if (sized) {       // the whole join of a batch in one call: size pass, then the fill behind it
-        const int rc = join_sizes_onepass(d, (hipStream_t)stream);
+        const int rc = join_sizes_onepass(d, layout, (hipStream_t)stream);
         if (rc != SUBGACC_OK || sizes_only) return rc;
     }
     if (keyed) {       // (also for S == 0: a caller learns about a key width that does not fit from its first, empty, call)
@@ -2484,31 +2494,21 @@ extern "C" int subgacc_sjoin_fill_v2(const subgacc_join_desc *d, void *stream) {
     const bool mirrored = pb > 0;
     SG_REQUIRE(d->form == SUBGACC_JOIN_COUNTS || seg, SUBGACC_ERR_BADARG, "sjoin_fill_v2: null argument (seg)");
 
-    JoinArgs a;
+    JoinArgs a = join_args(d, layout);
     a.sized_here = sized;
-    a.indptr = d->row_off, a.indices = headed ? d->ids + 1 : d->ids, a.data = d->payload;
-    a.row_len = d->row_len, a.row_stride = packed ? 0 : d->row_stride, a.row_head = headed ? d->ids : nullptr;
-    a.pb = pb, a.own = d->own, a.partner = d->partner, a.seg = seg, a.S = S, a.n_rows = d->n_rows;
-    a.table = d->table, a.table_rows = d->table_rows, a.k = d->k;
-    a.out_xz = d->out_xz, a.out_idx = d->out_idx, a.out_segid = d->out_segid;
-    // the longest row: the caller's bound for packed rows, what a row's slot holds otherwise
-    a.max_len = packed ? (d->max_len > 0 ? d->max_len : 1) : (int32_t)(headed ? d->row_stride - 1 : d->row_stride);
-    a.flags = d->flags;
-    a.slot_id = nullptr, a.val_add = 0;
-    a.key_M = a.key_m = a.key_shift = 0;
-
     if (d->form == SUBGACC_JOIN_COUNTS) {
         SG_REQUIRE(mirrored && d->out_counts && d->table_rows > 0, SUBGACC_ERR_BADARG,
                    "sjoin_counts: mirrored blocks (pair_block > 0), out_counts and table_rows > 0");
-        a.seg = nullptr, a.table = nullptr, a.k = 0, a.out_xz = nullptr, a.out_idx = nullptr, a.out_segid = nullptr;
+        a.table_rows = d->table_rows;
         return launch_counts(a, pb, d->out_counts, stream);
     }
+    a.seg = seg;
     if (d->form == SUBGACC_JOIN_PAIRS) {
         SG_REQUIRE(mirrored && d->out_pairs && d->out_mult && d->out_cnt, SUBGACC_ERR_BADARG,
                    "sjoin_pairs: mirrored blocks (pair_block > 0), out_pairs, out_mult and out_cnt");
-        a.table = nullptr, a.table_rows = 0, a.k = 0, a.out_xz = nullptr, a.out_idx = nullptr, a.out_segid = nullptr;
         return launch_pair_form(a, pb, d->out_pairs, d->out_mult, d->out_cnt, stream);
     }
+    a.out_xz = d->out_xz, a.out_segid = d->out_segid;
     if (keyed) {
         SG_REQUIRE(mirrored && d->out_xz, SUBGACC_ERR_BADARG,
                    "sjoin_fill_v2: key rows are joined as mirrored blocks (pair_block > 0, S a multiple of 2*pair_block) into out_xz");
@@ -2521,8 +2521,7 @@ extern "C" int subgacc_sjoin_fill_v2(const subgacc_join_desc *d, void *stream) {
     if (f64) {
         SG_REQUIRE(d->out_xz && !d->out_idx && !d->table, SUBGACC_ERR_BADARG,
                    "sjoin_fill_v2: float payload writes out_xz [R,2,1] only (train.py:39-43)");
-        a.k = 1, a.table = nullptr, a.table_rows = 0;
-        a.spec_len = packed ? 0 : (d->max_len > 0 ? d->max_len : (int32_t)(a.max_len < 128 ? a.max_len : 128));     // (headed / strided rows: max_len is the hint)
+        a.k = 1;
         if (star) return launch_star(a, 2, false, packed, pb, stream);
         if (mirrored && (size_t)a.max_len * 20 + 16 <= (size_t)kLdsBytes) return launch_f64_pairs(a, S, pb, stream);
         SG_REQUIRE(packed, SUBGACC_ERR_BADARG, "sjoin_fill_v2: strided / headed float rows are joined as mirrored blocks (pair_block > 0)");
@@ -2531,6 +2530,7 @@ extern "C" int subgacc_sjoin_fill_v2(const subgacc_join_desc *d, void *stream) {
     // SFptr+1 (packed / headed rows of a numbered store) or table slots (strided rows of a transient batch) with the Z_SF table
     SG_REQUIRE(!d->out_xz || (d->table && d->table_rows > 0 && d->k > 0 && d->k <= 16), SUBGACC_ERR_BADARG,
                "sjoin_fill_v2: out_xz needs the feature table, k <= 16");
+    a.table = d->table, a.table_rows = d->table_rows, a.k = d->k, a.out_idx = d->out_idx;
     if (strided) {
         // numbered table given: slot -> SFptr+1 through its id plane (uniq_table.hpp); else the table is indexed by slot+1
         SG_REQUIRE(!d->uniq_table || d->uniq_capacity > 0, SUBGACC_ERR_BADARG, "sjoin_fill_v2: uniq_capacity");
@@ -2545,81 +2545,49 @@ extern "C" int subgacc_sjoin_fill_v2(const subgacc_join_desc *d, void *stream) {
 }
 
 // The first model stages of the float encoders fused with the join (include/subgacc.h): the descriptor of a mirrored F64 join, no row
-// output.  f64stage_check: the descriptor's and H's refusals, shared by every fused stage (`name` leads the message); f64stage_join:
-// for S > 0, the JoinArgs, the staged row cap and the grid.  Every refusal comes before anything is launched.
-static int f64stage_check(const char *name, const subgacc_join_desc *d, int32_t H) {
-    SG_REQUIRE(d, SUBGACC_ERR_BADARG, "%s: null descriptor", name);
-    SG_REQUIRE(d->struct_bytes == (int32_t)sizeof(subgacc_join_desc), SUBGACC_ERR_BADARG,
-               "%s: descriptor of %d bytes, this library's is %d (set struct_bytes = sizeof(subgacc_join_desc))", name,
-               (int)d->struct_bytes, (int)sizeof(subgacc_join_desc));
-    const bool packed = d->row_off != nullptr, strided = d->row_len != nullptr;
-    const bool headed = !packed && !strided && d->row_stride > 1;
-    const int64_t S = d->S, pb = d->pair_block;
+// output.  f64stage_check: the refusals of every such stage beyond decode_desc's (`name` leads the message); f64stage_launch: for
+// S > 0, `kernel` over the S / 2 pairs, rows staged up to kMeanCap members.  Every refusal comes before anything is launched.
+static int f64stage_check(const char *name, const subgacc_join_desc *d, int32_t H, RowLayout &layout) {
+    if (int rc = decode_desc(name, d, true, layout)) return rc;
     SG_REQUIRE(d->payload_kind == SUBGACC_JOIN_F64, SUBGACC_ERR_BADARG,
                "%s: the fused stage joins a float payload (F64), not payload kind %d", name, (int)d->payload_kind);
-    SG_REQUIRE(!strided, SUBGACC_ERR_BADARG, "%s: joins packed or headed rows, not strided rows", name);
-    SG_REQUIRE(packed != headed, SUBGACC_ERR_BADARG, "%s: exactly one of row_off (packed rows) / row_stride > 1 (headed rows)", name);
-    SG_REQUIRE(packed || d->row_stride < (1ll << 31), SUBGACC_ERR_BADARG, "%s: row_stride = %lld", name, (long long)d->row_stride);
+    SG_REQUIRE(layout != RowLayout::Strided, SUBGACC_ERR_BADARG, "%s: joins packed or headed rows, not strided rows", name);
     SG_REQUIRE(d->form == SUBGACC_JOIN_ROWS && d->options == 0, SUBGACC_ERR_BADARG,
                "%s: form must be ROWS and options 0 (form %d, options %d)", name, (int)d->form, (int)d->options);
-    SG_REQUIRE(pb > 0, SUBGACC_ERR_BADARG, "%s: needs a mirrored list, pair_block > 0 (pair_block = %lld)", name, (long long)pb);
-    SG_REQUIRE(S >= 0 && S % (2 * pb) == 0, SUBGACC_ERR_BADARG,
-               "%s: S = %lld is not a multiple of 2*pair_block = %lld", name, (long long)S, (long long)(2 * pb));
-    SG_REQUIRE(d->own || S == 0, SUBGACC_ERR_BADARG, "%s: own = NULL with S = %lld segments", name, (long long)S);
     SG_REQUIRE(H >= 1 && H <= 1024, SUBGACC_ERR_BADARG, "%s: H = %d outside [1, 1024]", name, (int)H);
-    SG_REQUIRE(!d->out_xz && !d->out_idx && !d->out_segid && !d->out_counts && !d->out_pairs && !d->out_mult && !d->out_cnt &&
-                   !d->out_seg && !d->seg,
-               SUBGACC_ERR_BADARG, "%s: writes its own outputs only: the descriptor's out_* and seg fields must be NULL", name);
-    SG_REQUIRE(d->n_rows >= 0 && d->max_len >= 0, SUBGACC_ERR_BADARG, "%s: bad arguments", name);
     return SUBGACC_OK;
 }
 
-static int f64stage_join(const char *name, const subgacc_join_desc *d, JoinArgs &a, int32_t &cap, int64_t &grid) {
-    const bool packed = d->row_off != nullptr, headed = !packed;
-    const int64_t S = d->S, pb = d->pair_block;
+template <typename M>
+static int f64stage_launch(const char *name, const subgacc_join_desc *d, RowLayout layout,
+                           void (*kernel)(JoinArgs, uint32_t, uint32_t, int32_t, M), size_t (*lds)(int32_t), const M &m, void *stream) {
     SG_REQUIRE(d->flags && d->ids && d->payload, SUBGACC_ERR_BADARG, "%s: null argument (flags / ids / payload)", name);
-    a.indptr = d->row_off, a.indices = headed ? d->ids + 1 : d->ids, a.data = d->payload;
-    a.row_len = nullptr, a.row_stride = packed ? 0 : d->row_stride, a.row_head = headed ? d->ids : nullptr;
-    a.pb = pb, a.own = d->own, a.partner = d->partner, a.seg = nullptr, a.S = S, a.n_rows = d->n_rows;
-    a.table = nullptr, a.table_rows = 0, a.k = 1;
-    a.out_xz = nullptr, a.out_idx = nullptr, a.out_segid = nullptr;
-    a.max_len = packed ? (d->max_len > 0 ? d->max_len : 1) : (int32_t)(d->row_stride - 1);
-    a.flags = d->flags;
-    a.slot_id = nullptr, a.val_add = 0;
-    a.key_M = a.key_m = a.key_shift = 0;
-    a.spec_len = packed ? 0 : (d->max_len > 0 ? d->max_len : (int32_t)(a.max_len < 128 ? a.max_len : 128));
-    a.split = 1;
+    JoinArgs a = join_args(d, layout);
+    a.k = 1;
     // headed rows that the row form does not join are refused as it refuses them (sjoin_fill_v2: no one-segment kernel for them)
-    SG_REQUIRE(packed || (size_t)a.max_len * 20 + 16 <= (size_t)kLdsBytes, SUBGACC_ERR_BADARG,
+    SG_REQUIRE(layout == RowLayout::Packed || (size_t)a.max_len * 20 + 16 <= (size_t)kLdsBytes, SUBGACC_ERR_BADARG,
                "%s: headed float rows of %d members do not fit LDS (the row form refuses them too)", name, (int)a.max_len);
-    cap = a.max_len < kMeanCap ? a.max_len : kMeanCap;
-    SG_REQUIRE(S / 2 < (1ll << 31), SUBGACC_ERR_BADARG, "%s: too many segments in one call", name);
-    grid = xcd_grid(S / 2);
-    SG_REQUIRE(grid < (1ll << 31), SUBGACC_ERR_BADARG, "%s: too many segments in one call", name);
-    return SUBGACC_OK;
+    const int32_t cap = a.max_len < kMeanCap ? a.max_len : kMeanCap;
+    int64_t grid;
+    if (int rc = grid_of(d->S / 2, name, grid)) return rc;
+    return launch(kernel, grid, kMeanThreads, lds(cap), (hipStream_t)stream, a, (uint32_t)d->pair_block, (uint32_t)(d->S / 2), cap, m);
+}
+
+// sjoin_f64mean_kernel's LDS: f64pair_stage's arrays and S's pairs
+static size_t f64mean_lds(int32_t cap) {
+    return (size_t)cap * 16 + (size_t)((cap + 1) & ~1) * 4 + (size_t)(cap > kMeanThreads ? cap : kMeanThreads) * 8;
 }
 
 extern "C" int subgacc_sjoin_relu_mean(const subgacc_join_desc *d, const float *w1, const float *b1, int32_t H, float *out_mean,
                                        float *out_p, float *out_q, void *stream) {
     const char *name = "sjoin_relu_mean";
-    if (int rc = f64stage_check(name, d, H)) return rc;
+    RowLayout layout;
+    if (int rc = f64stage_check(name, d, H, layout)) return rc;
     SG_REQUIRE(w1 && b1 && out_mean, SUBGACC_ERR_BADARG, "sjoin_relu_mean: w1, b1 and out_mean are required (a NULL one given)");
     SG_REQUIRE((out_p == nullptr) == (out_q == nullptr), SUBGACC_ERR_BADARG, "sjoin_relu_mean: out_p and out_q go together (one is NULL)");
     if (d->S == 0) return SUBGACC_OK;
-    JoinArgs a;
-    int32_t cap;
-    int64_t grid;
-    if (int rc = f64stage_join(name, d, a, cap, grid)) return rc;
-    const size_t lds = (size_t)cap * 16 + (size_t)((cap + 1) & ~1) * 4 + (size_t)(cap > kMeanThreads ? cap : kMeanThreads) * 8;
-    const int64_t pb = d->pair_block, S = d->S;
-    MeanArgs m{w1, b1, H, out_mean, out_p, out_q};
-    hipStream_t s = (hipStream_t)stream;
-    if (out_p)
-        hipLaunchKernelGGL((sjoin_f64mean_kernel<true>), dim3((unsigned)grid), dim3(kMeanThreads), lds, s, a, (uint32_t)pb, (uint32_t)(S / 2), cap, m);
-    else
-        hipLaunchKernelGGL((sjoin_f64mean_kernel<false>), dim3((unsigned)grid), dim3(kMeanThreads), lds, s, a, (uint32_t)pb, (uint32_t)(S / 2), cap, m);
-    SG_LAUNCH_CHECK();
-    return SUBGACC_OK;
+    const MeanArgs m{w1, b1, H, out_mean, out_p, out_q};
+    return f64stage_launch(name, d, layout, out_p ? sjoin_f64mean_kernel<true> : sjoin_f64mean_kernel<false>, f64mean_lds, m, stream);
 }
 
 // sjoin_f64attn_kernel's LDS: f64pair_stage's arrays, S's pairs and two per-member factors, the block max
@@ -2631,80 +2599,50 @@ static size_t f64attn_lds(int32_t cap) {
 extern "C" int subgacc_sjoin_relu_attn(const subgacc_join_desc *d, const float *w1, const float *b1, const float *u, int32_t H,
                                        float *out_a, float *out_max, float *out_den, void *stream) {
     const char *name = "sjoin_relu_attn";
-    if (int rc = f64stage_check(name, d, H)) return rc;
+    RowLayout layout;
+    if (int rc = f64stage_check(name, d, H, layout)) return rc;
     SG_REQUIRE(w1 && b1 && u && out_a, SUBGACC_ERR_BADARG, "sjoin_relu_attn: w1, b1, u and out_a are required (a NULL one given)");
     SG_REQUIRE((out_max == nullptr) == (out_den == nullptr), SUBGACC_ERR_BADARG,
                "sjoin_relu_attn: out_max and out_den go together (one is NULL)");
     if (d->S == 0) return SUBGACC_OK;
-    JoinArgs a;
-    int32_t cap;
-    int64_t grid;
-    if (int rc = f64stage_join(name, d, a, cap, grid)) return rc;
-    AttnArgs m{w1, b1, u, H, out_a, out_max, out_den, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    hipLaunchKernelGGL((sjoin_f64attn_kernel<false>), dim3((unsigned)grid), dim3(kMeanThreads), f64attn_lds(cap), (hipStream_t)stream, a,
-                       (uint32_t)d->pair_block, (uint32_t)(d->S / 2), cap, m);
-    SG_LAUNCH_CHECK();
-    return SUBGACC_OK;
+    const AttnArgs m{w1, b1, u, H, out_a, out_max, out_den, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    return f64stage_launch(name, d, layout, sjoin_f64attn_kernel<false>, f64attn_lds, m, stream);
 }
 
 extern "C" int subgacc_sjoin_relu_attn_backward(const subgacc_join_desc *d, const float *w1, const float *b1, const float *u, int32_t H,
                                                 const float *g, const float *a_in, const float *max, const float *den, float *out_dw,
                                                 float *out_db, float *out_du, void *stream) {
     const char *name = "sjoin_relu_attn_backward";
-    if (int rc = f64stage_check(name, d, H)) return rc;
+    RowLayout layout;
+    if (int rc = f64stage_check(name, d, H, layout)) return rc;
     SG_REQUIRE(w1 && b1 && u && g && a_in && max && den && out_dw && out_db && out_du, SUBGACC_ERR_BADARG,
                "sjoin_relu_attn_backward: w1, b1, u, g, a, max, den, out_dw, out_db and out_du are required (a NULL one given)");
     if (d->S == 0) return SUBGACC_OK;
-    JoinArgs a;
-    int32_t cap;
-    int64_t grid;
-    if (int rc = f64stage_join(name, d, a, cap, grid)) return rc;
-    AttnArgs m{w1, b1, u, H, nullptr, nullptr, nullptr, g, a_in, max, den, out_dw, out_db, out_du};
-    hipLaunchKernelGGL((sjoin_f64attn_kernel<true>), dim3((unsigned)grid), dim3(kMeanThreads), f64attn_lds(cap), (hipStream_t)stream, a,
-                       (uint32_t)d->pair_block, (uint32_t)(d->S / 2), cap, m);
-    SG_LAUNCH_CHECK();
-    return SUBGACC_OK;
+    const AttnArgs m{w1, b1, u, H, nullptr, nullptr, nullptr, g, a_in, max, den, out_dw, out_db, out_du};
+    return f64stage_launch(name, d, layout, sjoin_f64attn_kernel<true>, f64attn_lds, m, stream);
 }
 
 // The LP encoder's first stage with attentional aggregation fused with the count form (include/subgacc.h): the descriptor of a mirrored
-// count-form join of a packed SFptr store, no output of the descriptor's own.  Every refusal comes before anything is launched.
+// count-form join of a packed SFptr store, no output of the descriptor's own.  counts_attn_check: the refusals beyond decode_desc's.
+// Every refusal comes before anything is launched.
 static int counts_attn_check(const char *name, const subgacc_join_desc *d) {
-    SG_REQUIRE(d, SUBGACC_ERR_BADARG, "%s: null descriptor", name);
-    SG_REQUIRE(d->struct_bytes == (int32_t)sizeof(subgacc_join_desc), SUBGACC_ERR_BADARG,
-               "%s: descriptor of %d bytes, this library's is %d (set struct_bytes = sizeof(subgacc_join_desc))", name,
-               (int)d->struct_bytes, (int)sizeof(subgacc_join_desc));
-    const int64_t S = d->S, pb = d->pair_block;
+    RowLayout layout;
+    if (int rc = decode_desc(name, d, true, layout)) return rc;
     SG_REQUIRE(d->form == SUBGACC_JOIN_COUNTS && d->options == 0, SUBGACC_ERR_BADARG,
                "%s: form must be COUNTS and options 0 (form %d, options %d)", name, (int)d->form, (int)d->options);
     SG_REQUIRE(d->payload_kind == SUBGACC_JOIN_SFPTR, SUBGACC_ERR_BADARG,
                "%s: the count form joins an SFptr payload (SFPTR), not payload kind %d", name, (int)d->payload_kind);
-    SG_REQUIRE(d->row_off && !d->row_len, SUBGACC_ERR_BADARG, "%s: joins packed rows (row_off set, row_len NULL), not strided or headed rows",
-               name);
-    SG_REQUIRE(pb > 0, SUBGACC_ERR_BADARG, "%s: needs a mirrored list, pair_block > 0 (pair_block = %lld)", name, (long long)pb);
-    SG_REQUIRE(S >= 0 && S % (2 * pb) == 0, SUBGACC_ERR_BADARG,
-               "%s: S = %lld is not a multiple of 2*pair_block = %lld", name, (long long)S, (long long)(2 * pb));
-    SG_REQUIRE(d->own || S == 0, SUBGACC_ERR_BADARG, "%s: own = NULL with S = %lld segments", name, (long long)S);
+    SG_REQUIRE(layout == RowLayout::Packed, SUBGACC_ERR_BADARG,
+               "%s: joins packed rows (row_off set, row_len NULL), not strided or headed rows", name);
     SG_REQUIRE(d->table_rows > 0 && d->table_rows < (1ll << 31), SUBGACC_ERR_BADARG, "%s: table_rows = %lld", name,
                (long long)d->table_rows);
-    SG_REQUIRE(!d->out_xz && !d->out_idx && !d->out_segid && !d->out_counts && !d->out_pairs && !d->out_mult && !d->out_cnt &&
-                   !d->out_seg && !d->seg,
-               SUBGACC_ERR_BADARG, "%s: writes its own outputs only: the descriptor's out_* and seg fields must be NULL", name);
-    SG_REQUIRE(d->n_rows >= 0 && d->max_len >= 0, SUBGACC_ERR_BADARG, "%s: bad arguments", name);
     return SUBGACC_OK;
 }
 
 static int counts_attn_launch(const char *name, const subgacc_join_desc *d, const CountsAttnArgs &c, bool bwd, void *stream) {
     SG_REQUIRE(d->flags && d->ids && d->payload, SUBGACC_ERR_BADARG, "%s: null argument (flags / ids / payload)", name);
-    JoinArgs a;
-    a.indptr = d->row_off, a.indices = d->ids, a.data = d->payload;
-    a.row_len = nullptr, a.row_stride = 0, a.row_head = nullptr;
-    a.pb = d->pair_block, a.own = d->own, a.partner = d->partner, a.seg = nullptr, a.S = d->S, a.n_rows = d->n_rows;
-    a.table = nullptr, a.table_rows = d->table_rows, a.k = 0;
-    a.out_xz = nullptr, a.out_idx = nullptr, a.out_segid = nullptr;
-    a.max_len = d->max_len > 0 ? d->max_len : 1;
-    a.flags = d->flags;
-    a.slot_id = nullptr, a.val_add = 0;
-    a.key_M = a.key_m = a.key_shift = 0;
+    JoinArgs a = join_args(d, RowLayout::Packed);      // (the only layout counts_attn_check admits)
+    a.table_rows = d->table_rows;
     const int64_t dcap = 2 * (int64_t)a.max_len < a.table_rows ? 2 * (int64_t)a.max_len : a.table_rows;   // distinct rows of a block
     const size_t lds = counts_attn_lds(a.max_len, a.table_rows, dcap, bwd);
     SG_REQUIRE(lds <= (size_t)kLdsBytes, SUBGACC_ERR_LDS,
@@ -2715,18 +2653,10 @@ static int counts_attn_launch(const char *name, const subgacc_join_desc *d, cons
     SG_REQUIRE(bwd || !c.out_max || lds_bwd <= (size_t)kLdsBytes, SUBGACC_ERR_LDS,
                "%s: %lld distinct LP rows and rows of %d members: the backward needs %zu B of LDS; use attn_stage (the pair form)", name,
                (long long)a.table_rows, (int)a.max_len, lds_bwd);
-    const void *fn = bwd ? (const void *)sjoin_counts_attn_kernel<true> : (const void *)sjoin_counts_attn_kernel<false>;
-    if (lds > 64 * 1024) SG_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int64_t grid = xcd_grid(d->S / 2);
-    SG_REQUIRE(grid < (1ll << 31), SUBGACC_ERR_BADARG, "%s: too many segments in one call", name);
-    if (bwd)
-        hipLaunchKernelGGL(sjoin_counts_attn_kernel<true>, dim3((unsigned)grid), dim3(kPairThreads), lds, (hipStream_t)stream, a,
-                           d->pair_block, (int32_t)dcap, c);
-    else
-        hipLaunchKernelGGL(sjoin_counts_attn_kernel<false>, dim3((unsigned)grid), dim3(kPairThreads), lds, (hipStream_t)stream, a,
-                           d->pair_block, (int32_t)dcap, c);
-    SG_LAUNCH_CHECK();
-    return SUBGACC_OK;
+    int64_t grid;
+    if (int rc = grid_of(d->S / 2, name, grid)) return rc;
+    return launch(bwd ? sjoin_counts_attn_kernel<true> : sjoin_counts_attn_kernel<false>, grid, kPairThreads, lds, (hipStream_t)stream, a,
+                  d->pair_block, (int32_t)dcap, c);
 }
 
 extern "C" int subgacc_sjoin_counts_attn(const subgacc_join_desc *d, const float *g, float *out_w, float *out_max, float *out_den,
