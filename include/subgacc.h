@@ -459,7 +459,8 @@ int subgacc_sjoin_counts_attn_backward(const subgacc_join_desc *d, const float *
  * partner row or 0 -- and row t's input is E[p_t] + E[q_t] with E = pe_embedding(Z_SF) [T, H].  The input projection folds into the
  * table G = E W_ih^T (f32 [T, 4H'], gate order i, f, g, o as nn.LSTM's) and b = b_ih + b_hh (f32 [4H'], NULL = zero).  Every segment
  * runs exactly L steps from h = c = 0, as the reference's zero padding makes it: step t < n_j takes G[p_t] + G[q_t], steps
- * n_j <= t < L take zero input (an empty segment runs L padded steps).  out_h (f32 [S, H']) receives h_{L-1}.  Per step and element:
+ * n_j <= t < L take zero input (an empty segment runs L padded steps); a segment longer than L runs its first L rows only (n_j =
+ * min(length, L)) and its later rows are ignored.  out_h (f32 [S, H']) receives h_{L-1}.  Per step and element:
  *     a = ((G[p_t] + G[q_t]) + b) as the accumulator's initial value (0 + b on a padded step), then + W_hh[row] . h_{t-1} as an fmaf
  *         chain over k ascending (v_mfma_f32_16x16x4_f32, bit for bit such a chain);
  *     i = 1 / (1 + expf(-a_i)), f, o likewise, g = tanhf(a_g) (accurate expf / tanhf, never the fast intrinsics);
@@ -479,7 +480,8 @@ int subgacc_lstm_aggr(const int32_t *pairs, const int64_t *indptr, int64_t S, in
  *            sums over tiles); inside a tile dW_hh[n][k] is an fmaf chain over t descending and, per step, the tile's segments in the
  *            order 4i + s (MFMA i = 0..3, s = 0..3); db per lane quad over t descending of (((d_0 + d_1) + d_2) + d_3), the 4 quads added
  *            in order.  Padded steps contribute here only.
- *   ws_rows (f32 [R, 4H'], R = indptr[S]): dgates of every real row, in row order.
+ *   ws_rows (f32 [R, 4H'], R = indptr[S]): dgates of every real row, in row order; rows past L of a segment longer than L take no
+ *            step and receive zeros, so dG ignores them as the forward does (every row of ws_rows is written).
  *   out_dg (f32 [T, 4H']): dL/dG[r] = the sum of ws_rows over the 2R index entries (row, side) with index r, in the order `order`
  *            lists them: order (int32 [2R]) holds the row of every entry of a stable sort of the 2R indices; piece_off (int64
  *            [n_pieces + 1]) cuts it into pieces inside one index's run; run_piece (int64 [T + 1]): the pieces of index r are

@@ -186,6 +186,10 @@ __global__ __launch_bounds__(HP / 16 * kWave) void lstm_bwd_kernel(const LstmArg
         const int64_t len = valid[i] ? a.indptr[(seg0 + 4 * quad + i) + 1] - beg[i] : 0;
         n[i] = (int32_t)(len < a.L ? len : a.L);
         dh[i] = valid[i] ? a.dh_last[(seg0 + 4 * quad + i) * HP + col] : 0.0f;
+        // rows past L take no step: zero dgates, so that dG ignores them (no trip when len <= L)
+        for (int64_t t = n[i]; t < len; ++t)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) a.out_drows[(beg[i] + t) * (4 * HP) + g * HP + col] = 0.0f;
     }
     f32x4 accw[4][NB];                          // dW_hh[g H' + 16 wv + 4 quad + i][16 cb + (lane & 15)]
 #pragma unroll

@@ -137,3 +137,41 @@ def _reference_attn_from_xz(xz, ind, nets):
     v = val(x) if val is not None else x
     out = torch.zeros((S, v.shape[-1]), device=g.device, dtype=g.dtype).index_add_(0, seg, alpha[:, None] * v)
     return out.view(2, -1, out.shape[-1])
+
+
+# ------------------------------------- the LP encoder's LSTM aggregation over the index form (index_lstm_stage, subgacc_lstm_aggr)
+def dense_batch(x, ind, L):
+    """to_dense_batch of the rows x [R, H] by segments ind [S+1] into [S, L, H]: zero padding, rows past L dropped; differentiable"""
+    S = ind.numel() - 1
+    lens = ind[1:] - ind[:-1]
+    seg = torch.repeat_interleave(torch.arange(S, device=x.device), lens.to(x.device))
+    pos = torch.arange(x.shape[0], device=x.device) - ind[:-1].to(x.device)[seg]
+    keep = pos < L
+    return x.new_zeros((S, L, x.shape[-1])).index_put((seg[keep], pos[keep]), x[keep])
+
+
+def lstm_steps(G, b, w_hh, pairs, indptr, L):
+    """The folded recurrence of subgacc_lstm_aggr (include/subgacc.h) step by step, vectorised over segments and looped over t only:
+    gates = (G[p_t] + G[q_t]) + b + W_hh h_{t-1} in the gate order i, f, g, o; zero input on the steps n_j <= t < L, n_j = min(length,
+    L).  Every h_t and c_t as [S, L, H'] in G's dtype on G's device, differentiable in G, b (None = zero) and w_hh."""
+    dev = G.device
+    ind = indptr.to(dev, torch.int64)
+    pr = pairs.to(dev, torch.int64).view(-1, 2)
+    S, H2 = ind.numel() - 1, w_hh.shape[1]
+    beg, lens = ind[:-1], ind[1:] - ind[:-1]
+    h, c = G.new_zeros((S, H2)), G.new_zeros((S, H2))
+    hs, cs = [], []
+    for t in range(L):
+        real = (lens > t)[:, None]
+        a = h @ w_hh.t()
+        if pr.shape[0]:
+            r = torch.where(lens > t, beg + t, 0)
+            a = torch.where(real, G[pr[r, 0]] + G[pr[r, 1]], 0.0) + a
+        if b is not None:
+            a = a + b
+        i, f, g, o = a.split(H2, dim=1)
+        c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(g)
+        h = torch.sigmoid(o) * torch.tanh(c)
+        hs.append(h)
+        cs.append(c)
+    return torch.stack(hs, 1), torch.stack(cs, 1)

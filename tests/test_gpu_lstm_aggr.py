@@ -150,11 +150,16 @@ def test_packed_strided_and_key_row_batches_give_the_same_bits(sp):
         _, _, bsets = sp.sample_and_gather(csr, e, num_walks=32, num_steps=3, seed=5, rng="philox", key_rows=kr)
         zs = sp.StridedSpG(bsets, csr.num_nodes)
         forms += [(kr, zs), (kr, zs.to_csr())]
-    idx = [sp.gather_index(rows, f)[0] for _, f in forms]
+    index = [sp.gather_index(rows, f) for _, f in forms]
+    idx = [i for i, _ in index]
     T = max(int(i.max()) for i in idx) + 1
     table = torch.randn((T, 4), device="cuda")
     with torch.no_grad():
         outs = [sp.index_lstm_stage(rows, f, table, *_nets(torch.float32)) for _, f in forms]
+        f64 = _nets(torch.float64)
+        for out, (pairs, ind) in zip(outs, index):              # each form against the float64 reference form of its own rows
+            truth = _reference_style_lstm(table.double()[pairs.long()], ind, *f64).view(2, -1, 16)
+            assert float((out.double() - truth).abs().max()) <= 2e-5 * float(truth.abs().max())
     assert torch.equal(outs[0], outs[1]) and torch.equal(outs[2], outs[3])
     if torch.equal(idx[0], idx[2]):
         assert torch.equal(outs[0], outs[2])
@@ -176,8 +181,9 @@ def test_refusals_on_the_device(sp):
 
 
 def test_a_large_batch_segment_by_segment(sp):
-    """B = 65,536 on a store with long rows, forward under no_grad; 64 sampled segments against a float64 nn.LSTM on [1, L, H] padded
-    to the batch's L (the dense batch is never built)"""
+    """B = 65,536 on a store with long rows, forward under no_grad; 64 sampled segments and those of at least L - 16 rows (the ones
+    whose first rows still reach h_{L-1} under default init) against a float64 nn.LSTM on [1, L, H] padded to the batch's L (the
+    dense batch is never built)"""
     csr, z, table = _store(sp, 20000, 120000, walks=100, seed=13)
     edge = torch.from_numpy(np.random.default_rng(7).integers(0, 20000, (2, 65536))).cuda()
     mlp, lstm = _nets(torch.float32, 32, 32)
@@ -188,7 +194,9 @@ def test_a_large_batch_segment_by_segment(sp):
         assert L > 100
         m64, l64 = _nets(torch.float64, 32, 32)
         E = m64(table.double())
-        for j in np.random.default_rng(8).choice(2 * 65536, 64, replace=False):
+        longs = torch.nonzero(ind[1:] - ind[:-1] >= L - 16).view(-1).cpu().numpy()[:64]
+        assert longs.size
+        for j in np.union1d(np.random.default_rng(8).choice(2 * 65536, 64, replace=False), longs):
             p = pairs[int(ind[j]):int(ind[j + 1])].long()
             x = torch.zeros((1, L, 32), dtype=torch.float64, device="cuda")
             x[0, :p.shape[0]] = E[p[:, 0]] + E[p[:, 1]]

@@ -209,3 +209,72 @@ def test_table_folded_recurrence_equals_nn_lstm_on_the_padded_batch(golden, bias
             h = o * np.tanh(c)
         out[j] = h
     np.testing.assert_allclose(out, truth, rtol=0, atol=1e-12)
+
+
+# ----------------------------------------------------------------- the step reference the GPU tests compare against, pinned
+@pytest.mark.parametrize("bias,forget,pad", [(True, 0.0, 0), (True, 5.0, 0), (False, 0.0, 6), (True, 0.0, 7)])
+def test_step_reference_equals_nn_lstm_on_the_padded_batch(bias, forget, pad):
+    """gpu_helpers.lstm_steps over the index form equals float64 nn.LSTM on the zero-padded dense batch of G rows: the whole h trajectory
+    and the final c within 1e-12, with segments of 0, 1 and L rows, L past the longest segment, and a long-memory forget bias"""
+    from gpu_helpers import dense_batch, lstm_steps
+    rng = np.random.default_rng(int(forget) + pad)
+    lens = np.array([0, 1, 23, 5, 0, 17, 23, 2, 9, 11, 1, 20, 3])
+    T, H, H2 = 9, 6, 16
+    L = int(lens.max()) + pad
+    indptr = torch.from_numpy(np.concatenate([[0], np.cumsum(lens)]))
+    pairs = torch.from_numpy(rng.integers(0, T, (int(indptr[-1]), 2)).astype(np.int32))
+    torch.manual_seed(3)
+    lstm = torch.nn.LSTM(H, H2, batch_first=True, bias=bias).double()
+    E = torch.randn((T, H), dtype=torch.float64)
+    with torch.no_grad():
+        if bias:
+            lstm.bias_hh_l0[H2:2 * H2] += forget
+        dense = dense_batch(E[pairs[:, 0].long()] + E[pairs[:, 1].long()], indptr, L)
+        out, (_, c_n) = lstm(dense)
+        G = E @ lstm.weight_ih_l0.t()
+        b = (lstm.bias_ih_l0 + lstm.bias_hh_l0) if bias else None
+        hs, cs = lstm_steps(G, b, lstm.weight_hh_l0, pairs, indptr, L)
+    assert hs.shape == cs.shape == (len(lens), L, H2)
+    torch.testing.assert_close(hs, out, rtol=0, atol=1e-12)
+    torch.testing.assert_close(cs[:, -1], c_n[0], rtol=0, atol=1e-12)
+
+
+def test_step_reference_runs_l_steps_of_a_longer_segment():
+    """a segment longer than L runs its first L rows: the same trajectory as the segment cut to L rows"""
+    from gpu_helpers import lstm_steps
+    rng = np.random.default_rng(1)
+    G, w, b = torch.from_numpy(rng.standard_normal((5, 32))), torch.from_numpy(rng.standard_normal((32, 8))) / 4, None
+    pairs = torch.from_numpy(rng.integers(0, 5, (30, 2)).astype(np.int32))
+    full = lstm_steps(G, b, w, pairs, torch.tensor([0, 12, 30]), 10)
+    cut = lstm_steps(G, b, w, torch.cat([pairs[:10], pairs[12:22]]), torch.tensor([0, 10, 20]), 10)
+    assert all(torch.equal(a, c) for a, c in zip(full, cut))
+
+
+# ------------------------------------------------------------------------------------ dG's ordered sum: grouping()'s pieces
+@pytest.mark.parametrize("counts", [(1, 1023, 1024, 1025, 2048, 2049, 3073), (2200,), (0, 1024, 0, 1)])
+def test_grouping_cuts_every_index_run_into_pieces_of_at_most_1024_in_order(counts):
+    """order lists the row of every (row, side) entry of a stable sort of the 2R indices; pieces cover it in sequence, each inside one
+    index's run, every piece but an index's last full (1024 entries), ceil(count / 1024) pieces per index, run_piece their ranges"""
+    from surel_plus_amd.spjoin import _LSTM_PIECE, _LstmJoin
+    assert _LSTM_PIECE == 1024
+    T = len(counts) + 2                                       # the first and the last index are used by no entry
+    flat = np.concatenate([np.full(c, 1 + i) for i, c in enumerate(counts)])
+    flat = np.random.default_rng(len(flat)).permutation(np.concatenate([flat, np.ones(len(flat) % 2, flat.dtype)]))
+    cnt = np.bincount(flat, minlength=T)
+    pairs = torch.from_numpy(flat.reshape(-1, 2).astype(np.int32))
+    join = _LstmJoin(pairs, torch.tensor([0, pairs.shape[0]]), 1, T, 16)
+    order, piece_off, P, run_piece = (v.numpy() if torch.is_tensor(v) else v for v in join.grouping())
+    perm = np.argsort(flat, kind="stable")
+    np.testing.assert_array_equal(order, perm // 2)
+    start = np.concatenate([[0], np.cumsum(cnt)])
+    npc = -(-cnt // 1024)
+    assert P == npc.sum() and len(piece_off) == P + 1 and piece_off[0] == 0 and piece_off[-1] == len(flat)
+    np.testing.assert_array_equal(run_piece, np.concatenate([[0], np.cumsum(npc)]))
+    for r in range(T):
+        cuts = piece_off[run_piece[r]:run_piece[r + 1] + 1]
+        if cnt[r] == 0:
+            assert run_piece[r] == run_piece[r + 1]
+            continue
+        assert cuts[0] == start[r] and cuts[-1] == start[r + 1]
+        np.testing.assert_array_equal(cuts[:-1], start[r] + 1024 * np.arange(npc[r]))
+        assert np.all(np.diff(cuts) >= 1) and np.all(np.diff(cuts) <= 1024)
