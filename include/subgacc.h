@@ -495,6 +495,45 @@ int subgacc_lstm_aggr_backward(const int32_t *pairs, const int64_t *indptr, int6
                                float *ws_rows, float *ws_pieces, float *out_dg, float *out_dw, float *out_db, int32_t *flags,
                                void *stream);
 
+/* The float encoders' (PPR / SPD / DEG) first stage with LSTM aggregation in the same recurrent kernel (ABI 7, backward compatible
+ * additions).  A row of the float join is a pair of scalars (a_t, b_t) -- own score, partner's score or 0 -- and pe_embedding =
+ * Linear(1, H), ReLU, Linear(H, H1), so with V = W_ih W2 the input projection is  F(a_t) + F(b_t) + c_real,  F(s) = V relu(w1 s + b1):
+ * a piecewise-linear function of ONE scalar.  Over the H knots -b1/w1 sorted ascending, F(s) = P[k] s + Q[k] in interval k of K = 2H + 1:
+ * with r = the number of knots <= s (torch.bucketize, right=True), k = 2r in the open interval behind r knots and k = 2r - 1 ON a knot,
+ * where that knot's channels count as off (F is continuous there; the gradients then take relu'(0) = 0 as torch does).  The caller
+ * builds idx, P and Q by this one rule.  vals (f32 [R, 2]) holds (a_t, b_t), idx (int32 [R, 2]) their intervals,
+ * tab (f32 [K, 4H', 2]) the pairs (P[k][n], Q[k][n]) interleaved, c_real = b_ih + b_hh + 2 W_ih b2 and c_pad = b_ih + b_hh (f32 [4H']
+ * each, NULL = zero); vals, idx and tab on 8-byte boundaries.  Segments, L, padding, out_h, h_state / c_state, the MFMA chain over W_hh
+ * and the cell update are those of subgacc_lstm_aggr; only the accumulator's initial value differs, per step and element:
+ *     a = (fmaf(P[ka], a_t, Q[ka]) + fmaf(P[kb], b_t, Q[kb])) + c_real   on a real step,   a = 0 + c_pad   on a padded step.
+ * A segment's bits depend only on its own rows, L and the tables: not on its tile-mates, the pair order or packed against headed rows.
+ * An interval outside [0, K) reads row 0 and sets flags[3] |= 2; nothing is read out of bounds.
+ * Refused with SUBGACC_ERR_BADARG before anything is launched: vals / idx / indptr / tab / w_hh / out_h / flags NULL, vals / idx / tab
+ * off an 8-byte boundary, S < 0, L < 1 with S > 0, H' not a multiple of 16 or outside [16, 128], K outside [1, 2^22] (the table is addressed with 32-bit
+ * offsets), exactly one of h_state / c_state. */
+int subgacc_lstm_aggr_hinge(const float *vals, const int32_t *idx, const int64_t *indptr, int64_t S, int32_t L, int64_t K, int32_t H,
+                            const float *tab, const float *c_real, const float *c_pad, const float *w_hh, float *out_h, float *h_state,
+                            float *c_state, int32_t *flags, void *stream);
+
+/* The backward of subgacc_lstm_aggr_hinge: BPTT as subgacc_lstm_aggr_backward runs it (gates recomputed bit for bit, out_dw and
+ * ws_rows as there).  What differs, still without a float added atomically:
+ *   out_dc_real / out_dc_pad (f32 [ceil(S/16), 4H'] each): the bias partials of a tile kept apart -- the dgates of real steps in
+ *            out_dc_real, those of padded steps in out_dc_pad (they reach different parameters), each summed as out_db is, a step
+ *            that belongs to the other sum adding 0.
+ *   out_dp / out_dq (f32 [K, 4H'] each): dL/dP[k] = sum of ws_rows[row] * vals[row][side] and dL/dQ[k] = sum of ws_rows[row] over the 2R
+ *            entries (row, side) with idx = k, in the order `order` lists them: order (int32 [2R]) holds the ENTRY 2 row + side of a
+ *            stable sort of the 2R intervals (R < 2^30), piece_off / run_piece cut it as in subgacc_lstm_aggr_backward (K in T's place).
+ *            Each piece is summed from 0 in order -- dP as the chain fmaf(d, val, .), dQ as plain adds -- into ws_pieces (f32
+ *            [2, n_pieces, 4H']: dP's pieces, then dQ's), then each interval's pieces are summed from 0 in order.
+ * Flags and refusals as the forward's; h_state, c_state, dh, order, piece_off, run_piece, ws_rows, out_dp, out_dq, out_dw, out_dc_real
+ * and out_dc_pad are required, ws_pieces when n_pieces > 0; n_pieces outside [0, 2^31) is refused. */
+int subgacc_lstm_aggr_hinge_backward(const float *vals, const int32_t *idx, const int64_t *indptr, int64_t S, int32_t L, int64_t K,
+                                     int32_t H, const float *tab, const float *c_real, const float *c_pad, const float *w_hh,
+                                     const float *h_state, const float *c_state, const float *dh, const int32_t *order,
+                                     const int64_t *piece_off, int64_t n_pieces, const int64_t *run_piece, float *ws_rows,
+                                     float *ws_pieces, float *out_dp, float *out_dq, float *out_dw, float *out_dc_real,
+                                     float *out_dc_pad, int32_t *flags, void *stream);
+
 
 /* Packed rows -> headed rows (ABI 7): the resident store of a serving loop laid out on whole lines -- the rows random_walks.py:79-81
  * builds as a SciPy CSR and train.py:17-18 / :39-43 slice one by one (x[edge[0]]), in the layout the pair kernels read with one

@@ -38,7 +38,7 @@ SYMBOLS = (
     "subgacc_locality_round", "subgacc_worklist_by_rank",
     "subgacc_sjoin_fill_v2", "subgacc_publish_words", "subgacc_rows_to_headed", "subgacc_sjoin_star_sizes", "subgacc_sjoin_relu_mean",
     "subgacc_sjoin_relu_attn", "subgacc_sjoin_relu_attn_backward", "subgacc_sjoin_counts_attn", "subgacc_sjoin_counts_attn_backward",
-    "subgacc_lstm_aggr", "subgacc_lstm_aggr_backward",
+    "subgacc_lstm_aggr", "subgacc_lstm_aggr_backward", "subgacc_lstm_aggr_hinge", "subgacc_lstm_aggr_hinge_backward",
 )
 
 
@@ -168,6 +168,9 @@ def lib():
     sig["subgacc_lstm_aggr"] = (C.c_int, [vp, vp, i64, i32, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp])
     sig["subgacc_lstm_aggr_backward"] = (C.c_int, [vp, vp, i64, i32, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp,
                                                    vp, vp, vp])
+    sig["subgacc_lstm_aggr_hinge"] = (C.c_int, [vp, vp, vp, i64, i32, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp])
+    sig["subgacc_lstm_aggr_hinge_backward"] = (C.c_int, [vp, vp, vp, i64, i32, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp,
+                                                         vp, vp, vp, vp, vp, vp, vp, vp])
     assert set(sig) == set(SYMBOLS)
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -1329,10 +1329,9 @@ LSTM_WIDTHS = tuple(range(16, 129, 16))     # H' the recurrent kernel takes (inc
 _LSTM_PIECE = 1024                           # entries of one piece of dG's ordered sum (a table row's run is cut into such pieces)
 
 
-def _lstm_layer(lstm, dev, name="index_lstm_stage"):
+def _lstm_layer(lstm, dev, name="index_lstm_stage", other="lstm_stage(edge, x, encode, embed, lstm)"):
     """(W_ih, W_hh, b_ih, b_hh) of a one-layer, unidirectional, batch_first, proj_size = 0, float32 nn.LSTM on `dev`, or TypeError /
-    ValueError naming lstm_stage as the general path"""
-    other = "lstm_stage(edge, x, encode, embed, lstm)"
+    ValueError naming `other` (lstm_stage) as the general path"""
     if not isinstance(lstm, torch.nn.LSTM):
         raise TypeError(f"{name} fuses a torch.nn.LSTM only, not {type(lstm).__name__}; for any other module use {other}")
     if lstm.num_layers != 1 or lstm.bidirectional or not lstm.batch_first or getattr(lstm, "proj_size", 0) != 0:
@@ -1351,6 +1350,28 @@ def _lstm_layer(lstm, dev, name="index_lstm_stage"):
 def _nonnull(t):
     """t, or one element of its dtype when t is empty (the library takes no NULL for an array it is told holds nothing)"""
     return t if t.numel() else torch.zeros(1, dtype=t.dtype, device=t.device)
+
+
+def _sorted_pieces(pairs, T):
+    """The ordered sums of the LSTM backwards (dG; dP / dQ): (perm, piece_off, P, run_piece) -- perm int64 [2R], the entries 2 row + side
+    of `pairs` (int32 [R, 2], values in [0, T)) in a stable sort by value; piece_off int64 [P + 1] cuts perm into P pieces of at most
+    _LSTM_PIECE entries, each inside one value's run; run_piece int64 [T + 1]: the pieces of value r are [run_piece[r], run_piece[r+1])"""
+    dev = pairs.device
+    idx = pairs.view(-1).long()
+    srt, perm = torch.sort(idx, stable=True)
+    cnt = torch.bincount(idx, minlength=T)
+    start = torch.zeros(T + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(cnt, 0, out=start[1:])
+    npc = (cnt + _LSTM_PIECE - 1) // _LSTM_PIECE
+    run_piece = torch.zeros(T + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(npc, 0, out=run_piece[1:])
+    P = int(run_piece[-1].item())
+    owner = torch.repeat_interleave(torch.arange(T, device=dev), npc, output_size=P)
+    k = torch.arange(P, device=dev) - run_piece[:-1][owner]
+    piece_off = torch.empty(P + 1, dtype=torch.int64, device=dev)
+    piece_off[:-1] = start[:-1][owner] + k * _LSTM_PIECE
+    piece_off[-1] = idx.numel()
+    return perm, piece_off.contiguous(), P, run_piece
 
 
 class _LstmJoin:
@@ -1379,22 +1400,8 @@ class _LstmJoin:
     def grouping(self):
         """dG's ordered sum: the row of every index entry in a stable sort of the 2R indices, cut into pieces of at most _LSTM_PIECE
         entries inside one index's run, and the pieces of every index"""
-        idx = self.pairs.view(-1).long()
-        srt, perm = torch.sort(idx, stable=True)
-        order = (perm // 2).to(torch.int32)
-        cnt = torch.bincount(idx, minlength=self.T)
-        start = torch.zeros(self.T + 1, dtype=torch.int64, device=self.dev)
-        torch.cumsum(cnt, 0, out=start[1:])
-        npc = (cnt + _LSTM_PIECE - 1) // _LSTM_PIECE
-        run_piece = torch.zeros(self.T + 1, dtype=torch.int64, device=self.dev)
-        torch.cumsum(npc, 0, out=run_piece[1:])
-        P = int(run_piece[-1].item())
-        owner = torch.repeat_interleave(torch.arange(self.T, device=self.dev), npc, output_size=P)
-        k = torch.arange(P, device=self.dev) - run_piece[:-1][owner]
-        piece_off = torch.empty(P + 1, dtype=torch.int64, device=self.dev)
-        piece_off[:-1] = start[:-1][owner] + k * _LSTM_PIECE
-        piece_off[-1] = idx.numel()
-        return order, piece_off.contiguous(), P, run_piece
+        perm, piece_off, P, run_piece = _sorted_pieces(self.pairs, self.T)
+        return (perm // 2).to(torch.int32), piece_off, P, run_piece
 
     def backward(self, G, b, w_hh, hs, cs, dh):
         S, H2, dev = self.S, self.H2, self.dev
@@ -1455,8 +1462,8 @@ def index_lstm_stage(edge, x, encode, embed, lstm):
     if not isinstance(x, (SpG, StridedSpG)):
         raise TypeError(f"{name} joins an integer (LP) SpG or StridedSpG, not {type(x).__name__}")
     if isinstance(x, SpG) and not x.keyrows and x.data.dtype != torch.int32:
-        raise TypeError(f"{name} joins an integer (LP) store; a float (PPR / SPD / DEG) store has no fused LSTM stage: use "
-                        "lstm_stage(edge, x, encode, embed, lstm) on its gather()")
+        raise TypeError(f"{name} joins an integer (LP) store; a float (PPR / SPD / DEG) store has "
+                        "float_lstm_stage(edge, x, embed, lstm)")
     dev = x.device
     w_ih, w_hh, b_ih, b_hh = _lstm_layer(lstm, dev, name)
     H2 = lstm.hidden_size
@@ -1496,4 +1503,174 @@ def index_lstm_stage(edge, x, encode, embed, lstm):
         join.checked()
     out = h.view(2, -1, H2)
     out.join_flags = join.flags
+    return out
+
+
+def hinge_tables(lin1, lin2, w_ih, b_ih=None, b_hh=None):
+    """The LSTM's input projection over a float store as a table of one scalar.  With pe_embedding = (lin1 = Linear(1, H), ReLU, lin2 =
+    Linear(H, H1)) and V = W_ih W2 ([4H', H]):  W_ih x_t + b_ih + b_hh = F(a_t) + F(b_t) + c_real,  F(s) = V relu(w1 s + b1), and F is
+    piecewise linear with the knots -b1[c] / w1[c].  Returns (knots, P, Q, c_real, c_pad):
+        knots [H] sorted ascending (+inf for a channel with w1 = 0); k(s) = hinge_intervals(s, knots) in [0, 2H]: 2r in the open
+            interval behind r knots, 2r - 1 ON a knot (r = the number of knots <= s);
+        P = (A * w1) V^T, Q = (A * b1) V^T  ([2H+1, 4H']): F(s) = P[k(s)] s + Q[k(s)], A [2H+1, H] the 0/1 activity of every channel in
+            every interval (w1 > 0: active above its knot; w1 < 0: active below its knot; w1 = 0: everywhere iff b1 > 0; on its own
+            knot a channel is off, so the gradients take relu'(0) = 0 as torch does -- F itself is continuous there);
+        c_pad = b_ih + b_hh (a padded step: zero input), c_real = c_pad + 2 W_ih b2; None where every term is absent.
+    knots and A are constants of autograd; P, Q, c_real, c_pad are torch products of the parameters, so their gradients reach w1, b1, W2,
+    b2, W_ih, b_ih and b_hh.  Pure torch, any dtype and device."""
+    w1 = lin1.weight.view(-1)
+    b1 = lin1.bias if lin1.bias is not None else torch.zeros_like(w1)
+    V = w_ih @ lin2.weight
+    with torch.no_grad():
+        inf = torch.full_like(w1, float("inf"))
+        knot = torch.where(w1 != 0, -b1 / torch.where(w1 != 0, w1, torch.ones_like(w1)), inf)
+        knots, _ = torch.sort(knot)
+        lo = torch.cat([-inf[:1], knots])                   # [H+1] the ends of the open interval behind r knots: lo[r] < s < hi[r]
+        hi = torch.cat([knots, inf[:1]])
+        up, down, const = (w1 > 0)[None, :], (w1 < 0)[None, :], ((w1 == 0) & (b1 > 0))[None, :]
+        A = torch.empty((2 * w1.numel() + 1, w1.numel()), dtype=w1.dtype, device=w1.device)
+        A[0::2] = ((up & (knot[None, :] <= lo[:, None])) | (down & (knot[None, :] >= hi[:, None])) | const).to(w1.dtype)
+        # on a knot the channels of that knot are off, as relu'(0) = 0 has it
+        A[1::2] = ((up & (knot[None, :] < knots[:, None])) | (down & (knot[None, :] > knots[:, None])) | const).to(w1.dtype)
+    P = (A * w1) @ V.t()
+    Q = (A * b1) @ V.t()
+    c_pad = (b_ih + b_hh) if b_ih is not None else None
+    c_real = c_pad
+    if lin2.bias is not None:
+        c2 = w_ih @ (2 * lin2.bias)
+        c_real = c2 if c_pad is None else c_pad + c2
+    return knots, P, Q, c_real, c_pad
+
+
+def hinge_intervals(s, knots):
+    """k(s) of hinge_tables: 2r in the open interval behind r knots, 2r - 1 on a knot, r = the number of knots <= s (int64, in [0, 2H])"""
+    s = s.contiguous()
+    r = torch.bucketize(s, knots, right=True)
+    return 2 * r - (r > torch.bucketize(s, knots, right=False)).to(r.dtype)
+
+
+class _HingeJoin:
+    """the two library calls of float_lstm_stage over one batch's float join (vals [R, 2], their intervals idx, indptr) padded to L steps"""
+
+    def __init__(self, vals, idx, indptr, L, K, H2, flags):
+        self.vals, self.idx, self.indptr, self.L, self.K, self.H2, self.flags = vals, idx, indptr, L, K, H2, flags
+        self.S = indptr.numel() - 1
+        self.dev = indptr.device
+
+    def checked(self):
+        if int(self.flags[3].item()) & 2:
+            raise IndexError(f"an interval of the join is out of bounds for the table with {self.K} rows")
+
+    def forward(self, tab, c_real, c_pad, w_hh, keep):
+        S, L, H2, dev = self.S, self.L, self.H2, self.dev
+        h = torch.empty((S, H2), dtype=torch.float32, device=dev)
+        hs, cs = (torch.empty((S, L, H2), dtype=torch.float32, device=dev), torch.empty((S, L, H2), dtype=torch.float32, device=dev)) \
+            if keep else (None, None)
+        with _timed("lstm_aggr_hinge"):
+            check(lib().subgacc_lstm_aggr_hinge(ptr(_nonnull(self.vals)), ptr(_nonnull(self.idx)), ptr(self.indptr), S, L, self.K, H2,
+                                                ptr(tab), ptr(c_real), ptr(c_pad), ptr(w_hh), ptr(h), ptr(hs), ptr(cs), ptr(self.flags),
+                                                stream_ptr()))
+        return h, hs, cs
+
+    def backward(self, tab, c_real, c_pad, w_hh, hs, cs, dh):
+        S, H2, K, dev = self.S, self.H2, self.K, self.dev
+        tiles = (S + 15) // 16
+        R = self.idx.shape[0]
+        perm, piece_off, P, run_piece = _sorted_pieces(self.idx, K)
+        order = perm.to(torch.int32)
+        rows = torch.empty((R, 4 * H2), dtype=torch.float32, device=dev)
+        pieces = torch.empty((2, P, 4 * H2), dtype=torch.float32, device=dev) if P else None
+        dP, dQ = (torch.empty((K, 4 * H2), dtype=torch.float32, device=dev) for _ in range(2))
+        dw = torch.empty((tiles, 4 * H2, H2), dtype=torch.float32, device=dev)
+        dcr, dcp = (torch.empty((tiles, 4 * H2), dtype=torch.float32, device=dev) for _ in range(2))
+        with _timed("lstm_aggr_hinge_backward"):
+            check(lib().subgacc_lstm_aggr_hinge_backward(
+                ptr(_nonnull(self.vals)), ptr(_nonnull(self.idx)), ptr(self.indptr), S, self.L, K, H2, ptr(tab), ptr(c_real), ptr(c_pad),
+                ptr(w_hh), ptr(hs), ptr(cs), ptr(dh), ptr(_nonnull(order)), ptr(piece_off), P, ptr(run_piece), ptr(_nonnull(rows)),
+                ptr(pieces), ptr(dP), ptr(dQ), ptr(dw), ptr(dcr), ptr(dcp), ptr(self.flags), stream_ptr()))
+        return torch.stack([dP, dQ], dim=-1), dcr.sum(0), dcp.sum(0), dw.sum(0)
+
+
+class _HingeLstm(torch.autograd.Function):
+    """h_{L-1} [S, H'] of subgacc_lstm_aggr_hinge as a function of (tab, c_real, c_pad, W_hh); backward: subgacc_lstm_aggr_hinge_backward's
+    dP / dQ (interleaved as tab is) and the sums over tiles of its dW_hh, dc_real and dc_pad partials"""
+
+    @staticmethod
+    def forward(ctx, tab, c_real, c_pad, w_hh, join):
+        ctx.join = join
+        ctx.has = (c_real is not None, c_pad is not None)
+        tab, w_hh = tab.detach().contiguous(), w_hh.detach().contiguous()
+        c_real = c_real.detach().contiguous() if c_real is not None else None
+        c_pad = c_pad.detach().contiguous() if c_pad is not None else None
+        h, hs, cs = join.forward(tab, c_real, c_pad, w_hh, True)
+        ctx.save_for_backward(tab, c_real, c_pad, w_hh, hs, cs)
+        return h
+
+    @staticmethod
+    def backward(ctx, dh):
+        tab, c_real, c_pad, w_hh, hs, cs = ctx.saved_tensors
+        dtab, dcr, dcp, dw = ctx.join.backward(tab, c_real if ctx.has[0] else None, c_pad if ctx.has[1] else None, w_hh, hs, cs,
+                                               dh.contiguous())
+        return dtab, (dcr if ctx.has[0] else None), (dcp if ctx.has[1] else None), dw, None
+
+
+def float_lstm_stage(edge, x, embed, lstm):
+    """The reference's first model stage for the float encoders (PPR, SPD, DEG) with --aggr lstm, in the recurrent kernel of
+    index_lstm_stage:  model.py:63-65,78-83
+        x = pe_embedding(xz).sum(dim=-2);  xl, xr = LSTMAggregation(H1, H')(x, index=ptr).view(2, -1, H')
+    with pe_embedding = embed = Sequential(Linear(1, H), ReLU(), Linear(H, H1)) over the float join's xz [R,2,1], every segment padded
+    with zero rows to the batch's longest (L = max(longest, 1)) and the output taken at position L-1.  A row is a pair of scalars (a, b),
+    and W_ih x_t = F(a) + F(b) + const with F(s) = W_ih W2 relu(w1 s + b1) piecewise linear in one scalar: hinge_tables() turns the
+    parameters into P, Q [2H+1, 4H'] with F(s) = P[k(s)] s + Q[k(s)], and the library's kernel (subgacc_lstm_aggr_hinge) runs
+        gates_t = ((P[ka] a + Q[ka]) + (P[kb] b + Q[kb])) + c_real + W_hh h_{t-1}   (c_pad + W_hh h_{t-1} on a padded step)
+    on the MFMA -- neither the [R,2,H] activations, nor the dense [S, L, H1] batch, nor the LSTM's [S, L, H'] output exist.  The rows
+    come from the float join (gather: xz float32 [R,2,1] and indptr, 8 bytes per row).  Under autograd the forward keeps h_t, c_t
+    (8 S L H' bytes) and the backward (subgacc_lstm_aggr_hinge_backward) takes a [R, 4H'] workspace (16 R H' bytes) and returns dP, dQ,
+    dc_real, dc_pad and dW_hh; torch carries them into every parameter of embed and lstm.  At B = 65,536 over a top-100 store with
+    H' = 96 that is about 10 GB + 18 GB (derived, not measured).  With grad disabled (or nothing requiring it) no state is kept and the
+    forward's bits are the same.  No float is added atomically: repeated runs give the same bits, and a segment's result does not
+    depend on the other segments, the order of the pairs or the store layout.
+    edge: [2, B] integer (torch or NumPy); x: a float64 SpG or HeadedSpG; lstm: a one-layer, unidirectional, batch_first, proj_size = 0,
+    float32 nn.LSTM on the store's device with input_size = H1 and hidden_size in 16, 32, .., 128.  Returns float32 [2, B, H'] (left
+    endpoints, right endpoints) with the join's status words as .join_flags.  There is no general float path behind this one: anything
+    else is written by hand as xz, ind = gather(edge, x) and the modules on xz."""
+    name = "float_lstm_stage"
+    other = "xz, ind = gather(edge, x) and the modules on xz"
+    st = _FloatStage(name, "index_lstm_stage(edge, x, encode, embed, lstm)", edge, x, embed)
+    w_ih, w_hh, b_ih, b_hh = _lstm_layer(lstm, st.dev, name, other)
+    H1, H2 = st.lin2.out_features, lstm.hidden_size
+    if lstm.input_size != H1:
+        raise ValueError(f"{name}: embed gives rows of {H1}, the LSTM takes rows of {lstm.input_size}; otherwise use {other}")
+    dev = st.dev
+    e = _as_rows(st.edge, dev)
+    B = int(e.shape[1])
+    own = e.contiguous().view(-1)
+    if B and bool(((own < 0) | (own >= x.n_rows)).any()):
+        raise IndexError(f"row index out of range for an SpG with {x.n_rows} rows")
+    st.join_on()
+    if B == 0 or not bool(st.nonempty().any()):     # no rows at all (the join asks for none): L = 1 padded step per segment
+        xz, indptr = torch.zeros((0, 2, 1), dtype=torch.float32, device=dev), torch.zeros(2 * B + 1, dtype=torch.int64, device=dev)
+        flags = st.flags
+    else:
+        xz, indptr, flags = sjoin(x, own, None, None, ptr_mode=True, pair_block=B)
+    S = 2 * B
+    if xz.shape[0] >= 1 << 30:
+        raise ValueError(f"{name}: {xz.shape[0]} rows in one batch; the ordered sums index 2R entries with 32 bits")
+    L = max(int((indptr[1:] - indptr[:-1]).max().item()), 1) if S else 1
+    knots, P, Q, c_real, c_pad = hinge_tables(st.lin1, st.lin2, w_ih, b_ih, b_hh)
+    vals = xz.reshape(-1, 2).contiguous()
+    idx = hinge_intervals(vals, knots).to(torch.int32)
+    tab = torch.stack([P, Q], dim=-1)
+    join = _HingeJoin(vals, idx, indptr.contiguous(), L, 2 * st.H + 1, H2, flags)
+    if S == 0:
+        h = tab.new_zeros((0, H2))
+    elif torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (tab, c_real, c_pad, w_hh)):
+        h = _HingeLstm.apply(tab, c_real, c_pad, w_hh, join)
+    else:
+        h = join.forward(tab.detach().contiguous(), c_real.detach().contiguous() if c_real is not None else None,
+                         c_pad.detach().contiguous() if c_pad is not None else None, w_hh.detach().contiguous(), False)[0]
+    if S:
+        join.checked()
+    out = h.view(2, -1, H2)
+    out.join_flags = flags
     return out
