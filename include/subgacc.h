@@ -289,7 +289,9 @@ int subgacc_sjoin_star_sizes(const int64_t *spg_indptr, int64_t n_rows, const in
  *              there (flags[3] |= 4 if the list is not mirrored like that); `partner` may then be NULL.  Strided rows, keys, the count
  *              and the pair form: mirrored lists only
  *   form       SUBGACC_JOIN_ROWS   out_xz f32 [R,2,k] and / or out_idx i32 [R,2] (the raw index pairs, SFPTR only), out_segid i64 [R]
- *                                  (segment id of every row, `ptr=False`, train.py:25-30; optional; not with strided rows)
+ *                                  (segment id of every row: `ptr=False`, train.py:25-30, and always for hgather's triplets,
+ *                                  train.py:57-59; optional; every row layout and payload, the strided rows of an on-demand step --
+ *                                  table slots, KEY32, KEY64 -- included: a row's id leaves with the span that carries the row)
  *              SUBGACC_JOIN_COUNTS out_counts f32 [S, table_rows]: how often LP row p (SFptr+1, 0 = partner absent) occurs in either
  *                                  feature slot of segment j, so that segment_sum_j(MLP(xz).sum(-2)) == out_counts[j] @ MLP(Z_SF)
  *                                  (model.py:78-83); 8*max_len + 8*table_rows + 16 bytes of LDS <= 160 KiB (SUBGACC_ERR_LDS)
@@ -665,6 +667,24 @@ size_t subgacc_step_dedup_workspace_bytes(int64_t n);
 int subgacc_step_prologue_dedup(void *uniq_table, int64_t capacity, int64_t *zero_words, int64_t n_zero, const int64_t *edge,
                                 int32_t *roots, int64_t *own, int64_t *partner, int32_t *worklist, int32_t *row_len, int64_t n,
                                 void *workspace, size_t workspace_bytes, int64_t *n_distinct, void *stream);
+/* The dedup prologue for a step whose roots play ROLES: the n = r*B roots `edge` come in r blocks of B and the segment list has s
+ * blocks of B, each reading one root block.  r = 3, s = 4: the triplets (u, v, w) of the higher-order model, edge = [u.. | v.. | w..],
+ * segment blocks u, w, v, w -- hgather's [U|w ; W|u ; V|w ; W|v] (train.py:48-72), whose negatives keep (u, v) of their positive and
+ * replace w (dataloader.py:265-268, 275: two of the three roots of every negative are repeats).  r = 2, s = 2: gather's pairs, blocks
+ * u, v (train.py:13-23).  Written: roots, worklist, row_len and n_distinct as by subgacc_step_prologue_dedup -- first occurrence is
+ * over the WHOLE root list, so a node that is u of one triplet and w of another is walked once -- and
+ *   own         int64 [s*B]: own[b*B + t] = the row of the first occurrence of the root that segment t of block b reads
+ * No partner list: the segment list is mirrored (pair_block = B: block 2t+1 mirrors block 2t), subgacc_sjoin_sizes_rows and
+ * subgacc_sjoin_fill_v2 take partner = NULL.  workspace: subgacc_step_dedup_workspace_bytes(n) bytes, zeroed once, as above.
+ * Refused before anything is launched, with a message that starts with "step_prologue_dedup_roles: ": a NULL argument
+ * (SUBGACC_ERR_BADARG; uniq_table may be NULL: key rows), (r, s) other than (2, 2) and (3, 4), B <= 0, n != r*B or n >= 2^30, a
+ * workspace that is too small (SUBGACC_ERR_WORKSPACE).
+ * (The plain triplet step needs no entry point of its own: subgacc_step_prologue with n = 3B, and own = [0..B | 2B..3B | B..2B |
+ * 2B..3B) is a constant of B.) */
+int subgacc_step_prologue_dedup_roles(void *uniq_table, int64_t capacity, int64_t *zero_words, int64_t n_zero, const int64_t *edge,
+                                      int32_t *roots, int64_t *own, int32_t *worklist, int32_t *row_len, int64_t n, int64_t B,
+                                      int32_t r, int32_t s, void *workspace, size_t workspace_bytes, int64_t *n_distinct,
+                                      void *stream);
 /* subgacc_walk_spg over some of the rows only: the rows worklist[0 .. *n_work) (both on the device; the launch covers n rows,
  * blocks past the list's length leave at once), or -- worklist = n_work = NULL -- every row i whose query[i] is not
  * SUBGACC_NO_ROOT (such a row gets nsize[i] = 0 and nothing else is touched; rows that are not on the work list are not touched

@@ -9,8 +9,8 @@ Host mirror of the reference's interfaces over a C-ABI HIP library (include/subg
 from ._lib import SubgAccError, build  # noqa: F401
 from .sampler import DeviceCSR, LocalityOrder, SampledSets, locality_order, sample_sets  # noqa: F401
 from .spg import HeadedSpG, SpG, StridedSpG, np_sampling, rw_matrix, sample_spg, subg_matrix  # noqa: F401
-from .spjoin import (attn_stage, bgather, counts_attn_stage, gather, gather_counts, gather_index, gather_many, gather_star, gather_pairs, hgather, hgather_many, index_lstm_stage, lstm_stage,  # noqa: F401
-                     float_attn_stage, float_lstm_stage, float_mean_stage, hinge_intervals, hinge_tables, mean_stage, pgather, sample_and_gather, sample_and_gather_many, sjoin, split_batches, StepBuffers)
+from .spjoin import (attn_stage, bgather, counts_attn_stage, gather, gather_counts, gather_index, gather_many, gather_star, gather_pairs, hgather, hgather_counts, hgather_many, hmean_stage, index_lstm_stage, lstm_stage,  # noqa: F401
+                     float_attn_stage, float_lstm_stage, float_mean_stage, hinge_intervals, hinge_tables, mean_stage, pgather, sample_and_gather, sample_and_gather_many, sample_and_hgather, sjoin, split_batches, StepBuffers)
 from .subg_acc import batch_sampler, gset_sampler, walk_join, walk_sampler  # noqa: F401
 from .ppr import topk_ppr_matrix  # noqa: F401
 from .stepgraph import CapturedJoin, CapturedJoinPool, CapturedStep, CapturedStepPool  # noqa: F401

@@ -33,7 +33,7 @@ SYMBOLS = (
     "subgacc_encode_sizes", "subgacc_encode_fill", "subgacc_finish_rows",
     "subgacc_batch_sampler_workspace_bytes", "subgacc_batch_sampler", "subgacc_step_prologue",
     "subgacc_hop_records_format", "subgacc_hop_records_build", "subgacc_step_dedup_workspace_bytes",
-    "subgacc_step_prologue_dedup", "subgacc_walk_spg_sparse",
+    "subgacc_step_prologue_dedup", "subgacc_step_prologue_dedup_roles", "subgacc_walk_spg_sparse",
     "subgacc_keyrows_register", "subgacc_keyrows_cand_capacity", "subgacc_walk_tags", "subgacc_keyrows_compact", "subgacc_keyrows_translate", "subgacc_rng_replay", "subgacc_walk_keyrows64", "subgacc_worklist_workspace_bytes", "subgacc_worklist_by_root", "subgacc_walk_spg_list",
     "subgacc_locality_round", "subgacc_worklist_by_rank",
     "subgacc_sjoin_fill_v2", "subgacc_publish_words", "subgacc_rows_to_headed", "subgacc_sjoin_star_sizes", "subgacc_sjoin_relu_mean",
@@ -136,6 +136,7 @@ def lib():
     sig["subgacc_hop_records_build"] = (C.c_int, [vp, i32, vp, i64, i64, i32, i32, vp, vp])
     sig["subgacc_step_dedup_workspace_bytes"] = (C.c_size_t, [i64])
     sig["subgacc_step_prologue_dedup"] = (C.c_int, [vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, C.c_size_t, vp, vp])
+    sig["subgacc_step_prologue_dedup_roles"] = (C.c_int, [vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, i64, i32, i32, vp, C.c_size_t, vp, vp])
     sig["subgacc_walk_spg_sparse"] = (C.c_int, [cfgp, vp, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp])
     sig["subgacc_step_prologue"] = (C.c_int, [vp, i64, vp, i64, vp, vp, i64, vp])
     sig["subgacc_batch_sampler_workspace_bytes"] = (sz, [i64])

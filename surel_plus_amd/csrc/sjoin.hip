@@ -2469,9 +2469,8 @@ extern "C" int subgacc_sjoin_fill_v2(const subgacc_join_desc *d, void *stream) {
     }
     if (!sizes_only) {
         SG_REQUIRE(d->flags, SUBGACC_ERR_BADARG, "sjoin_fill_v2: null argument (flags)");
-        SG_REQUIRE(!(kind == SUBGACC_JOIN_KEY64 && packed) && !(keyed && strided && d->out_segid), SUBGACC_ERR_BADARG,
-                   "sjoin_fill_v2: this payload kind does not go with this row layout (64-bit keys: strided or headed rows; keys "
-                   "of strided rows -- a transient batch -- are joined with segment pointers)");
+        SG_REQUIRE(!(kind == SUBGACC_JOIN_KEY64 && packed), SUBGACC_ERR_BADARG,
+                   "sjoin_fill_v2: this payload kind does not go with this row layout (64-bit keys: strided or headed rows)");
         SG_REQUIRE(d->form == SUBGACC_JOIN_ROWS || kind == SUBGACC_JOIN_SFPTR, SUBGACC_ERR_BADARG,
                    "sjoin_fill_v2: the count and pair forms join an SFptr store");
         if (S > 0 || sized) {

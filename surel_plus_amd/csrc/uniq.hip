@@ -86,23 +86,9 @@ __global__ void step_dedup_claim_kernel(UniqTable t, int64_t cap, int64_t *zero_
     atomicMax(&hvals[h], ((unsigned long long)gen << 32) | (0xFFFFFFFFu - (uint32_t)i));   // later stamp wins, then the smaller index
 }
 
-__global__ __launch_bounds__(256) void step_dedup_map_kernel(const int64_t *__restrict__ edge, const int32_t *__restrict__ slot_of,
-                                                             const unsigned long long *__restrict__ hvals, int32_t *__restrict__ roots,
-                                                             int64_t *__restrict__ own, int64_t *__restrict__ partner,
-                                                             int32_t *__restrict__ worklist, int32_t *__restrict__ row_len, int64_t n,
-                                                             int64_t *last_gen, int64_t *n_distinct) {
-    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    bool first = false;
-    if (j < n) {
-        const int64_t row = (int64_t)(0xFFFFFFFFu - (uint32_t)hvals[slot_of[j]]);
-        const int64_t half = n / 2;
-        own[j] = row;
-        partner[j < half ? j + half : j - half] = row;
-        first = row == j;
-        const int64_t v = edge[j];
-        roots[j] = first ? ((v < 0 || v > 0x7FFFFFFFll) ? -1 : (int32_t)v) : SUBGACC_NO_ROOT;
-        if (!first) row_len[j] = 0;      // the walk kernel never visits this row: it is empty, not stale
-    }
+// The tail of both map kernels: `first` says whether this thread's occurrence j is the first of its node.
+__device__ __forceinline__ void dedup_list_first(bool first, int64_t j, int32_t *__restrict__ worklist, int64_t *last_gen,
+                                                 int64_t *__restrict__ n_distinct) {
     // the rows that carry a set, as a dense work list for the walk kernel (its order is the order of arrival and does not
     // matter: entry k names its row); ONE atomicAdd per workgroup (one per wavefront were 2,048 returning atomics on one word
     // for a batch of 65,536 pairs, served one after the other: 20 of the kernel's 28 us)
@@ -131,6 +117,53 @@ __global__ __launch_bounds__(256) void step_dedup_map_kernel(const int64_t *__re
             *last_gen = (int64_t)gen;
         }
     }
+}
+
+__global__ __launch_bounds__(256) void step_dedup_map_kernel(const int64_t *__restrict__ edge, const int32_t *__restrict__ slot_of,
+                                                             const unsigned long long *__restrict__ hvals, int32_t *__restrict__ roots,
+                                                             int64_t *__restrict__ own, int64_t *__restrict__ partner,
+                                                             int32_t *__restrict__ worklist, int32_t *__restrict__ row_len, int64_t n,
+                                                             int64_t *last_gen, int64_t *n_distinct) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool first = false;
+    if (j < n) {
+        const int64_t row = (int64_t)(0xFFFFFFFFu - (uint32_t)hvals[slot_of[j]]);
+        const int64_t half = n / 2;
+        own[j] = row;
+        partner[j < half ? j + half : j - half] = row;
+        first = row == j;
+        const int64_t v = edge[j];
+        roots[j] = first ? ((v < 0 || v > 0x7FFFFFFFll) ? -1 : (int32_t)v) : SUBGACC_NO_ROOT;
+        if (!first) row_len[j] = 0;      // the walk kernel never visits this row: it is empty, not stale
+    }
+    dedup_list_first(first, j, worklist, last_gen, n_distinct);
+}
+
+// The map kernel of a step whose n = r*B roots come in r blocks of B and whose segment list has s blocks of B, segment block b
+// reading root block (roles >> 4*b) & 15 (triplets: r = 3, s = 4, blocks u, w, v, w -- hgather's [U|w ; W|u ; V|w ; W|v],
+// train.py:57-68; pairs: r = 2, s = 2).  own[b*B + t] = the row of the first occurrence of segment (b, t)'s root over the WHOLE root
+// list: a node that is u of one triplet and w of another is walked once.  No partner list: the segment list is mirrored
+// (pair_block = B) and the join derives it.
+__global__ __launch_bounds__(256) void step_dedup_roles_map_kernel(const int64_t *__restrict__ edge, const int32_t *__restrict__ slot_of,
+                                                                   const unsigned long long *__restrict__ hvals,
+                                                                   int32_t *__restrict__ roots, int64_t *__restrict__ own,
+                                                                   int32_t *__restrict__ worklist, int32_t *__restrict__ row_len,
+                                                                   int64_t n, int64_t B, int32_t s, uint32_t roles, int64_t *last_gen,
+                                                                   int64_t *n_distinct) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool first = false;
+    if (j < n) {
+        const int64_t row = (int64_t)(0xFFFFFFFFu - (uint32_t)hvals[slot_of[j]]);
+        const uint32_t blk = (uint32_t)(j >= B) + (uint32_t)(j >= 2 * B);      // r <= 3
+        const int64_t t = j - (int64_t)blk * B;
+        for (int b = 0; b < s; ++b)
+            if (((roles >> (4 * b)) & 15u) == blk) own[(int64_t)b * B + t] = row;
+        first = row == j;
+        const int64_t v = edge[j];
+        roots[j] = first ? ((v < 0 || v > 0x7FFFFFFFll) ? -1 : (int32_t)v) : SUBGACC_NO_ROOT;
+        if (!first) row_len[j] = 0;      // the walk kernel never visits this row: it is empty, not stale
+    }
+    dedup_list_first(first, j, worklist, last_gen, n_distinct);
 }
 
 // The distinct LP rows are 10^2..10^5 while the members are 10^7..10^9, so almost every member repeats a key
@@ -392,6 +425,49 @@ extern "C" int subgacc_step_prologue_dedup(void *table, int64_t capacity, int64_
                        n_distinct, n);
     hipLaunchKernelGGL(step_dedup_map_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, edge, slot_of, hvals, roots, own,
                        partner, worklist, row_len, n, last_gen, n_distinct);
+    SG_LAUNCH_CHECK();
+    return SUBGACC_OK;
+}
+
+// segment block b of a step with r root blocks and s segment blocks reads root block (roles >> 4*b) & 15; 0 = not implemented
+static uint32_t dedup_roles(int32_t r, int32_t s) {
+    if (r == 2 && s == 2) return 0x10u;         // pairs: u, v (train.py:13-23)
+    if (r == 3 && s == 4) return 0x2120u;       // triplets: u, w, v, w (train.py:57-68)
+    return 0;
+}
+
+extern "C" int subgacc_step_prologue_dedup_roles(void *table, int64_t capacity, int64_t *zero_words, int64_t n_zero, const int64_t *edge,
+                                                 int32_t *roots, int64_t *own, int32_t *worklist, int32_t *row_len, int64_t n, int64_t B,
+                                                 int32_t r, int32_t s, void *workspace, size_t workspace_bytes, int64_t *n_distinct,
+                                                 void *stream) {
+    SG_REQUIRE(!table || (is_pow2(capacity) && capacity < (1ll << 31)), SUBGACC_ERR_BADARG,
+               "step_prologue_dedup_roles: capacity must be a power of two below 2^31");
+    if (!table) capacity = 0;
+    SG_REQUIRE(edge && roots && own && worklist && row_len && n_distinct && n_zero >= 0 && (n_zero == 0 || zero_words), SUBGACC_ERR_BADARG,
+               "step_prologue_dedup_roles: null argument");
+    const uint32_t roles = dedup_roles(r, s);
+    SG_REQUIRE(roles != 0, SUBGACC_ERR_BADARG,
+               "step_prologue_dedup_roles: r = %d root blocks with s = %d segment blocks is not implemented (pairs: 2, 2; triplets: 3, 4)",
+               (int)r, (int)s);
+    SG_REQUIRE(B > 0 && n == (int64_t)r * B && n < (1ll << 30), SUBGACC_ERR_BADARG,
+               "step_prologue_dedup_roles: n = %lld roots is not r*B = %d x %lld (0 < n < 2^30)", (long long)n, (int)r, (long long)B);
+    SG_REQUIRE(workspace && workspace_bytes >= subgacc_step_dedup_workspace_bytes(n), SUBGACC_ERR_WORKSPACE,
+               "step_prologue_dedup_roles: workspace too small");
+    const int64_t c = dedup_slots(n);
+    char *w = (char *)workspace;
+    int64_t *last_gen = (int64_t *)w;                       // the stamp of the previous call on this workspace (0 at first)
+    unsigned long long *hkeys = (unsigned long long *)(w + 256);
+    unsigned long long *hvals = (unsigned long long *)(w + 256 + align_up((size_t)c * 8, 256));
+    int32_t *slot_of = (int32_t *)(w + 256 + 2 * align_up((size_t)c * 8, 256));
+    int64_t span = capacity > n ? capacity : n;
+    if (n_zero > span) span = n_zero;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(step_dedup_claim_kernel, dim3((unsigned)ceil_div(span, 256)), dim3(256), 0, st,
+                       table ? uniq_view(table, capacity) : UniqTable{nullptr, nullptr, nullptr, 0}, capacity, zero_words, n_zero,
+                       edge, slot_of, hkeys, hvals, (uint32_t)(c - 1), 32 - (63 - __builtin_clzll((unsigned long long)c)), last_gen,
+                       n_distinct, n);
+    hipLaunchKernelGGL(step_dedup_roles_map_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, edge, slot_of, hvals, roots, own,
+                       worklist, row_len, n, B, s, roles, last_gen, n_distinct);
     SG_LAUNCH_CHECK();
     return SUBGACC_OK;
 }

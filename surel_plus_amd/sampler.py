@@ -237,6 +237,7 @@ class SampledSets:
     keyrows: bool = False        # strided rows whose payload (`slot`) is the member's LP key: no table, no numbering
     key64: bool = False          # ... a 64-bit key (`slot` is int64: 4-hop walks with M >= 128), else 32 bits
     _table_form: object = None   # key64: the same batch sampled again with the table form, once number() / to_csr() needed it
+    _rows_are_members: bool = True   # False: the join emits some rows twice (triplets: w), so its row count is not the member count
     _fresh: object = None        # sets of a buffered step: () -> do the step buffers still hold THIS batch? (spjoin._buffered_step)
     _keyctx: dict = None         # keyrows: what number() needs to register the rows' keys (csr, roots, cfg, rng positions, capacity, fresh())
     _ktable: torch.Tensor = None  # keyrows: the table of distinct LP rows once number() has built it (capacity _kcap)
@@ -311,7 +312,7 @@ class SampledSets:
         if self.strided:
             # root dedup: the rows of repeated endpoints are empty, so the members are fewer than the join's rows -- counted when
             # somebody asks (X): a reduction + read-back here would stall a serving loop once per step behind the NEXT step's launches
-            self._members = X if self.n_distinct is None else None
+            self._members = X if (self.n_distinct is None and self._rows_are_members) else None
             return self
         self.ids = self.ids[:X]
         for name in ("slot", "keys", "data", "sf"):

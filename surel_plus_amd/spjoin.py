@@ -133,8 +133,6 @@ def sjoin(spg, own, partner, encode=None, ptr_mode=True, return_index=False, pai
     if pair_block <= 0 and (kind in (JOIN_KEY32, JOIN_KEY64) or "row_off" not in rows) and (S > 0 or "row_len" in rows):
         raise ValueError("this store is joined by gather / hgather (mirrored segment lists); use the packed store (to_csr() / "
                          "to_spg()) for the other forms")
-    if kind in (JOIN_KEY32, JOIN_KEY64) and "row_len" in rows and not ptr_mode:
-        raise ValueError("a key-rows batch is joined with segment pointers (ptr=True); use z.to_csr() for segment ids")
     seg, flags = _seg_and_flags(S, dev)
     st, R = stream_ptr(), None              # (R stays on the device in a lazy join)
     star_bit = _lib.JOIN_OPT_STAR if star else 0
@@ -508,10 +506,15 @@ class StepBuffers:
     The hash is stamped with a per-step generation kept on the device: a captured step replays correctly.
     order=LocalityOrder (sampler.locality_order) or an int32 rank [num_nodes]: every step the fused-row kernel serves walks its
     rows (or, with dedup_roots, its first occurrences) in ascending rank of their root, whatever the batch size -- the rows are
-    the same; `walk_order` records after each step which order ran ("rank", "id" or "batch")."""
+    the same; `walk_order` records after each step which order ran ("rank", "id" or "batch").
+    ptr=False: the step also writes the segment id of every output row (train.py:25-30, what the reference's --aggrs lstm runs
+    with, main.py:217) into a buffer of its own, `segid` int64 [worst case rows]; one batch per step (batch=None).
+    triplets=True: the step of sample_and_hgather -- `pairs` triplets (u, v, w), 3B roots walked once each, 4B segments
+    [U|w ; W|u ; V|w ; W|v] (train.py:57-68), always with segment ids; dedup_roots=True takes the prologue that knows the roles
+    (subgacc_step_prologue_dedup_roles); Philox only (the reference never samples triplets in a stream), one batch per step."""
 
     def __init__(self, csr, pairs, num_walks=200, num_steps=3, uniq_capacity=1 << 17, out=None, dedup_roots=False, rng="philox",
-                 key_rows=True, sort_roots=True, batch=None, align_rows=True, order=None):
+                 key_rows=True, sort_roots=True, batch=None, align_rows=True, order=None, ptr=True, triplets=False):
         from .sampler import FUSED_MAX_Q, as_rank
         L, dev = lib(), csr.device
         # order=LocalityOrder / int32 rank: the walk kernel takes the rows in ascending rank of their root (subgacc_worklist_by_rank),
@@ -527,7 +530,16 @@ class StepBuffers:
             raise ValueError(f"StepBuffers: pairs = {self.B} is not a whole number of batches of {batch}")
         if self.batch != self.B and dedup_roots:
             raise ValueError("StepBuffers: root dedup works on one batch (batch=None)")
-        n, self.Q, self.k = 2 * self.B, self.M * self.m + 1, self.m + 1
+        self.triplets = bool(triplets)
+        self.ptr = bool(ptr) and not self.triplets          # hgather always answers with segment ids (train.py:57-59)
+        if self.batch != self.B and not self.ptr:
+            raise ValueError("StepBuffers: segment ids (ptr=False, triplets=True) are those of one batch (batch=None)")
+        if self.triplets and rng != "philox":
+            raise ValueError("StepBuffers(triplets=True) samples with rng='philox' (the reference never samples triplets in a rand_r "
+                             "stream: there is nothing to reproduce)")
+        # n roots = rows of the step, S segments of the join: pairs [u | v] -> 2B and 2B, triplets [u | v | w] -> 3B and 4B
+        n, S = (3 * self.B, 4 * self.B) if self.triplets else (2 * self.B, 2 * self.B)
+        self.n, self.S, self.Q, self.k = n, S, self.M * self.m + 1, self.m + 1
         if self.Q > FUSED_MAX_Q or self.m < 1:
             raise ValueError(f"StepBuffers: num_walks*num_steps+1 = {self.Q} exceeds what the fused-row walk kernel holds")
         # the rows of two roots lie `stride` words apart: M*m+1 rounded up to whole 128-byte lines (subgacc_walk_cfg::row_pitch) --
@@ -545,8 +557,8 @@ class StepBuffers:
         self.slot = torch.empty(n * self.stride, dtype=torch.int64 if self.key64 else torch.int32, device=dev)
         self.sort_roots = bool(sort_roots)     # the walk kernel takes the rows in ascending order of root id (csrc/worklist.hip)
         self.table = None if self.keyrows else torch.empty(L.subgacc_uniq_table_bytes(self.capacity), dtype=torch.uint8, device=dev)
-        self.tail = torch.zeros(n + 1 + 4 + 1, dtype=torch.int64, device=dev)  # seg [n+1] | status [4] | distinct roots [1]
-        self.seg, self.status, self.n_distinct = self.tail[: n + 1], self.tail[n + 1: n + 5], self.tail[n + 5:]
+        self.tail = torch.zeros(S + 1 + 4 + 1, dtype=torch.int64, device=dev)  # seg [S+1] | status [4] | distinct roots [1]
+        self.seg, self.status, self.n_distinct = self.tail[: S + 1], self.tail[S + 1: S + 5], self.tail[S + 5:]
         self.dedup = bool(dedup_roots)
         self.rng = rng
         if rng not in ("philox", "rand_r") or (rng == "rand_r" and self.dedup):
@@ -563,16 +575,18 @@ class StepBuffers:
             from .sampler import walk_kernel_name
             if walk_kernel_name(csr, self.M, self.m, True) != "walk_rows_kernel":
                 raise ValueError("StepBuffers(dedup_roots=True) needs a shape the fused-row walk kernel serves (2..4 hops, M <= 256)")
-            self.own = torch.empty(n, dtype=torch.int64, device=dev)
-            self.partner = torch.empty(n, dtype=torch.int64, device=dev)
+            self.own = torch.empty(S, dtype=torch.int64, device=dev)
+            # (triplets: no partner list -- the roles prologue leaves it to the kernels, the list is mirrored)
+            self.partner = None if self.triplets else torch.empty(n, dtype=torch.int64, device=dev)
             self.worklist = torch.empty(n, dtype=torch.int32, device=dev)
             self.dedup_ws = torch.zeros(L.subgacc_step_dedup_workspace_bytes(n), dtype=torch.uint8, device=dev)
             self.dedup_steps = 0
-        self.ws = torch.empty(max(L.subgacc_sjoin_workspace_bytes(n), 8), dtype=torch.uint8, device=dev)
+        self.ws = torch.empty(max(L.subgacc_sjoin_workspace_bytes(S), 8), dtype=torch.uint8, device=dev)
         self.feat = None if self.keyrows else torch.empty((self.capacity + 1, self.k), dtype=torch.float32, device=dev)
-        if out is not None:         # room for the worst case: 2B rows of M*m+1 members
-            _out_view(out, dev, self.k, worst=n * self.Q)
-        self.out = out if out is not None else torch.empty(n * self.Q * 2 * self.k, dtype=torch.float32, device=dev)
+        if out is not None:         # room for the worst case: S segments (2B; triplets: 4B) of M*m+1 members
+            _out_view(out, dev, self.k, worst=S * self.Q)
+        self.out = out if out is not None else torch.empty(S * self.Q * 2 * self.k, dtype=torch.float32, device=dev)
+        self.segid = None if self.ptr else torch.empty(S * self.Q, dtype=torch.int64, device=dev)
 
 
 def _dedup_tick(bufs):
@@ -585,12 +599,15 @@ def _dedup_tick(bufs):
 
 
 def _buffered_step(csr, e, bufs, seed, out):
-    """sample_and_gather through a StepBuffers: six launches, nothing allocated, nothing read back"""
+    """sample_and_gather / sample_and_hgather through a StepBuffers: six launches, nothing allocated, nothing read back"""
     from .sampler import SampledSets, _timed, _walk, make_cfg, sorted_worklist, walk_kernel_name, worklist_buffers
     L, st, dev = lib(), stream_ptr(), csr.device
-    B, M, m, k, n = bufs.B, bufs.M, bufs.m, bufs.k, 2 * bufs.B
+    B, M, m, k, n, S = bufs.B, bufs.M, bufs.m, bufs.k, bufs.n, bufs.S      # n roots (rows), S segments
     PB = bufs.batch              # pairs per mirrored block of the segment list
-    if tuple(e.shape) != ((2, B) if PB == B else (B // PB, 2, PB)):
+    if bufs.triplets:
+        if tuple(e.shape) != (3, B):
+            raise ValueError(f"these StepBuffers were made for [3, {B}] triplets")
+    elif tuple(e.shape) != ((2, B) if PB == B else (B // PB, 2, PB)):
         raise ValueError(f"these StepBuffers were made for [2, {B}] pairs" if PB == B else
                          f"these StepBuffers were made for [{B // PB}, 2, {PB}] pairs")
     e = e.contiguous()
@@ -605,9 +622,14 @@ def _buffered_step(csr, e, bufs, seed, out):
     if bufs.dedup:      # first occurrences only: the other rows stay empty, the segment lists point at the first occurrence
         if not torch.cuda.is_current_stream_capturing():
             _dedup_tick(bufs)
-        check(L.subgacc_step_prologue_dedup(*tab, ptr(bufs.status), 4, ptr(e), ptr(bufs.roots), ptr(bufs.own), ptr(bufs.partner),
-                                            ptr(bufs.worklist), ptr(bufs.nsize), n, ptr(bufs.dedup_ws), bufs.dedup_ws.numel(),
-                                            ptr(bufs.n_distinct), st))
+        if bufs.triplets:       # roots [u | v | w], segment blocks u, w, v, w: first occurrences over all three roles
+            check(L.subgacc_step_prologue_dedup_roles(*tab, ptr(bufs.status), 4, ptr(e), ptr(bufs.roots), ptr(bufs.own),
+                                                      ptr(bufs.worklist), ptr(bufs.nsize), n, B, 3, 4, ptr(bufs.dedup_ws),
+                                                      bufs.dedup_ws.numel(), ptr(bufs.n_distinct), st))
+        else:
+            check(L.subgacc_step_prologue_dedup(*tab, ptr(bufs.status), 4, ptr(e), ptr(bufs.roots), ptr(bufs.own), ptr(bufs.partner),
+                                                ptr(bufs.worklist), ptr(bufs.nsize), n, ptr(bufs.dedup_ws), bufs.dedup_ws.numel(),
+                                                ptr(bufs.n_distinct), st))
     else:
         check(L.subgacc_step_prologue(*tab, ptr(bufs.status), 4, ptr(e), ptr(bufs.roots), n, st))
     # the work list the walk kernel runs over.  Root dedup: its first occurrences (no sort by id there: what that order buys is mostly
@@ -633,8 +655,13 @@ def _buffered_step(csr, e, bufs, seed, out):
         _walk(cfg, csr, bufs.roots, n, flags, st, "keys64" if bufs.key64 else "fused", ids=bufs.ids, payload=bufs.slot,
               nsize=bufs.nsize, rng=(bufs.rng_pos, bufs.rng_seed) if rr else (None, None), table=bufs.table,
               capacity=0 if kr else bufs.capacity, work=work, select=bufs.dedup)
-    own, partner = (bufs.own, bufs.partner) if bufs.dedup else _arange_segments(B, dev, PB)
-    check(L.subgacc_sjoin_sizes_rows(ptr(bufs.nsize), n, ptr(own), ptr(partner), n, ptr(bufs.seg), ptr(flags), ptr(bufs.ws),
+    if bufs.dedup:
+        own, partner = bufs.own, bufs.partner
+    elif bufs.triplets:
+        own, partner = _triplet_segments(B, dev), None
+    else:
+        own, partner = _arange_segments(B, dev, PB)
+    check(L.subgacc_sjoin_sizes_rows(ptr(bufs.nsize), n, ptr(own), ptr(partner), S, ptr(bufs.seg), ptr(flags), ptr(bufs.ws),
                                      bufs.ws.numel(), st))
     if kr:
         kind, payload = (JOIN_KEY64 if bufs.key64 else JOIN_KEY32), dict(num_walks=M, num_steps=m)
@@ -642,10 +669,10 @@ def _buffered_step(csr, e, bufs, seed, out):
         keys = bufs.table[: bufs.capacity * 8].view(torch.int64)
         check(L.subgacc_unpack_lp(ptr(keys), bufs.capacity, None, M, m, None, None, ptr(bufs.feat), 1, st))
         kind, payload = JOIN_SFPTR, dict(table=bufs.feat, table_rows=bufs.capacity + 1, k=k)
-    xz = _out_view(out if out is not None else bufs.out, dev, k, worst=n * bufs.Q)
+    xz = _out_view(out if out is not None else bufs.out, dev, k, worst=S * bufs.Q)
     with _timed("sjoin_fill"):
         join_fill(JOIN_ROWS, kind, st, row_len=bufs.nsize, n_rows=n, row_stride=bufs.stride, ids=bufs.ids, payload=bufs.slot, own=own,
-                  partner=partner, S=n, seg=bufs.seg, pair_block=PB, out_xz=xz, flags=flags, **payload)
+                  partner=partner, S=S, seg=bufs.seg, pair_block=PB, out_xz=xz, out_segid=bufs.segid, flags=flags, **payload)
     sets = SampledSets(bufs.nsize, None, bufs.ids, None, None, None, M, m, bufs.stride, None)
     sets.slot, sets.table, sets.capacity, sets.strided = bufs.slot, bufs.table, (0 if kr else bufs.capacity), True
     if kr:
@@ -660,13 +687,15 @@ def _buffered_step(csr, e, bufs, seed, out):
     # every set of a buffered step -- key rows or table form -- is a view of buffers that the NEXT step overwrites: what is computed
     # from them on demand (the member count of a deduplicated step, X / nnz) is refused once they hold a later batch
     sets._fresh = lambda: getattr(bufs, "step_id", 0) == step_id
-    sets.status, sets._tail = bufs.status, bufs.tail[n: n + (6 if bufs.dedup else 5)]
+    sets.status, sets._tail = bufs.status, bufs.tail[S: S + (6 if bufs.dedup else 5)]
+    sets._rows_are_members = not bufs.triplets       # (the rows of w are joined twice: the join's rows are not the members)
     sets.walk_order = bufs.walk_order
-    return xz, bufs.seg, sets
+    # ptr=False / triplets: the ids of the first seg[-1] rows (as xz: a view of the whole buffer, the row count stays on the device)
+    return xz, (bufs.seg if bufs.ptr else _with_pointers(bufs.segid[: xz.shape[0]], bufs.seg)), sets
 
 
 def sample_and_gather(csr, edge, num_walks=200, num_steps=3, seed=111413, rng="philox", dedup_roots=False, out=None,
-                      lazy=False, strided=None, buffers=None, order=None, **kw):
+                      lazy=False, strided=None, buffers=None, order=None, ptr=True, **kw):
     """The on-demand form of the path in one call: sample the endpoints of `edge` [2, B] (node ids), build their SpG
     rows, join -> (xz, indptr, sets), the same (xz, indptr) as `gather(edge, subg_matrix(G, arange(N)))` would give for sets
     drawn with the same RNG (Philox keys every walk by (seed, root id, walk, step), so a root's set does not depend on
@@ -678,7 +707,11 @@ def sample_and_gather(csr, edge, num_walks=200, num_steps=3, seed=111413, rng="p
     buffers=StepBuffers(...): the same step without a single allocation or helper kernel (six launches; the result is
     lazy: sets.prefetch() / sets.resolve() as with lazy=True, xz is a view of out= or of the buffers' own output).
     order=LocalityOrder (sampler.locality_order) or an int32 rank [num_nodes]: the walk kernel takes the endpoints in that order
-    (with buffers=, the StepBuffers' own order= is the one used); (xz, indptr) do not change, sets.walk_order says which ran."""
+    (with buffers=, the StepBuffers' own order= is the one used); (xz, indptr) do not change, sets.walk_order says which ran.
+    ptr=False: the second result is the segment id (0 .. 2B-1) of every row of xz, int64 [R], with the pointers as its
+    .seg_pointers -- gather(ptr=False) of train.py:25-30, what the reference's --aggrs lstm runs with (main.py:217); the join
+    writes the ids next to the rows.  With buffers=StepBuffers(..., ptr=False): a view of the buffers' id buffer, as xz is of
+    the output buffer."""
     from .sampler import as_rank
     from .spg import sample_spg
     order = as_rank(csr, order)
@@ -687,6 +720,9 @@ def sample_and_gather(csr, edge, num_walks=200, num_steps=3, seed=111413, rng="p
         raise ValueError("sample_and_gather: edge must be [2, B] (many batches at once: sample_and_gather_many)")
     B = e.shape[-1]
     if buffers is not None:     # the allocation-free form of a serving loop: same rows, same (xz, indptr), lazily resolved
+        if buffers.triplets or bool(ptr) != buffers.ptr:
+            raise ValueError("buffers= were made for another result: StepBuffers(..., ptr=False) serves ptr=False, "
+                             "StepBuffers(..., triplets=True) serves sample_and_hgather")
         if (dedup_roots and not buffers.dedup) or rng != buffers.rng or strided is False or kw.get("fused") is False or \
                 kw.get("bucket", -1) > 0 or (num_walks, num_steps) != (buffers.M, buffers.m) or \
                 kw.get("uniq_capacity", buffers.capacity) != buffers.capacity:
@@ -711,13 +747,65 @@ def sample_and_gather(csr, edge, num_walks=200, num_steps=3, seed=111413, rng="p
                          strided=strided, order=order, **kw)
     table = z.slot_table() if sets.strided else sets.feature_table()
     if rows is not None:
-        xz, ind = gather(rows, z, e.device, ptr=True, encode=table, out=out, lazy=lazy)
+        xz, ind = gather(rows, z, e.device, ptr=bool(ptr), encode=table, out=out, lazy=lazy)
     else:
         own, partner = _arange_segments(B, e.device)
-        xz, ind = _checked(*sjoin(_as_spg(z), own, partner, table, ptr_mode=True, pair_block=B, out=out, lazy=lazy), lazy=lazy)
+        xz, ind = _checked(*sjoin(_as_spg(z), own, partner, table, ptr_mode=bool(ptr), pair_block=B, out=out, lazy=lazy), lazy=lazy)
     if lazy:      # the join's status word travels with the sets' own: resolve() raises IndexError for a row outside the store
         sets._join_flags = getattr(ind, "join_flags", None)
     return xz, ind, sets
+
+
+def _as_triplets(hedge, device, who):
+    """[3, B] triplets (u, v, w) as an int64 device tensor, or ValueError"""
+    h = _as_rows(hedge, device)
+    if h.dim() != 2 or h.shape[0] != 3:
+        raise ValueError(f"{who}: hedge must be [3, B] triplets (u, v, w), not {list(h.shape)}")
+    return h
+
+
+def sample_and_hgather(csr, hedge, num_walks=200, num_steps=3, seed=111413, rng="philox", dedup_roots=False, out=None, buffers=None,
+                       order=None, **kw):
+    """The on-demand form of hgather (train.py:48-72, the batches of main_horder.py / train.py:142-172) in one call: the three
+    roles of `hedge` [3, B] (node ids u, v, w) are walked ONCE each -- 3B roots, not the 4B that two pair steps (u, w) and (v, w)
+    would walk -- and joined as [U|w ; W|u ; V|w ; W|v] -> (xz, ids, sets): bit for bit the (xz, ids) of
+    `hgather(hedge, z, encode=table)` over a store z sampled for all nodes with the same seed (Philox keys every walk by (seed,
+    root id, walk, step)), ids int64 [R] = segment ids 0 .. 4B-1 with their pointers as .seg_pointers.  `num_steps` = walk hops.
+    dedup_roots=True samples every distinct node of the batch once, whatever its roles: the model's negatives keep (u, v) of their
+    positive and replace w (dataloader.py:265-268, 275), so two of the three roots of every negative are repeats.
+    buffers=StepBuffers(csr, B, ..., triplets=True): the allocation-free six-launch step (xz and ids are views of the buffers,
+    their first ids.seg_pointers[-1] rows are the result; sets.prefetch() / sets.resolve() as for sample_and_gather).
+    rng: "philox" only -- the reference never samples triplets in a rand_r stream, there is nothing to reproduce.
+    order=: as for sample_and_gather."""
+    from .sampler import as_rank
+    from .spg import sample_spg
+    if rng != "philox":
+        raise ValueError("sample_and_hgather samples with rng='philox' (a rand_r set depends on its root's place in a stream the "
+                         "reference never draws for triplets)")
+    order = as_rank(csr, order)
+    h = _as_triplets(hedge, csr.device, "sample_and_hgather")
+    B = h.shape[1]
+    if buffers is not None:
+        if not buffers.triplets or (dedup_roots and not buffers.dedup) or (num_walks, num_steps) != (buffers.M, buffers.m) or \
+                kw.get("uniq_capacity", buffers.capacity) != buffers.capacity or kw.get("fused") is False or kw.get("bucket", -1) > 0:
+            raise ValueError("buffers= serves the triplet step of the shape its StepBuffers(..., triplets=True) were made for (root "
+                             "dedup if they were made with dedup_roots=True)")
+        if order is not None and (buffers.order is None or order.rank is not buffers.order.rank):
+            raise ValueError("buffers= walks in the order its StepBuffers were made with: pass order= to StepBuffers(...)")
+        return _buffered_step(csr, h, buffers, seed, out)
+    kw.setdefault("number_rows", False)     # joined by table slot: the distinct LP rows need no numbering
+    if dedup_roots:
+        roots, inv = torch.unique(h.reshape(-1), return_inverse=True)
+        u, v, w = inv.view(3, B)
+        own = torch.cat([u, w, v, w])
+    else:
+        roots = h.reshape(-1)
+        own = _triplet_segments(B, h.device)      # row i of the batch's SpG = root i of [u | v | w]
+    z, sets = sample_spg(csr, roots.to(torch.int32), num_walks=num_walks, num_steps=num_steps, seed=seed, rng=rng, strided=True,
+                         order=order, **kw)
+    table = z.slot_table() if sets.strided else sets.feature_table()
+    xz, ids = _checked(*sjoin(_as_spg(z), own, None, table, ptr_mode=False, pair_block=B, out=out))
+    return xz, ids, sets
 
 
 def sample_and_gather_many(csr, edges, num_walks=200, num_steps=3, seed=111413, rng="philox", out=None, buffers=None, order=None,
@@ -783,6 +871,23 @@ def _arange_segments(B, device, block=None):
     return hit
 
 
+def _triplet_segments(B, device):
+    """hgather()'s own list [u | w | v | w] for hedge = [[0..B), [B..2B), [2B..3B)] -- the rows of a triplet batch sampled root by
+    root -- kept per (B, device) like _arange_segments (the mirrored partner list [w | u | w | v] is derived by the kernels)"""
+    key = (int(B), str(device), "triplets")
+    hit = _ARANGE_SEGMENTS.get(key)
+    if hit is None:
+        with _CACHE_LOCK:
+            hit = _ARANGE_SEGMENTS.get(key)
+            if hit is None:
+                r = torch.arange(3 * B, device=device, dtype=torch.int64).view(3, B)
+                hit = torch.cat([r[0], r[2], r[1], r[2]])
+                if not torch.cuda.is_current_stream_capturing():
+                    torch.cuda.current_stream(hit.device).synchronize()
+                _ARANGE_SEGMENTS[key] = hit
+    return hit
+
+
 def _packed_rows(spg, form):
     """The row fields of the store the count / pair / index forms join: these forms have no headed one (ValueError, before any
     device work)."""
@@ -800,26 +905,67 @@ def gather_counts(edge, x, table_rows, device=None):
     embedding f:  segment_sum_j(f(xz).sum(-2)) == C[j] @ f(Z_SF), so `x = f(xz).sum(-2); aggr(x, ptr)` of the
     reference's Net.forward becomes `(C @ f(Z_SF)) / sizes[:, None]` and the [R,2,k] tensor never exists."""
     spg = _as_spg(x)
-    rows = _packed_rows(spg, "gather_counts")
+    rows = _count_rows(spg, table_rows, "gather_counts")
+    e = _as_rows(edge, spg.device)
+    return _counts(spg, rows, e, (e[0], e[1]), (e[1], e[0]), table_rows)
+
+
+def _count_rows(spg, table_rows, form):
+    """the row fields of the store the count form joins, or the refusals of gather_counts / hgather_counts (before any device work)"""
+    rows = _packed_rows(spg, form)
     if "row_off" not in rows or rows["payload"].dtype != torch.int32 or spg.keyrows:
-        raise TypeError("gather_counts needs a packed SFptr (integer) SpG (not a keyed() one)")
+        raise TypeError(f"{form} needs a packed SFptr (integer) SpG (not a keyed() one)")
     if table_rows <= spg.max_data:
         raise IndexError(f"index {spg.max_data} is out of bounds for a table with {table_rows} rows")
-    e = _as_rows(edge, spg.device)
+    return rows
+
+
+def _counts(spg, rows, e, own_blocks, partner_blocks, table_rows):
+    """ONE launch of the count kernel over the mirrored blocks `own_blocks` (each [B]; block 2t+1 mirrors block 2t) of the rows `e`"""
     B = e.shape[1]
     if B and bool(((e < 0) | (e >= spg.n_rows)).any()):          # this form has no size pass to carry the check
         raise IndexError(f"row index out of range for an SpG with {spg.n_rows} rows")
-    own = torch.cat([e[0], e[1]]).contiguous()
-    partner = torch.cat([e[1], e[0]]).contiguous()
+    own = torch.cat(own_blocks).contiguous()
+    partner = torch.cat(partner_blocks).contiguous()
     dev = spg.device
-    out = torch.empty((2 * B, int(table_rows)), dtype=torch.float32, device=dev)
+    out = torch.empty((own.numel(), int(table_rows)), dtype=torch.float32, device=dev)
     flags = torch.zeros(4, dtype=torch.int32, device=dev)
     with _timed("sjoin_counts"):
-        join_fill(JOIN_COUNTS, JOIN_SFPTR, **rows, own=own, partner=partner, S=2 * B, pair_block=B, table_rows=int(table_rows),
+        join_fill(JOIN_COUNTS, JOIN_SFPTR, **rows, own=own, partner=partner, S=own.numel(), pair_block=B, table_rows=int(table_rows),
                   out_counts=out, flags=flags)
     sizes = rows["row_off"][own + 1] - rows["row_off"][own]
     _checked(out, sizes, flags)
     return out, sizes
+
+
+def hgather_counts(hedge, x, table_rows, device=None):
+    """Count form of hgather() (train.py:48-72) for HONet's mean aggregation (model_horder.py:56-57).
+
+    Returns (C float32 [4B, table_rows], sizes int64 [4B]) with C[j, p] = occurrences of LP row p (0 = partner absent) in either
+    feature slot of segment j -- hgather's blocks [U|w ; W|u ; V|w ; W|v] --, so that for any row-wise embedding f
+    segment_sum_j(f(xz).sum(-2)) == C[j] @ f(Z_SF) and the [R,2,k] tensor of 4B segments never exists.  The count kernel takes any
+    number of mirrored blocks (segment j = (p / pb) * 2 * pb + p % pb of pair p): own = [u | w | v | w], S = 4B, pair_block = B is
+    ONE launch of the kernel gather_counts() runs; there is no second count kernel."""
+    spg = _as_spg(x)
+    rows = _count_rows(spg, table_rows, "hgather_counts")
+    h = _as_triplets(hedge, spg.device, "hgather_counts")
+    u, v, w = h[0], h[1], h[2]
+    return _counts(spg, rows, h, (u, w, v, w), (w, u, w, v), table_rows)
+
+
+def hmean_stage(hedge, x, encode, embed):
+    """HONet's first model stage, fused:  model_horder.py:56-57
+        x = pe_embedding(xz).sum(dim=-2);  xu, xwu, xv, xwv = scatter_mean(x, ind, dim=0).view(4, -1, H)
+    as  (C @ embed(encode)) / sizes  with C = hgather_counts(hedge, x): mean_stage's algebra over hgather's four blocks instead of
+    gather's two.  `x` is a packed SFptr SpG as for mean_stage, `embed` any row-wise module; autograd reaches its parameters
+    through the small [T, H] activation -- C is a constant of the batch -- while xz [R,2,k] and the [R,2,H] activations never exist.
+    Returns float32 [4, B, H] in the order (xu, xwu, xv, xwv); empty segments give zero rows."""
+    table = encode if torch.is_tensor(encode) else torch.as_tensor(encode)
+    spg = _as_spg(x)
+    table = table.to(device=spg.device, dtype=torch.float32)
+    C, sizes = hgather_counts(hedge, spg, table.shape[0])
+    out = (C @ embed(table)) / sizes.clamp(min=1).to(torch.float32)[:, None]
+    return out.view(4, -1, out.shape[-1])
 
 
 def mean_stage(edge, x, encode, embed):
