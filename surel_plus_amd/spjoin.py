@@ -3,7 +3,8 @@
 Reference: train.py:13-45 (gather), :48-72 (hgather), :75-85 (bgather), :88-111 (pgather).  Same names,
 same argument meaning, same return values (xz float32 [R,2,k], indptr-or-segment-ids int64 on `device`);
 `x` is an SpG (surel_plus_amd.spg.SpG) or a scipy CSR (uploaded once and cached), `encode` the Z_SF table
-as a float32 CUDA tensor or None for a float payload.  The work is done by csrc/sjoin.hip.
+as a float32 CUDA tensor or None for a float payload.  The work is done by csrc/sjoin.hip (the row form),
+csrc/sjoin_sizes.hip (the size pass), csrc/sjoin_f64stage.hip and csrc/sjoin_forms.hip (the fused stages, the count and pair forms).
 """
 import ctypes
 import os

@@ -1,5 +1,5 @@
-"""GPU (MI355X): the fused first stages -- float_mean_stage, float_attn_stage and counts_attn_stage (csrc/sjoin.hip:
-sjoin_f64mean_kernel, sjoin_f64attn_kernel, sjoin_counts_attn_kernel) -- on stores whose row lengths sit at every boundary of the
+"""GPU (MI355X): the fused first stages -- float_mean_stage, float_attn_stage and counts_attn_stage (csrc/sjoin_f64stage.hip:
+sjoin_f64mean_kernel, sjoin_f64attn_kernel; csrc/sjoin_forms.hip: sjoin_counts_attn_kernel) -- on stores whose row lengths sit at every boundary of the
 kernels' code paths, and at every width boundary of their channel loops:
   * f64pair_stage's register trips (4 x 128 = 512 members), its span loop and the T rows it loads after them (513 ... 1,024), the staged
     / streamed cut (kMeanCap = 1,024), the streamed pairs' blocks of 128 channels (H > 128), H = 1,024 (the documented maximum);

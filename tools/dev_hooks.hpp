@@ -9,7 +9,7 @@
 //                             7 per-phase cycle shares (tools/walk_phases.py) | 8 no registration in the HBM table
 //   SG_EXPERIMENT (walk_rows.hip) 9 the last hop's read hits L2 (no missed line) | 10 every later hop's does
 //   SG_STOP_AFTER = k         every workgroup of walk_sets_kernel / walk_rows_kernel ends at stamp k (tools/walk_insts.sh)
-//   SJ_EXPERIMENT (sjoin.hip) 1 no search | 4 no row loads | 5 ends when the rows stand in LDS | 6 ends at entry
+//   SJ_EXPERIMENT (sjoin.hip, sjoin_f64pair.hpp, sjoin.hpp) 1 no search | 4 no row loads | 5 ends when the rows stand in LDS | 6 ends at entry
 //                             7 spans unpacked and staged but not stored      (rounds 1-4 also had 2 / 3 / 8: store variants of the old kernel)
 #pragma once
 #define SG_DEV_HOOKS 1
@@ -111,7 +111,7 @@
 #define SG_HOOK_FLUSH_SLOT(s2, real) (real)
 #endif
 
-// ---- sjoin.hip
+// ---- sjoin.hip (the key-pair kernel), sjoin_f64pair.hpp (f64pair_stage), sjoin.hpp (sorted_find)
 #if SJ_EXPERIMENT == 1
 #define SJ_HOOK_SEARCH_RANGE(lo, hi) hi = 0
 #else

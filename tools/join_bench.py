@@ -20,7 +20,10 @@ CSRC = os.path.join(ROOT, "surel_plus_amd", "csrc")
 FLAGS = "-O3 -std=c++17 -fPIC --offload-arch=gfx950 -fhip-fp32-correctly-rounded-divide-sqrt -ffp-contract=off".split()
 
 
-def build(flags, name, files=("sjoin.hip",)):
+JOIN_FILES = ("sjoin.hip", "sjoin_sizes.hip", "sjoin_f64stage.hip", "sjoin_forms.hip")      # the join's translation units
+
+
+def build(flags, name, files=JOIN_FILES):
     out = os.path.join(ROOT, "tools", "build", f"libsubgacc_{name}.so")
     os.makedirs(os.path.dirname(out), exist_ok=True)
     objs = [os.path.join(CSRC, "build", f) for f in os.listdir(os.path.join(CSRC, "build")) if f.endswith(".o") and f[:-2] + ".hip" not in files]
@@ -139,7 +142,7 @@ def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--one-store":
         return one_store(sys.argv[2], int(sys.argv[3]))
     if len(sys.argv) > 1 and sys.argv[1] == "--build":
-        return build(sys.argv[2], sys.argv[3], tuple(sys.argv[4].split(",")) if len(sys.argv) > 4 else ("sjoin.hip",))
+        return build(sys.argv[2], sys.argv[3], tuple(sys.argv[4].split(",")) if len(sys.argv) > 4 else JOIN_FILES)
     if len(sys.argv) > 1 and sys.argv[1] == "--one":
         return one(sys.argv[2], int(sys.argv[3]))
     opts = dict(a[2:].split("=", 1) for a in sys.argv[1:] if a.startswith("--") and "=" in a)
