@@ -733,6 +733,57 @@ int subgacc_keyrows_compact(const int32_t *row_ids, const int32_t *row_keys, con
 int subgacc_keyrows_translate(int32_t *data_inout, int64_t n, const int64_t *n_dev, void *uniq_table, int64_t uniq_capacity,
                               const uint64_t *ukeys, const int64_t *n_ukeys, int64_t max_ukeys, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The count form over the key rows of an on-demand step (ABI 7, backward compatible additions).  A step that samples, joins and drops
+ * its batch (subgacc_walk_spg with uniq_table = NULL: rows of 32-bit LP keys) has neither the table of distinct LP rows nor their
+ * numbering, which the count form of the join -- and with it the mean first stage, model.py:78-83 as (C @ MLP(Z_SF)) / sizes -- indexes
+ * its columns by.  These two entry points give the step both, without xz [R,2,k] and without a resident store.
+ *
+ * subgacc_keyrows_columns: one column per DISTINCT LP key of the rows row_keys[i*stride, +nsize[i]), i < n (the strided key rows of a
+ * step; a length beyond `stride` is read as `stride`), for table_rows = T >= 2 columns, column 0 being "partner absent":
+ *   out_ukeys  int32 [T-1]    the distinct keys of all rows, ascending as unsigned integers (entries past the count: 0)
+ *   out_count  int64 [1]      their number c, on the device
+ *   out_feat   f32 [T, m+1]   row 0 zero (random_walks.py:81); row 1+i = out_ukeys[i] unpacked as subgacc_unpack_lp does it (float(count) /
+ *                             float(M), main.py:174; column 0 = 1 on a root's own row): bit for bit the rows of xz; rows past c zero
+ * A column is the RANK of its key among the batch's distinct keys -- not a hash slot, not a first-occurrence number (subg_acc.c:957-978
+ * numbers by first appearance: a function of the order of the roots) --, so columns, counts and everything computed from them are the
+ * same bits for every schedule, walk order and root dedup.  More than T-1 distinct keys: flags[2] |= 1 (the meaning this word has for a
+ * full table of distinct rows), out_count = T-1, the T-1 smallest keys are kept (unless even the set of 2T..4T slots overflowed: then
+ * some T-1 keys) and nothing is written out of bounds.  flags: int32[4], caller zeroes.
+ * Two launches (a streaming pass that dedups per workgroup in LDS and inserts the survivors into a set in HBM; one workgroup that
+ * sorts and unpacks), no host read, no allocation: capturable.  workspace: subgacc_keyrows_columns_workspace_bytes(T) bytes (0 for a
+ * T the call refuses), ZEROED ONCE by its owner before the first call -- every call leaves it zeroed for the next (one workspace serves
+ * one stream at a time).
+ * Refused before anything is launched, with a message that starts with "keyrows_columns: ": T < 2, n < 0, stride <= 0, num_walks or
+ * num_steps < 1, a key of more than 31 bits (num_steps*SHIFT+1 > 31), a NULL out_ukeys / out_count / out_feat / flags / workspace, NULL
+ * row_keys / nsize with n > 0 (SUBGACC_ERR_BADARG); T > 16,384 (the keys are sorted in LDS: SUBGACC_ERR_LDS); a workspace that is too
+ * small (SUBGACC_ERR_WORKSPACE). */
+size_t subgacc_keyrows_columns_workspace_bytes(int64_t table_rows);
+int subgacc_keyrows_columns(const int32_t *row_keys, const int32_t *nsize, int64_t n, int32_t stride, int32_t num_walks,
+                            int32_t num_steps, int64_t table_rows, int32_t *out_ukeys, int64_t *out_count, float *out_feat,
+                            int32_t *flags, void *workspace, size_t workspace_bytes, void *stream);
+
+/* subgacc_sjoin_key_counts: SUBGACC_JOIN_COUNTS over those rows -- out_counts f32 [S, T] is exactly what the count form writes for an
+ * SFptr store whose LP row 1+i is ukeys[i]: entry [j, 1+i] = how often key ukeys[i] occurs in either feature slot of segment j, entry
+ * [j, 0] = the members of segment j without a partner, columns past *n_keys zero; so segment_sum_j(MLP(xz).sum(-2)) == out_counts[j] @
+ * MLP(out_feat) (model.py:78-83; HONet, model_horder.py:56-57, with own = [u | w | v | w], S = 4B).  out_len (optional; int32 [S])
+ * receives the length of every segment's own row, the mean's divisor.
+ *   d        payload_kind = SUBGACC_JOIN_KEY32, strided rows (row_len, row_stride, ids, payload = the keys), own / partner (partner may
+ *            be NULL), pair_block = P > 0, S a multiple of 2*P (any number of mirrored blocks: segment j = (p / P) * 2 * P + p % P of pair
+ *            p), table_rows = T, num_walks, num_steps, flags (int32[4], caller zeroes); no out_* field, no seg, no option bit.
+ *   ukeys    int32 [T-1] ascending (unsigned), n_keys int64 [1] on the device: out_ukeys / out_count of subgacc_keyrows_columns (at most
+ *            min(*n_keys, T-1) keys are read).
+ * The plan of the count form: the longer row of a pair staged, the shorter searched in it once, a hit counted for both blocks, n - hits
+ * added to column 0; the sorted keys lie in LDS and every member's key is mapped to its column once, by a halving search; integer LDS
+ * histograms, no float is added atomically.  Flags: flags[3] |= 2 a key that is not in the list (the feature slot that carries it is not counted; nothing
+ * is read or written out of bounds), |= 1 a row longer than row_stride, |= 4 a list that is not mirrored (the segments of such a pair are
+ * not written), |= 16 a row number outside the store (an empty row).  LDS: 8 row_stride + 12 T + 16 bytes <= 160 KiB, else
+ * SUBGACC_ERR_LDS before anything is launched.  Refused with SUBGACC_ERR_BADARG before anything is launched, besides the descriptor
+ * refusals of every fused stage (subgacc_join_desc): packed or headed rows, a payload other than KEY32, any option bit, T < 2, a NULL
+ * ukeys / n_keys / out_counts. */
+int subgacc_sjoin_key_counts(const subgacc_join_desc *d, const int32_t *ukeys, const int64_t *n_keys, float *out_counts,
+                             int32_t *out_len, void *stream);
+
 /* ABI 4: subgacc_walk_spg over ALL n rows but in the order of a work list (worklist[0 .. *n_work) names every row once:
  * subgacc_worklist_by_root) -- either RNG mode: row i keeps its place in the batch AND in the rand_r stream (rng_pos[i] /
  * rng_seed[i] from subgacc_rng_positions over the n roots in batch order; NULL for Philox), only the order in which the kernel

@@ -244,6 +244,7 @@ class SampledSets:
     _kcap: int = 0
     _kcount: torch.Tensor = None  # ... and the number of distinct rows, on the device
     _join_flags: torch.Tensor = None   # sample_and_gather(lazy=True): the join's int32[4] status words (resolve() checks them)
+    _table_rows: int = None      # a step with stage="counts": the columns of its count form (table_rows - 1 distinct LP rows at most)
 
     # ------------------------------------------------------------------ lazy bookkeeping
     @property
@@ -296,11 +297,16 @@ class SampledSets:
             if len(st) > 5:             # root dedup: the sets of the distinct endpoints are fewer than the join's rows
                 self.n_distinct = int(st[5])
             st = unpack_status(st[1:4] + st[:1])
+            if self._table_rows is not None:    # stage="counts": no row form ran, the row-count word was never written
+                self.extra = None
         else:
             self.extra = st[self.status.numel():]
             st = unpack_status(st[: self.status.numel()])
         self.status = None
         check_walk_flags(self, st[:4])
+        if st[2] and self._table_rows is not None:
+            raise _lib.SubgAccError(f"the step had more than table_rows - 1 = {self._table_rows - 1} distinct LP rows: its counts have "
+                                    "no column for the others; run it again with a larger table_rows")
         if st[2]:
             raise _lib.SubgAccError("the table of distinct LP rows overflowed: sample again with a larger "
                                     "uniq_capacity (or lazy=False, which retries by itself)")

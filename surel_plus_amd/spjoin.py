@@ -4,7 +4,8 @@ Reference: train.py:13-45 (gather), :48-72 (hgather), :75-85 (bgather), :88-111 
 same argument meaning, same return values (xz float32 [R,2,k], indptr-or-segment-ids int64 on `device`);
 `x` is an SpG (surel_plus_amd.spg.SpG) or a scipy CSR (uploaded once and cached), `encode` the Z_SF table
 as a float32 CUDA tensor or None for a float payload.  The work is done by csrc/sjoin.hip (the row form),
-csrc/sjoin_sizes.hip (the size pass), csrc/sjoin_f64stage.hip and csrc/sjoin_forms.hip (the fused stages, the count and pair forms).
+csrc/sjoin_sizes.hip (the size pass), csrc/sjoin_f64stage.hip and csrc/sjoin_forms.hip (the fused stages, the count and pair forms),
+csrc/keycols.hip (the count form over the key rows of an on-demand step).
 """
 import ctypes
 import os
@@ -512,11 +513,27 @@ class StepBuffers:
     with, main.py:217) into a buffer of its own, `segid` int64 [worst case rows]; one batch per step (batch=None).
     triplets=True: the step of sample_and_hgather -- `pairs` triplets (u, v, w), 3B roots walked once each, 4B segments
     [U|w ; W|u ; V|w ; W|v] (train.py:57-68), always with segment ids; dedup_roots=True takes the prologue that knows the roles
-    (subgacc_step_prologue_dedup_roles); Philox only (the reference never samples triplets in a stream), one batch per step."""
+    (subgacc_step_prologue_dedup_roles); Philox only (the reference never samples triplets in a stream), one batch per step.
+    stage="counts": the step of sample_and_counts / sample_and_hcounts (and of sample_and_mean_stage / sample_and_hmean_stage) --
+    prologue, work list, walk, then the columns of the step's LP keys (subgacc_keyrows_columns) and the count form of the join over the
+    key rows (subgacc_sjoin_key_counts): no size pass, no scan, no row form.  Instead of `out` and `segid` the buffers hold `counts`
+    float32 [S, table_rows], `sizes` int32 [S], `ukeys` int32 [table_rows - 1] and `feat` float32 [table_rows, m+1]; table_rows - 1 is
+    the number of distinct LP rows a step may show (more: sets.resolve() raises and names table_rows).  Needs 32-bit key rows and one
+    batch per step (ValueError otherwise, before any device work)."""
 
     def __init__(self, csr, pairs, num_walks=200, num_steps=3, uniq_capacity=1 << 17, out=None, dedup_roots=False, rng="philox",
-                 key_rows=True, sort_roots=True, batch=None, align_rows=True, order=None, ptr=True, triplets=False):
+                 key_rows=True, sort_roots=True, batch=None, align_rows=True, order=None, ptr=True, triplets=False, stage=None,
+                 table_rows=2048):
         from .sampler import FUSED_MAX_Q, as_rank
+        self.stage, self.T = stage, int(table_rows)
+        if stage not in (None, "counts"):
+            raise ValueError(f"StepBuffers: stage is None (the row form) or 'counts', not {stage!r}")
+        if stage == "counts":       # refused before anything touches the device
+            _counts_stage_shape("StepBuffers(stage='counts')", num_walks, num_steps, key_rows, self.T)
+            if batch is not None and int(batch) != int(pairs):
+                raise ValueError("StepBuffers(stage='counts'): the columns are those of one batch (batch=None)")
+            if out is not None or not ptr:
+                raise ValueError("StepBuffers(stage='counts') writes no rows: it takes neither out= nor ptr=False")
         L, dev = lib(), csr.device
         # order=LocalityOrder / int32 rank: the walk kernel takes the rows in ascending rank of their root (subgacc_worklist_by_rank),
         # the deduplicated step its first occurrences too; self.walk_order says which order the last step ran
@@ -582,12 +599,51 @@ class StepBuffers:
             self.worklist = torch.empty(n, dtype=torch.int32, device=dev)
             self.dedup_ws = torch.zeros(L.subgacc_step_dedup_workspace_bytes(n), dtype=torch.uint8, device=dev)
             self.dedup_steps = 0
+        if stage == "counts":       # counts, sizes, the sorted keys and their feature rows; no output rows, no segment ids, no size pass
+            T = self.T
+            self.counts = self._counts_buffer(S, T, dev)
+            self.sizes = torch.empty(S, dtype=torch.int32, device=dev)
+            self.ukeys = torch.empty(T - 1, dtype=torch.int32, device=dev)
+            self.feat = torch.empty((T, self.k), dtype=torch.float32, device=dev)
+            self.col_ws = torch.zeros(L.subgacc_keyrows_columns_workspace_bytes(T), dtype=torch.uint8, device=dev)   # zeroed once
+            self.ws = self.out = self.segid = None
+            return
         self.ws = torch.empty(max(L.subgacc_sjoin_workspace_bytes(S), 8), dtype=torch.uint8, device=dev)
         self.feat = None if self.keyrows else torch.empty((self.capacity + 1, self.k), dtype=torch.float32, device=dev)
         if out is not None:         # room for the worst case: S segments (2B; triplets: 4B) of M*m+1 members
             _out_view(out, dev, self.k, worst=S * self.Q)
         self.out = out if out is not None else torch.empty(S * self.Q * 2 * self.k, dtype=torch.float32, device=dev)
         self.segid = None if self.ptr else torch.empty(S * self.Q, dtype=torch.int64, device=dev)
+
+    def _counts_buffer(self, S, T, dev):
+        """stage="counts": the step's C [S, table_rows]"""
+        return torch.empty((S, T), dtype=torch.float32, device=dev)
+
+
+class _FitStepBuffers(StepBuffers):
+    """The buffers sample_and_counts makes for ONE call without table_rows: columns for as many distinct LP rows as the columns pass
+    holds (keys, feature rows and workspace: 0.5 MB) and no C -- the count kernel writes a tensor of exactly c + 1 columns, allocated
+    once c has been read back (_counts_tail(fit=True)).  Never handed out."""
+
+    def _counts_buffer(self, S, T, dev):
+        return None
+
+
+COUNTS_MAX_TABLE_ROWS = 16384      # subgacc_keyrows_columns sorts the distinct keys of a step in LDS
+
+
+def _counts_stage_shape(who, num_walks, num_steps, key_rows, table_rows):
+    """what the count stage of a step refuses before any device work: a shape without 32-bit key rows, key_rows=False, a table_rows
+    the columns pass does not hold"""
+    from .sampler import key_rows_form
+    if not key_rows:
+        raise ValueError(f"{who} runs over the key rows of the step: key_rows=False has none")
+    form = key_rows_form(int(num_walks), int(num_steps))
+    if form != 32:
+        raise ValueError(f"{who} needs 32-bit LP keys: num_walks = {num_walks}, num_steps = {num_steps} " +
+                         ("has 64-bit keys (key_rows_form == 64)" if form == 64 else "has no key-rows form"))
+    if not 2 <= int(table_rows) <= COUNTS_MAX_TABLE_ROWS:
+        raise ValueError(f"{who}: table_rows = {table_rows} (2 .. {COUNTS_MAX_TABLE_ROWS}: column 0 and one column per distinct LP row)")
 
 
 def _dedup_tick(bufs):
@@ -599,9 +655,62 @@ def _dedup_tick(bufs):
         bufs.dedup_steps = 0
 
 
-def _buffered_step(csr, e, bufs, seed, out):
-    """sample_and_gather / sample_and_hgather through a StepBuffers: six launches, nothing allocated, nothing read back"""
-    from .sampler import SampledSets, _timed, _walk, make_cfg, sorted_worklist, walk_kernel_name, worklist_buffers
+def _step_sets(csr, bufs, cfg, rr, step_id):
+    """the SampledSets of a buffered step: views of the step's buffers, lazily resolved"""
+    from .sampler import SampledSets
+    kr = bufs.keyrows
+    sets = SampledSets(bufs.nsize, None, bufs.ids, None, None, None, bufs.M, bufs.m, bufs.stride, None)
+    sets.slot, sets.table, sets.capacity, sets.strided = bufs.slot, bufs.table, (0 if kr else bufs.capacity), True
+    if kr:
+        sets.keyrows, sets.key64 = True, bufs.key64
+        # number() registers the keys of the rows as they stand in the buffers (root dedup: the rows of repeated endpoints are
+        # empty, and a repeated endpoint never is the first to show an LP row, so the numbering is the one of the whole batch);
+        # once the buffers have taken a later batch -- or a captured step has been replayed -- the answer would describe that
+        # batch, so it is refused (stamp of the step that made these sets against the buffers' current one)
+        sets._keyctx = {"csr": csr, "roots": bufs.roots, "cfg": cfg, "rng_pos": bufs.rng_pos if rr else None,
+                        "rng_seed": bufs.rng_seed if rr else None, "capacity": bufs.capacity,
+                        "fresh": lambda: getattr(bufs, "step_id", 0) == step_id}
+    # every set of a buffered step -- key rows or table form -- is a view of buffers that the NEXT step overwrites: what is computed
+    # from them on demand (the member count of a deduplicated step, X / nnz) is refused once they hold a later batch
+    sets._fresh = lambda: getattr(bufs, "step_id", 0) == step_id
+    sets.status, sets._tail = bufs.status, bufs.tail[bufs.S: bufs.S + (6 if bufs.dedup else 5)]
+    sets._rows_are_members = not bufs.triplets       # (the rows of w are joined twice: the join's rows are not the members)
+    sets.walk_order = bufs.walk_order
+    if bufs.stage == "counts":      # no row form ran: the join's row count is not there, the members are counted on demand
+        sets._rows_are_members, sets._table_rows = False, bufs.T
+    return sets
+
+
+def _counts_tail(bufs, own, partner, flags, st, fit):
+    """the end of a step with stage="counts": the columns of the step's LP keys, then the count form over the key rows -- three
+    launches, nothing allocated, nothing read back -> (C, table), views of the buffers.  fit (sample_and_counts without buffers and
+    without table_rows): the number of distinct LP rows c is read back once and the count kernel runs with T = c + 1 columns into a
+    tensor of that width, so that the GEMM behind it has no dead column."""
+    L = lib()
+    n, S, T = bufs.n, bufs.S, bufs.T
+    count = bufs.status[2:3]        # the status word `distinct rows`: resolve() reads it with the flags
+    with _timed("keyrows_columns"):
+        check(L.subgacc_keyrows_columns(ptr(bufs.slot), ptr(bufs.nsize), n, bufs.stride, bufs.M, bufs.m, T, ptr(bufs.ukeys), ptr(count),
+                                        ptr(bufs.feat), ptr(flags), ptr(bufs.col_ws), bufs.col_ws.numel(), st))
+    C = bufs.counts
+    if fit:
+        words = bufs.status.tolist()
+        if (words[1] & 0xFFFFFFFF) & 1:
+            raise _lib.SubgAccError(f"this batch has more than {T - 1} distinct LP rows: the count form has no column for them "
+                                    f"(table_rows = {T} is the most the columns pass holds; use the row form, sample_and_gather)")
+        T = max(int(words[2]) + 1, 2)
+        C = torch.empty((S, T), dtype=torch.float32, device=bufs.sizes.device)
+    d = _lib.join_desc(JOIN_COUNTS, JOIN_KEY32, row_len=bufs.nsize, n_rows=n, row_stride=bufs.stride, ids=bufs.ids, payload=bufs.slot,
+                       own=own, partner=partner, S=S, pair_block=bufs.batch, table_rows=T, num_walks=bufs.M, num_steps=bufs.m, flags=flags)
+    with _timed("sjoin_key_counts"):
+        check(L.subgacc_sjoin_key_counts(ctypes.byref(d), ptr(bufs.ukeys), ptr(count), ptr(C), ptr(bufs.sizes), st))
+    return C, bufs.feat[:T]
+
+
+def _buffered_step(csr, e, bufs, seed, out, fit=False):
+    """sample_and_gather / sample_and_hgather through a StepBuffers: six launches, nothing allocated, nothing read back
+    (StepBuffers(stage="counts"): the step of sample_and_counts / sample_and_hcounts -> (C, sizes, table, sets); fit: _counts_tail)"""
+    from .sampler import _timed, _walk, make_cfg, sorted_worklist, walk_kernel_name, worklist_buffers
     L, st, dev = lib(), stream_ptr(), csr.device
     B, M, m, k, n, S = bufs.B, bufs.M, bufs.m, bufs.k, bufs.n, bufs.S      # n roots (rows), S segments
     PB = bufs.batch              # pairs per mirrored block of the segment list
@@ -662,6 +771,10 @@ def _buffered_step(csr, e, bufs, seed, out):
         own, partner = _triplet_segments(B, dev), None
     else:
         own, partner = _arange_segments(B, dev, PB)
+    if bufs.stage == "counts":
+        C, table = _counts_tail(bufs, own, partner, flags, st, fit)
+        bufs.sets = _step_sets(csr, bufs, cfg, rr, step_id)      # the step's status: what a caller of the stage functions resolves
+        return C, bufs.sizes, table, bufs.sets
     check(L.subgacc_sjoin_sizes_rows(ptr(bufs.nsize), n, ptr(own), ptr(partner), S, ptr(bufs.seg), ptr(flags), ptr(bufs.ws),
                                      bufs.ws.numel(), st))
     if kr:
@@ -674,23 +787,7 @@ def _buffered_step(csr, e, bufs, seed, out):
     with _timed("sjoin_fill"):
         join_fill(JOIN_ROWS, kind, st, row_len=bufs.nsize, n_rows=n, row_stride=bufs.stride, ids=bufs.ids, payload=bufs.slot, own=own,
                   partner=partner, S=S, seg=bufs.seg, pair_block=PB, out_xz=xz, out_segid=bufs.segid, flags=flags, **payload)
-    sets = SampledSets(bufs.nsize, None, bufs.ids, None, None, None, M, m, bufs.stride, None)
-    sets.slot, sets.table, sets.capacity, sets.strided = bufs.slot, bufs.table, (0 if kr else bufs.capacity), True
-    if kr:
-        sets.keyrows, sets.key64 = True, bufs.key64
-        # number() registers the keys of the rows as they stand in the buffers (root dedup: the rows of repeated endpoints are
-        # empty, and a repeated endpoint never is the first to show an LP row, so the numbering is the one of the whole batch);
-        # once the buffers have taken a later batch -- or a captured step has been replayed -- the answer would describe that
-        # batch, so it is refused (stamp of the step that made these sets against the buffers' current one)
-        sets._keyctx = {"csr": csr, "roots": bufs.roots, "cfg": cfg, "rng_pos": bufs.rng_pos if rr else None,
-                        "rng_seed": bufs.rng_seed if rr else None, "capacity": bufs.capacity,
-                        "fresh": lambda: getattr(bufs, "step_id", 0) == step_id}
-    # every set of a buffered step -- key rows or table form -- is a view of buffers that the NEXT step overwrites: what is computed
-    # from them on demand (the member count of a deduplicated step, X / nnz) is refused once they hold a later batch
-    sets._fresh = lambda: getattr(bufs, "step_id", 0) == step_id
-    sets.status, sets._tail = bufs.status, bufs.tail[S: S + (6 if bufs.dedup else 5)]
-    sets._rows_are_members = not bufs.triplets       # (the rows of w are joined twice: the join's rows are not the members)
-    sets.walk_order = bufs.walk_order
+    sets = _step_sets(csr, bufs, cfg, rr, step_id)
     # ptr=False / triplets: the ids of the first seg[-1] rows (as xz: a view of the whole buffer, the row count stays on the device)
     return xz, (bufs.seg if bufs.ptr else _with_pointers(bufs.segid[: xz.shape[0]], bufs.seg)), sets
 
@@ -721,9 +818,10 @@ def sample_and_gather(csr, edge, num_walks=200, num_steps=3, seed=111413, rng="p
         raise ValueError("sample_and_gather: edge must be [2, B] (many batches at once: sample_and_gather_many)")
     B = e.shape[-1]
     if buffers is not None:     # the allocation-free form of a serving loop: same rows, same (xz, indptr), lazily resolved
-        if buffers.triplets or bool(ptr) != buffers.ptr:
+        if buffers.triplets or bool(ptr) != buffers.ptr or buffers.stage is not None:
             raise ValueError("buffers= were made for another result: StepBuffers(..., ptr=False) serves ptr=False, "
-                             "StepBuffers(..., triplets=True) serves sample_and_hgather")
+                             "StepBuffers(..., triplets=True) serves sample_and_hgather, StepBuffers(..., stage='counts') "
+                             "sample_and_counts")
         if (dedup_roots and not buffers.dedup) or rng != buffers.rng or strided is False or kw.get("fused") is False or \
                 kw.get("bucket", -1) > 0 or (num_walks, num_steps) != (buffers.M, buffers.m) or \
                 kw.get("uniq_capacity", buffers.capacity) != buffers.capacity:
@@ -787,8 +885,8 @@ def sample_and_hgather(csr, hedge, num_walks=200, num_steps=3, seed=111413, rng=
     h = _as_triplets(hedge, csr.device, "sample_and_hgather")
     B = h.shape[1]
     if buffers is not None:
-        if not buffers.triplets or (dedup_roots and not buffers.dedup) or (num_walks, num_steps) != (buffers.M, buffers.m) or \
-                kw.get("uniq_capacity", buffers.capacity) != buffers.capacity or kw.get("fused") is False or kw.get("bucket", -1) > 0:
+        if not buffers.triplets or buffers.stage is not None or (dedup_roots and not buffers.dedup) or \
+                (num_walks, num_steps) != (buffers.M, buffers.m) or kw.get("uniq_capacity", buffers.capacity) != buffers.capacity or kw.get("fused") is False or kw.get("bucket", -1) > 0:
             raise ValueError("buffers= serves the triplet step of the shape its StepBuffers(..., triplets=True) were made for (root "
                              "dedup if they were made with dedup_roots=True)")
         if order is not None and (buffers.order is None or order.rank is not buffers.order.rank):
@@ -807,6 +905,87 @@ def sample_and_hgather(csr, hedge, num_walks=200, num_steps=3, seed=111413, rng=
     table = z.slot_table() if sets.strided else sets.feature_table()
     xz, ids = _checked(*sjoin(_as_spg(z), own, None, table, ptr_mode=False, pair_block=B, out=out))
     return xz, ids, sets
+
+
+def _step_counts(who, csr, e, triplets, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers):
+    """sample_and_counts / sample_and_hcounts: the step with stage="counts" through the caller's StepBuffers, or through a set made for
+    this one call"""
+    from .sampler import as_rank
+    order = as_rank(csr, order)
+    if buffers is not None:
+        if buffers.stage != "counts" or buffers.triplets != triplets:
+            raise ValueError(f"{who}: buffers= must be StepBuffers(..., stage='counts'" + (", triplets=True)" if triplets else ")"))
+        if (dedup_roots and not buffers.dedup) or (num_walks, num_steps) != (buffers.M, buffers.m) or \
+                (table_rows is not None and int(table_rows) != buffers.T):
+            raise ValueError(f"{who}: buffers= serves the step its StepBuffers were made for (num_walks, num_steps, table_rows; root "
+                             "dedup if they were made with dedup_roots=True)")
+        if order is not None and (buffers.order is None or order.rank is not buffers.order.rank):
+            raise ValueError("buffers= walks in the order its StepBuffers were made with: pass order= to StepBuffers(...)")
+        return _buffered_step(csr, e, buffers, seed, None)
+    fit = table_rows is None
+    T = COUNTS_MAX_TABLE_ROWS if fit else int(table_rows)
+    _counts_stage_shape(who, num_walks, num_steps, True, T)
+    bufs = (_FitStepBuffers if fit else StepBuffers)(csr, e.shape[1], num_walks=num_walks, num_steps=num_steps, dedup_roots=dedup_roots,
+                                                     order=order, triplets=triplets, stage="counts", table_rows=T)
+    C, sizes, table, sets = _buffered_step(csr, e, bufs, seed, None, fit=fit)
+    sets.resolve()
+    return C, sizes, table, sets
+
+
+def sample_and_counts(csr, edge, num_walks=200, num_steps=3, seed=111413, dedup_roots=False, order=None, table_rows=None, buffers=None):
+    """The count form of the on-demand step: sample the endpoints of `edge` [2, B] and join their key rows as COUNTS ->
+    (C float32 [2B, T], sizes int32 [2B], table float32 [T, m+1], sets).  C[j, p] = how often row p of `table` occurs in either feature
+    slot of segment j (gather()'s segments: left blocks, then right blocks), p = 0 the zero row of a member without a partner; sizes =
+    the segments' row counts; table = [0-row ; the batch's distinct LP rows / M] in ascending order of their packed keys.  The rows
+    gather_counts(edge, z, ...) counts over the all-nodes store z of the same seed are these rows, under the store's own numbering:
+    segment_sum_j(f(xz).sum(-2)) == C[j] @ f(table) for the (xz, indptr) of sample_and_gather.  A column is its key's RANK among the
+    batch's distinct keys, so (C, sizes, table) are the same bits whatever the schedule, the walk order (order=), root dedup
+    (dedup_roots=True: Philox as ever) and whether buffers are used.  Neither xz nor an output buffer of the row form exists.
+    table_rows=None (no buffers): the number of distinct LP rows is read back once and T is exactly that + 1.  table_rows=T: T columns,
+    the columns past the batch's distinct rows zero; more distinct rows than T - 1 raise SubgAccError.
+    buffers=StepBuffers(csr, B, ..., stage="counts", table_rows=T): nothing is allocated and nothing read back (capturable); C, sizes
+    and table are views of the buffers, and sets.resolve() raises SubgAccError naming table_rows when the step had more distinct LP
+    rows than columns (C is then not to be used).  Shapes: 32-bit key rows (2 to 4 hops, num_steps*SHIFT+1 <= 31), rng Philox."""
+    e = _as_rows(edge, csr.device)
+    if e.dim() != 2 or e.shape[0] != 2:
+        raise ValueError(f"sample_and_counts: edge must be [2, B], not {list(e.shape)}")
+    return _step_counts("sample_and_counts", csr, e, False, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers)
+
+
+def sample_and_hcounts(csr, hedge, num_walks=200, num_steps=3, seed=111413, dedup_roots=False, order=None, table_rows=None,
+                       buffers=None):
+    """sample_and_counts for the triplets `hedge` [3, B] (u, v, w) of the higher-order model: 3B roots walked once each, hgather's 4B
+    segments [U|w ; W|u ; V|w ; W|v] -> (C float32 [4B, T], sizes int32 [4B], table, sets); the rows hgather_counts(hedge, z, ...)
+    counts.  buffers=StepBuffers(csr, B, ..., triplets=True, stage="counts", table_rows=T)."""
+    h = _as_triplets(hedge, csr.device, "sample_and_hcounts")
+    return _step_counts("sample_and_hcounts", csr, h, True, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers)
+
+
+def _step_mean(C, sizes, table, sets, embed, blocks):
+    """(C @ embed(table)) / sizes as [blocks, B, H]; a segment of size 0 (a zero row of C) gives a zero row"""
+    out = (C @ embed(table)) / sizes.clamp(min=1).to(torch.float32)[:, None]
+    return out.view(blocks, -1, out.shape[-1])
+
+
+def sample_and_mean_stage(csr, edge, embed, num_walks=200, num_steps=3, seed=111413, dedup_roots=False, order=None, table_rows=None,
+                          buffers=None):
+    """The reference's first model stage for mean aggregation (model.py:78-83: x = pe_embedding(xz).sum(dim=-2); xl, xr =
+    MeanAggregation(x, ptr).view(2, -1, H)) on the on-demand step: (C @ embed(table)) / sizes with (C, sizes, table) =
+    sample_and_counts(csr, edge, ...) -- mean_stage's algebra without a resident store, and without xz [R,2,k] or the [R,2,H]
+    activations.  `embed` is any row-wise module; autograd reaches its parameters through the small [T, H] activation (C is a constant
+    of the batch).  Returns float32 [2, B, H] (left endpoints, right endpoints), empty segments as zero rows.  Without buffers the step
+    is checked before the result is returned.  With buffers= nothing is read back, as for every buffered step: the step's SampledSets
+    are `buffers.sets`, and `buffers.sets.resolve()` (after `.prefetch()`, if the loop queues ahead) raises SubgAccError when the step
+    had more distinct LP rows than table_rows - 1 -- its result is then not to be used."""
+    return _step_mean(*sample_and_counts(csr, edge, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers), embed, 2)
+
+
+def sample_and_hmean_stage(csr, hedge, embed, num_walks=200, num_steps=3, seed=111413, dedup_roots=False, order=None, table_rows=None,
+                           buffers=None):
+    """HONet's first stage (model_horder.py:56-57: scatter_mean(pe_embedding(xz).sum(-2), ind).view(4, -1, H)) on the on-demand triplet
+    step: hmean_stage's algebra over sample_and_hcounts.  Returns float32 [4, B, H] in the order (xu, xwu, xv, xwv); with buffers= the
+    step is checked through `buffers.sets.resolve()`, as for sample_and_mean_stage."""
+    return _step_mean(*sample_and_hcounts(csr, hedge, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers), embed, 4)
 
 
 def sample_and_gather_many(csr, edges, num_walks=200, num_steps=3, seed=111413, rng="philox", out=None, buffers=None, order=None,
