@@ -9,6 +9,10 @@
 //   keycols_finish_kernel   one workgroup: the HBM set into LDS, a bitonic sort, out_ukeys / out_count / out_feat written, the set
 //                           left zeroed for the next call.  A column is the RANK of its key among the batch's distinct keys (ascending,
 //                           unsigned): a function of the batch alone, not of the schedule, the root dedup or the walk order.
+//                           More distinct keys than the T-1 columns: flags[2] |= 1 and the smallest T-1 keys OF THE SET are kept --
+//                           the smallest of the batch while its distinct keys fit the set's slots.  Once they do not, the set
+//                           itself has dropped keys (kc_set_insert), which ones depends on the schedule: what is kept is then
+//                           a sorted subset of the batch's keys with the flag raised, not "the smallest".
 //   sjoin_key_counts_kernel the plan of sjoin_counts_kernel over strided key rows: the sorted keys copied to LDS, every member's key
 //                           mapped to its column once by a halving search, integer LDS histograms (no float is added atomically).
 // (Written out here instead of sharing code with keyrows.hip / sjoin_forms.hip: those kernels stay bit for bit what they were.)
@@ -34,7 +38,8 @@ __device__ __forceinline__ uint32_t kc_mix(uint32_t key) {       // LP keys are 
 }
 
 // The HBM set: `cap` words (a power of two), 0 = free, else key + 1.  A set that is full (more distinct keys than slots) raises
-// flags[2] |= 1 and drops the key: nothing is written outside the set.
+// flags[2] |= 1 and drops the key: nothing is written outside the set.  WHICH keys a full set holds is whichever came first: it
+// depends on the schedule, only "a subset of the batch's keys, flag raised" does not.
 __device__ __forceinline__ void kc_set_insert(uint32_t *set, uint32_t mask, uint32_t key, int32_t *flags) {
     const uint32_t want = key + 1u;
     uint32_t h = kc_mix(key) & mask;
@@ -127,7 +132,7 @@ __global__ __launch_bounds__(kKcSortThreads) void keycols_finish_kernel(uint32_t
         if (a[s] != kKcEmpty && (s + 1 == cap || a[s + 1] == kKcEmpty)) n_found = s + 1;
     __syncthreads();
     int64_t c = n_found;
-    if (c > T - 1) {                                // more distinct LP rows than columns: the smallest T-1 keys are kept
+    if (c > T - 1) {                                // more distinct LP rows than columns: the smallest T-1 keys of the set are kept
         c = T - 1;
         if (tid == 0) atomicOr(&flags[2], 1);
     }

@@ -29,54 +29,78 @@ def world(sp):
 
 
 # ------------------------------------------------------------------------------------------------------------- synthetic key rows
-def _lp_keys(count, seed):
-    """`count` distinct valid LP keys of (M, HOPS): three counts of 8 bits, some with the root's LEAD bit"""
+def _lp_keys(count, seed, M=M, hops=HOPS, shift=SHIFT):
+    """`count` distinct valid LP keys of (M, hops): `hops` counts of `shift` bits (three of 8), some with the root's LEAD bit"""
     rng = np.random.default_rng(seed)
     keys = set()
     while len(keys) < count:
-        c = rng.integers(0, M + 1, 3)
-        k = (int(c[0]) << (2 * SHIFT)) | (int(c[1]) << SHIFT) | int(c[2])
+        c = rng.integers(0, M + 1, hops)
+        k = 0
+        for v in c:
+            k = (k << shift) | int(v)
         if rng.integers(0, 4) == 0:
-            k |= 1 << (HOPS * SHIFT)
+            k |= 1 << (hops * shift)
         if k:
             keys.add(k)
     return np.array(sorted(keys), dtype=np.uint32)
 
 
 class Rows:
-    """strided key rows built on the host: ids ascend inside a row, keys are drawn from `keyset`; every key of the set occurs"""
+    """strided key rows built on the host: ids ascend inside a row, keys are drawn from `keyset`; every key of the set occurs.
+    Without `lens`: the rows of LENS, a disjoint pair and a fully overlapping pair, each row joined with itself and its neighbour.
+    With `lens`: one row of random ids (below `id_space`) per entry, `stride` words apart; `pairs = (a, b)` replaces the list of
+    every row with itself and with its neighbour; `distinct`: a row no longer than the key set holds no key twice (before the keys
+    that make every key of the set stand somewhere are laid over the rows' first members)."""
 
-    def __init__(self, keyset, seed):
+    def __init__(self, keyset, seed, lens=None, stride=STRIDE, pairs=None, distinct=False, id_space=4000):
         rng = np.random.default_rng(seed)
-        self.keyset = keyset
+        self.keyset, self.stride = keyset, stride
         rows = []
-        for L in LENS:
-            rows.append(np.sort(rng.choice(4000, L, replace=False)))
-        rows.append(np.arange(0, 600, 2))                    # disjoint ids: even against odd
-        rows.append(np.arange(1, 601, 2))
-        same = np.sort(rng.choice(4000, 2 * NT + 1, replace=False))
-        rows += [same, same.copy()]                          # full overlap: the same ids, other keys
+        for L in (LENS if lens is None else lens):
+            rows.append(np.sort(rng.choice(id_space, L, replace=False)))
+        if lens is None:
+            rows.append(np.arange(0, 600, 2))                    # disjoint ids: even against odd
+            rows.append(np.arange(1, 601, 2))
+            same = np.sort(rng.choice(4000, 2 * NT + 1, replace=False))
+            rows += [same, same.copy()]                          # full overlap: the same ids, other keys
         self.n = len(rows)
-        self.ids = np.full((self.n, STRIDE), -1, dtype=np.int32)
-        self.keys = np.full((self.n, STRIDE), POISON, dtype=np.uint32)
+        self.ids = np.full((self.n, stride), -1, dtype=np.int32)
+        self.keys = np.full((self.n, stride), POISON, dtype=np.uint32)
         self.len = np.array([len(r) for r in rows], dtype=np.int32)
         at = 0
         for i, r in enumerate(rows):
             self.ids[i, : len(r)] = r
-            k = keyset[rng.integers(0, len(keyset), len(r))]
+            if distinct and len(r) <= len(keyset):
+                k = rng.permutation(keyset)[: len(r)]
+            else:
+                k = keyset[rng.integers(0, len(keyset), len(r))]
             take = min(len(r), len(keyset) - at)              # every key of the set stands somewhere
             k[:take] = keyset[at: at + take]
             at += take
             self.keys[i, : len(r)] = k
         assert at == len(keyset)
-        e, o, x = len(LENS), len(LENS) + 1, len(LENS) + 2
-        a = list(range(self.n)) + list(range(self.n)) + [e, x, 0, 0]
-        b = list(range(self.n)) + [(i + 1) % self.n for i in range(self.n)] + [o, x + 1, 0, len(LENS) - 1]
+        if pairs is not None:
+            a, b = pairs
+        elif lens is not None:
+            a = list(range(self.n)) + list(range(self.n))
+            b = list(range(self.n)) + [(i + 1) % self.n for i in range(self.n)]
+        else:
+            e, o, x = len(LENS), len(LENS) + 1, len(LENS) + 2
+            a = list(range(self.n)) + list(range(self.n)) + [e, x, 0, 0]
+            b = list(range(self.n)) + [(i + 1) % self.n for i in range(self.n)] + [o, x + 1, 0, len(LENS) - 1]
         self.a, self.b = np.array(a), np.array(b)            # with itself, with its neighbour, disjoint, full overlap, empty rows
 
+    @classmethod
+    def of(cls, keys, lens):
+        """rows given as arrays (keys [n, stride] uint32, lens [n]) for the columns pass alone: no ids, no segment list"""
+        self = cls.__new__(cls)
+        self.n, self.stride = keys.shape
+        self.keys, self.len, self.ids = keys, lens.astype(np.int32), None
+        return self
+
     def device(self):
-        return (torch.from_numpy(self.ids.reshape(-1)).cuda(), torch.from_numpy(self.keys.view(np.int32).reshape(-1)).cuda(),
-                torch.from_numpy(self.len).cuda())
+        ids = None if self.ids is None else torch.from_numpy(self.ids.reshape(-1)).cuda()
+        return ids, torch.from_numpy(self.keys.view(np.int32).reshape(-1)).cuda(), torch.from_numpy(self.len).cuda()
 
     def present(self):
         return np.unique(np.concatenate([self.keys[i, : self.len[i]] for i in range(self.n)]))
@@ -106,25 +130,36 @@ def _guarded(n, dtype, fill):
     return torch.full((n + GUARD,), fill, dtype=dtype, device="cuda")
 
 
-def _columns(sp, rows, T):
+def _workspace(nbytes):
+    """a zeroed columns workspace of nbytes with GUARD bytes of 0x5A behind it"""
+    ws = torch.zeros(nbytes + GUARD, dtype=torch.uint8, device="cuda")
+    ws[nbytes:] = 0x5A
+    return ws
+
+
+def _columns(sp, rows, T, M=M, hops=HOPS, ws=None):
+    """the columns pass over `rows`; `ws`: a _workspace() of the caller's (at least as large as T needs), given to the call whole"""
     from surel_plus_amd import _lib
     L = _lib.lib()
     ids, keys, nsize = rows.device()
     ukeys, count = _guarded(T - 1, torch.int32, -7), _guarded(1, torch.int64, -7)
-    feat = _guarded(T * (HOPS + 1), torch.float32, -7.0)
+    feat = _guarded(T * (hops + 1), torch.float32, -7.0)
     flags = torch.zeros(4, dtype=torch.int32, device="cuda")
     nbytes = L.subgacc_keyrows_columns_workspace_bytes(T)
-    ws = torch.zeros(nbytes + GUARD, dtype=torch.uint8, device="cuda")
-    ws[nbytes:] = 0x5A
-    _lib.check(L.subgacc_keyrows_columns(_lib.ptr(keys), _lib.ptr(nsize), rows.n, STRIDE, M, HOPS, T, _lib.ptr(ukeys), _lib.ptr(count),
-                                         _lib.ptr(feat), _lib.ptr(flags), _lib.ptr(ws), nbytes, _lib.stream_ptr()))
+    if ws is None:
+        ws = _workspace(nbytes)
+    else:
+        assert ws.numel() - GUARD >= nbytes
+        nbytes = ws.numel() - GUARD
+    _lib.check(L.subgacc_keyrows_columns(_lib.ptr(keys), _lib.ptr(nsize), rows.n, rows.stride, M, hops, T, _lib.ptr(ukeys),
+                                         _lib.ptr(count), _lib.ptr(feat), _lib.ptr(flags), _lib.ptr(ws), nbytes, _lib.stream_ptr()))
     torch.cuda.synchronize()
-    assert bool((ukeys[T - 1:] == -7).all()) and bool((count[1:] == -7).all()) and bool((feat[T * (HOPS + 1):] == -7.0).all())
+    assert bool((ukeys[T - 1:] == -7).all()) and bool((count[1:] == -7).all()) and bool((feat[T * (hops + 1):] == -7.0).all())
     assert bool((ws[:nbytes] == 0).all()) and bool((ws[nbytes:] == 0x5A).all())       # the workspace is left zeroed, its guard alone
-    return ukeys[: T - 1], count[:1], feat[: T * (HOPS + 1)].view(T, HOPS + 1), flags
+    return ukeys[: T - 1], count[:1], feat[: T * (hops + 1)].view(T, hops + 1), flags
 
 
-def _key_counts(sp, rows, ukeys, count, T, partner=False, want_len=True):
+def _key_counts(sp, rows, ukeys, count, T, partner=False, want_len=True, M=M, hops=HOPS):
     from surel_plus_amd import _lib
     L = _lib.lib()
     ids, keys, nsize = rows.device()
@@ -133,8 +168,8 @@ def _key_counts(sp, rows, ukeys, count, T, partner=False, want_len=True):
     S = own.numel()
     out, olen = _guarded(S * T, torch.float32, -7.0), _guarded(S, torch.int32, -7)
     flags = torch.zeros(4, dtype=torch.int32, device="cuda")
-    d = _lib.join_desc(_lib.JOIN_COUNTS, _lib.JOIN_KEY32, row_len=nsize, n_rows=rows.n, row_stride=STRIDE, ids=ids, payload=keys, own=own,
-                       partner=par, S=S, pair_block=S // 2, table_rows=T, num_walks=M, num_steps=HOPS, flags=flags)
+    d = _lib.join_desc(_lib.JOIN_COUNTS, _lib.JOIN_KEY32, row_len=nsize, n_rows=rows.n, row_stride=rows.stride, ids=ids, payload=keys,
+                       own=own, partner=par, S=S, pair_block=S // 2, table_rows=T, num_walks=M, num_steps=hops, flags=flags)
     _lib.check(L.subgacc_sjoin_key_counts(C.byref(d), _lib.ptr(ukeys), _lib.ptr(count), _lib.ptr(out), _lib.ptr(olen) if want_len else None,
                                           _lib.stream_ptr()))
     torch.cuda.synchronize()
@@ -142,11 +177,11 @@ def _key_counts(sp, rows, ukeys, count, T, partner=False, want_len=True):
     return out[: S * T].view(S, T).cpu().numpy(), olen[:S].cpu().numpy(), flags.cpu().numpy()
 
 
-def _feature_rows(keys):
+def _feature_rows(keys, M=M, hops=HOPS, shift=SHIFT):
     """NumPy restatement of subgacc_unpack_lp(out_f32): float32 divisions by float32(M)"""
     k = keys.astype(np.uint64)
-    cols = [np.where((k >> (HOPS * SHIFT)) & 1, np.float32(M), np.float32(0))]
-    cols += [((k >> ((HOPS - j) * SHIFT)) & 0xFF).astype(np.float32) for j in range(1, HOPS + 1)]
+    cols = [np.where((k >> (hops * shift)) & 1, np.float32(M), np.float32(0))]
+    cols += [((k >> ((hops - j) * shift)) & ((1 << shift) - 1)).astype(np.float32) for j in range(1, hops + 1)]
     return (np.stack(cols, 1).astype(np.float32) / np.float32(M)).astype(np.float32)
 
 
