@@ -784,6 +784,38 @@ int subgacc_keyrows_columns(const int32_t *row_keys, const int32_t *nsize, int64
 int subgacc_sjoin_key_counts(const subgacc_join_desc *d, const int32_t *ukeys, const int64_t *n_keys, float *out_counts,
                              int32_t *out_len, void *stream);
 
+/* subgacc_sjoin_key_counts_attn / _backward: the count form with attentional aggregation (subgacc_sjoin_counts_attn / _backward: the LP
+ * encoder's first stage for --aggr attn, model.py:59-62,78-81) over those rows -- out_w f32 [S, T] is what subgacc_sjoin_counts_attn
+ * writes for an SFptr store whose LP row 1+i is ukeys[i], bit for bit.  Member t of segment j is the index pair (p_t, q_t):
+ *     p_t = 1 + the rank of its own key in ukeys;   q_t = the same for the member of the partner row with the same id, 0 without one
+ * and everything else is subgacc_sjoin_counts_attn's arithmetic in its order: l_t = g[p_t] + g[q_t] (one fp32 add), m_j a max
+ * (order-free), e_t = expf(l_t - m_j) (never __expf), den_j and each sum_t e_t c_t(r) fp32 chains over the own row's members in ascending
+ * id order from 0 (e_t added if p_t = r, then again if q_t = r), one IEEE division; the backward: kappa_j an fmaf chain over the
+ * segment's occurring columns in ascending column order, beta_t = alpha_t ((dW[j, p_t] + dW[j, q_t]) - kappa_j), Dg_j[r] a chain in the
+ * forward's order, dL/dg = sum_j Dg_j.  No float is added atomically; either row of a pair may be the staged one, the bits are the
+ * same.  An empty segment gives a zero row and m_j = den_j = 0.  out_max / out_den (both or neither; f32 [S]) keep m_j and den_j for
+ * the backward; out_len (optional; int32 [S]) receives the length of every segment's own row.
+ *   d        as subgacc_sjoin_key_counts: form SUBGACC_JOIN_COUNTS, payload_kind SUBGACC_JOIN_KEY32, strided rows, own / partner (partner
+ *            may be NULL), pair_block = P > 0, S a multiple of 2*P (any number of mirrored blocks), table_rows = T >= 2, num_walks,
+ *            num_steps, flags (int32[4], caller zeroes); no out_* field, no seg, no option bit.
+ *   ukeys / n_keys   out_ukeys / out_count of subgacc_keyrows_columns (at most min(*n_keys, T-1) keys are read; *n_keys < 0 reads none).
+ *   g        f32 [T].
+ * One 256-lane workgroup per mirrored pair: the sorted keys lie in LDS, every member's key is mapped to its column once by a halving
+ * search, then the layout of subgacc_sjoin_counts_attn's kernel.  Flags: flags[3] |= 2 a key that is not in the list (that slot is read
+ * as column 0, as subgacc_sjoin_counts_attn reads an SFptr outside the table; nothing is read or written out of bounds), |= 1 a row
+ * longer than row_stride, |= 4 a list that is not mirrored (the segments of such a pair are not written), |= 16 a row number outside
+ * the store (an empty row).
+ * LDS: 4 (7 row_stride + 3 T + 2 D + 7) bytes, D = min(2 row_stride, T) (the backward: 6 D) <= 160 KiB, else SUBGACC_ERR_LDS with a
+ * message that names table_rows and the row form; with out_max / out_den given a backward follows, so the backward's LDS must fit too,
+ * else SUBGACC_ERR_LDS from the forward.  (row_stride = 608, T = 2,048: 51,356 B forward, 70,812 B backward.)
+ * Refused before anything is launched, each message led by the function's name: every refusal of subgacc_sjoin_key_counts; a NULL g /
+ * out_w; exactly one of out_max / out_den; for the backward a NULL g / dw / w / max / den / out_dg (SUBGACC_ERR_BADARG); the LDS bound. */
+int subgacc_sjoin_key_counts_attn(const subgacc_join_desc *d, const int32_t *ukeys, const int64_t *n_keys, const float *g, float *out_w,
+                                  float *out_max, float *out_den, int32_t *out_len, void *stream);
+int subgacc_sjoin_key_counts_attn_backward(const subgacc_join_desc *d, const int32_t *ukeys, const int64_t *n_keys, const float *g,
+                                           const float *dw, const float *w, const float *max, const float *den, float *out_dg,
+                                           void *stream);
+
 /* ABI 4: subgacc_walk_spg over ALL n rows but in the order of a work list (worklist[0 .. *n_work) names every row once:
  * subgacc_worklist_by_root) -- either RNG mode: row i keeps its place in the batch AND in the rand_r stream (rng_pos[i] /
  * rng_seed[i] from subgacc_rng_positions over the n roots in batch order; NULL for Philox), only the order in which the kernel

@@ -15,8 +15,10 @@
 //                           a sorted subset of the batch's keys with the flag raised, not "the smallest".
 //   sjoin_key_counts_kernel the plan of sjoin_counts_kernel over strided key rows: the sorted keys copied to LDS, every member's key
 //                           mapped to its column once by a halving search, integer LDS histograms (no float is added atomically).
-// (Written out here instead of sharing code with keyrows.hip / sjoin_forms.hip: those kernels stay bit for bit what they were.)
+// (Written out here instead of sharing code with keyrows.hip / sjoin_forms.hip: those kernels stay bit for bit what they were;
+// the column search, kc_column, is in sjoin_cols.hpp, which keyattn.hip shares.)
 #include "sjoin.hpp"
+#include "sjoin_cols.hpp"
 
 namespace subgacc {
 
@@ -151,18 +153,6 @@ __global__ __launch_bounds__(kKcSortThreads) void keycols_finish_kernel(uint32_t
         }
         out_feat[x] = v;
     }
-}
-
-// The column of `key`: its rank in the sorted LDS array keys[0, n), by halving (the trip count depends on n alone), or -1
-__device__ __forceinline__ int32_t kc_column(const uint32_t *keys, int n, uint32_t key) {
-    int b = 0;
-    const int n0 = n;
-    while (n > 1) {
-        const int h = n >> 1;
-        b = keys[b + h] <= key ? b + h : b;
-        n -= h;
-    }
-    return (n0 > 0 && keys[b] == key) ? b + 1 : -1;
 }
 
 // The count form over strided key rows.  The plan of sjoin_counts_kernel: the longer row T of the pair is staged (ids, and the COLUMN of

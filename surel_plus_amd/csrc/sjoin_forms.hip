@@ -5,6 +5,7 @@
 //                                       softmax-weighted count row W, and its backward (subgacc_sjoin_counts_attn[_backward])
 // The count and pair forms are launched from subgacc_sjoin_fill_v2 (sjoin.hip); subgacc_sjoin_counts_attn / _backward are here.
 #include "sjoin.hpp"
+#include "sjoin_cols.hpp"
 
 namespace subgacc {
 
@@ -107,12 +108,6 @@ struct CountsAttnArgs {
     const float *dw, *w, *max, *den;            // backward
     float *out_dg;
 };
-
-__device__ __forceinline__ int32_t ord_of(float f) {     // a float as an int of the same order (max by integer atomics: exact)
-    const int32_t b = __float_as_int(f);
-    return b >= 0 ? b : b ^ 0x7FFFFFFF;
-}
-__device__ __forceinline__ float float_of(int32_t o) { return __int_as_float(o >= 0 ? o : o ^ 0x7FFFFFFF); }
 
 // LDS of sjoin_counts_attn_kernel in 4-byte words: ids of the staged row, own / partner values and l / e / beta of both blocks, the
 // two table-indexed arrays, the distinct rows of both blocks (the backward: with W and dW in ascending r), 8 words of block state

@@ -519,21 +519,26 @@ class StepBuffers:
     key rows (subgacc_sjoin_key_counts): no size pass, no scan, no row form.  Instead of `out` and `segid` the buffers hold `counts`
     float32 [S, table_rows], `sizes` int32 [S], `ukeys` int32 [table_rows - 1] and `feat` float32 [table_rows, m+1]; table_rows - 1 is
     the number of distinct LP rows a step may show (more: sets.resolve() raises and names table_rows).  Needs 32-bit key rows and one
-    batch per step (ValueError otherwise, before any device work)."""
+    batch per step (ValueError otherwise, before any device work).
+    stage="counts_attn": the step of sample_and_attn_counts / sample_and_attn_stage -- the same launches up to the columns, then the
+    caller's gate g = gate(table) in torch and the attentional count form over the key rows (subgacc_sjoin_key_counts_attn).  The buffers
+    are those of "counts", where `counts` holds the softmax-weighted count rows W, plus `smax` and `sden` float32 [S] (m_j and den_j, kept
+    for the backward, which rejoins the step's rows: it must run before the buffers take their next step).  Same refusals."""
 
     def __init__(self, csr, pairs, num_walks=200, num_steps=3, uniq_capacity=1 << 17, out=None, dedup_roots=False, rng="philox",
                  key_rows=True, sort_roots=True, batch=None, align_rows=True, order=None, ptr=True, triplets=False, stage=None,
                  table_rows=2048):
         from .sampler import FUSED_MAX_Q, as_rank
         self.stage, self.T = stage, int(table_rows)
-        if stage not in (None, "counts"):
-            raise ValueError(f"StepBuffers: stage is None (the row form) or 'counts', not {stage!r}")
-        if stage == "counts":       # refused before anything touches the device
-            _counts_stage_shape("StepBuffers(stage='counts')", num_walks, num_steps, key_rows, self.T)
+        if stage not in (None,) + _COUNT_STAGES:
+            raise ValueError(f"StepBuffers: stage is None (the row form), 'counts' or 'counts_attn', not {stage!r}")
+        if stage in _COUNT_STAGES:  # refused before anything touches the device
+            who = f"StepBuffers(stage='{stage}')"
+            _counts_stage_shape(who, num_walks, num_steps, key_rows, self.T)
             if batch is not None and int(batch) != int(pairs):
-                raise ValueError("StepBuffers(stage='counts'): the columns are those of one batch (batch=None)")
+                raise ValueError(f"{who}: the columns are those of one batch (batch=None)")
             if out is not None or not ptr:
-                raise ValueError("StepBuffers(stage='counts') writes no rows: it takes neither out= nor ptr=False")
+                raise ValueError(f"{who} writes no rows: it takes neither out= nor ptr=False")
         L, dev = lib(), csr.device
         # order=LocalityOrder / int32 rank: the walk kernel takes the rows in ascending rank of their root (subgacc_worklist_by_rank),
         # the deduplicated step its first occurrences too; self.walk_order says which order the last step ran
@@ -599,9 +604,12 @@ class StepBuffers:
             self.worklist = torch.empty(n, dtype=torch.int32, device=dev)
             self.dedup_ws = torch.zeros(L.subgacc_step_dedup_workspace_bytes(n), dtype=torch.uint8, device=dev)
             self.dedup_steps = 0
-        if stage == "counts":       # counts, sizes, the sorted keys and their feature rows; no output rows, no segment ids, no size pass
+        if stage in _COUNT_STAGES:  # counts, sizes, the sorted keys and their feature rows; no output rows, no segment ids, no size pass
             T = self.T
             self.counts = self._counts_buffer(S, T, dev)
+            if stage == "counts_attn":      # m_j and den_j of the softmax, for the backward
+                self.smax, self.sden = (None, None) if self.counts is None else \
+                    (torch.empty(S, dtype=torch.float32, device=dev), torch.empty(S, dtype=torch.float32, device=dev))
             self.sizes = torch.empty(S, dtype=torch.int32, device=dev)
             self.ukeys = torch.empty(T - 1, dtype=torch.int32, device=dev)
             self.feat = torch.empty((T, self.k), dtype=torch.float32, device=dev)
@@ -630,6 +638,7 @@ class _FitStepBuffers(StepBuffers):
 
 
 COUNTS_MAX_TABLE_ROWS = 16384      # subgacc_keyrows_columns sorts the distinct keys of a step in LDS
+_COUNT_STAGES = ("counts", "counts_attn")       # the stages of a step that run over the columns of its LP keys
 
 
 def _counts_stage_shape(who, num_walks, num_steps, key_rows, table_rows):
@@ -676,9 +685,26 @@ def _step_sets(csr, bufs, cfg, rr, step_id):
     sets.status, sets._tail = bufs.status, bufs.tail[bufs.S: bufs.S + (6 if bufs.dedup else 5)]
     sets._rows_are_members = not bufs.triplets       # (the rows of w are joined twice: the join's rows are not the members)
     sets.walk_order = bufs.walk_order
-    if bufs.stage == "counts":      # no row form ran: the join's row count is not there, the members are counted on demand
+    if bufs.stage in _COUNT_STAGES: # no row form ran: the join's row count is not there, the members are counted on demand
         sets._rows_are_members, sets._table_rows = False, bufs.T
     return sets
+
+
+def _step_columns(bufs, flags, st, fit):
+    """the columns of the step's LP keys (subgacc_keyrows_columns: two launches) -> (the count word on the device, T); fit: the
+    number of distinct LP rows c is read back once and T = c + 1"""
+    n, T = bufs.n, bufs.T
+    count = bufs.status[2:3]        # the status word `distinct rows`: resolve() reads it with the flags
+    with _timed("keyrows_columns"):
+        check(lib().subgacc_keyrows_columns(ptr(bufs.slot), ptr(bufs.nsize), n, bufs.stride, bufs.M, bufs.m, T, ptr(bufs.ukeys),
+                                            ptr(count), ptr(bufs.feat), ptr(flags), ptr(bufs.col_ws), bufs.col_ws.numel(), st))
+    if fit:
+        words = bufs.status.tolist()
+        if (words[1] & 0xFFFFFFFF) & 1:
+            raise _lib.SubgAccError(f"this batch has more than {T - 1} distinct LP rows: the count form has no column for them "
+                                    f"(table_rows = {T} is the most the columns pass holds; use the row form, sample_and_gather)")
+        T = max(int(words[2]) + 1, 2)
+    return count, T
 
 
 def _counts_tail(bufs, own, partner, flags, st, fit):
@@ -687,18 +713,10 @@ def _counts_tail(bufs, own, partner, flags, st, fit):
     without table_rows): the number of distinct LP rows c is read back once and the count kernel runs with T = c + 1 columns into a
     tensor of that width, so that the GEMM behind it has no dead column."""
     L = lib()
-    n, S, T = bufs.n, bufs.S, bufs.T
-    count = bufs.status[2:3]        # the status word `distinct rows`: resolve() reads it with the flags
-    with _timed("keyrows_columns"):
-        check(L.subgacc_keyrows_columns(ptr(bufs.slot), ptr(bufs.nsize), n, bufs.stride, bufs.M, bufs.m, T, ptr(bufs.ukeys), ptr(count),
-                                        ptr(bufs.feat), ptr(flags), ptr(bufs.col_ws), bufs.col_ws.numel(), st))
+    n, S = bufs.n, bufs.S
+    count, T = _step_columns(bufs, flags, st, fit)
     C = bufs.counts
     if fit:
-        words = bufs.status.tolist()
-        if (words[1] & 0xFFFFFFFF) & 1:
-            raise _lib.SubgAccError(f"this batch has more than {T - 1} distinct LP rows: the count form has no column for them "
-                                    f"(table_rows = {T} is the most the columns pass holds; use the row form, sample_and_gather)")
-        T = max(int(words[2]) + 1, 2)
         C = torch.empty((S, T), dtype=torch.float32, device=bufs.sizes.device)
     d = _lib.join_desc(JOIN_COUNTS, JOIN_KEY32, row_len=bufs.nsize, n_rows=n, row_stride=bufs.stride, ids=bufs.ids, payload=bufs.slot,
                        own=own, partner=partner, S=S, pair_block=bufs.batch, table_rows=T, num_walks=bufs.M, num_steps=bufs.m, flags=flags)
@@ -709,7 +727,8 @@ def _counts_tail(bufs, own, partner, flags, st, fit):
 
 def _buffered_step(csr, e, bufs, seed, out, fit=False):
     """sample_and_gather / sample_and_hgather through a StepBuffers: six launches, nothing allocated, nothing read back
-    (StepBuffers(stage="counts"): the step of sample_and_counts / sample_and_hcounts -> (C, sizes, table, sets); fit: _counts_tail)"""
+    (StepBuffers(stage="counts"): the step of sample_and_counts / sample_and_hcounts -> (C, sizes, table, sets); fit: _counts_tail;
+    stage="counts_attn": the same with the step's _StepAttnJoin in the place of C)"""
     from .sampler import _timed, _walk, make_cfg, sorted_worklist, walk_kernel_name, worklist_buffers
     L, st, dev = lib(), stream_ptr(), csr.device
     B, M, m, k, n, S = bufs.B, bufs.M, bufs.m, bufs.k, bufs.n, bufs.S      # n roots (rows), S segments
@@ -771,8 +790,12 @@ def _buffered_step(csr, e, bufs, seed, out, fit=False):
         own, partner = _triplet_segments(B, dev), None
     else:
         own, partner = _arange_segments(B, dev, PB)
-    if bufs.stage == "counts":
+    if bufs.stage == "counts_attn":     # (C: the step's _StepAttnJoin -- the gate is the caller's, the kernel runs once it is there)
+        T = _step_columns(bufs, flags, st, fit)[1]
+        C, table = _StepAttnJoin(bufs, own, partner, T, step_id, flags), bufs.feat[:T]
+    elif bufs.stage == "counts":
         C, table = _counts_tail(bufs, own, partner, flags, st, fit)
+    if bufs.stage in _COUNT_STAGES:
         bufs.sets = _step_sets(csr, bufs, cfg, rr, step_id)      # the step's status: what a caller of the stage functions resolves
         return C, bufs.sizes, table, bufs.sets
     check(L.subgacc_sjoin_sizes_rows(ptr(bufs.nsize), n, ptr(own), ptr(partner), S, ptr(bufs.seg), ptr(flags), ptr(bufs.ws),
@@ -907,14 +930,14 @@ def sample_and_hgather(csr, hedge, num_walks=200, num_steps=3, seed=111413, rng=
     return xz, ids, sets
 
 
-def _step_counts(who, csr, e, triplets, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers):
+def _step_counts(who, csr, e, triplets, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers, stage="counts"):
     """sample_and_counts / sample_and_hcounts: the step with stage="counts" through the caller's StepBuffers, or through a set made for
-    this one call"""
+    this one call (stage="counts_attn": sample_and_attn_counts, which checks the step itself once its kernel has run)"""
     from .sampler import as_rank
     order = as_rank(csr, order)
     if buffers is not None:
-        if buffers.stage != "counts" or buffers.triplets != triplets:
-            raise ValueError(f"{who}: buffers= must be StepBuffers(..., stage='counts'" + (", triplets=True)" if triplets else ")"))
+        if buffers.stage != stage or buffers.triplets != triplets:
+            raise ValueError(f"{who}: buffers= must be StepBuffers(..., stage='{stage}'" + (", triplets=True)" if triplets else ")"))
         if (dedup_roots and not buffers.dedup) or (num_walks, num_steps) != (buffers.M, buffers.m) or \
                 (table_rows is not None and int(table_rows) != buffers.T):
             raise ValueError(f"{who}: buffers= serves the step its StepBuffers were made for (num_walks, num_steps, table_rows; root "
@@ -926,9 +949,10 @@ def _step_counts(who, csr, e, triplets, num_walks, num_steps, seed, dedup_roots,
     T = COUNTS_MAX_TABLE_ROWS if fit else int(table_rows)
     _counts_stage_shape(who, num_walks, num_steps, True, T)
     bufs = (_FitStepBuffers if fit else StepBuffers)(csr, e.shape[1], num_walks=num_walks, num_steps=num_steps, dedup_roots=dedup_roots,
-                                                     order=order, triplets=triplets, stage="counts", table_rows=T)
+                                                     order=order, triplets=triplets, stage=stage, table_rows=T)
     C, sizes, table, sets = _buffered_step(csr, e, bufs, seed, None, fit=fit)
-    sets.resolve()
+    if stage == "counts":
+        sets.resolve()
     return C, sizes, table, sets
 
 
@@ -986,6 +1010,153 @@ def sample_and_hmean_stage(csr, hedge, embed, num_walks=200, num_steps=3, seed=1
     step: hmean_stage's algebra over sample_and_hcounts.  Returns float32 [4, B, H] in the order (xu, xwu, xv, xwv); with buffers= the
     step is checked through `buffers.sets.resolve()`, as for sample_and_mean_stage."""
     return _step_mean(*sample_and_hcounts(csr, hedge, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers), embed, 4)
+
+
+class _StepAttnJoin:
+    """the two library calls of sample_and_attn_counts (subgacc_sjoin_key_counts_attn / _backward) over the key rows of ONE step of
+    `bufs`: the descriptor of _counts_tail, the step's stamp.  The backward joins the step's rows again, and with buffers= those rows
+    live until the buffers take their next step: a backward that comes later is refused, never answered from another batch.
+    bufs = None: an empty batch, nothing is launched."""
+
+    def __init__(self, bufs, own, partner, T, step_id, flags, dev=None):
+        self.bufs, self.own, self.partner, self.T, self.step_id, self.flags = bufs, own, partner, int(T), step_id, flags
+        self.S = bufs.S if bufs is not None else 0
+        self.dev = bufs.sizes.device if bufs is not None else dev
+
+    def desc(self):
+        b = self.bufs
+        return _lib.join_desc(JOIN_COUNTS, JOIN_KEY32, row_len=b.nsize, n_rows=b.n, row_stride=b.stride, ids=b.ids, payload=b.slot,
+                              own=self.own, partner=self.partner, S=b.S, pair_block=b.batch, table_rows=self.T, num_walks=b.M,
+                              num_steps=b.m, flags=self.flags)
+
+    def _require_fresh(self, what):
+        now = getattr(self.bufs, "step_id", 0)
+        if now != self.step_id:
+            raise RuntimeError(f"sample_and_attn_counts: the {what} of step {self.step_id} of these StepBuffers ran after they took "
+                               f"step {now}: the rows it joins are gone (run a step's backward before the buffers' next step)")
+
+    def forward(self, g, keep):
+        S, T, dev, b = self.S, self.T, self.dev, self.bufs
+        own = b is None or b.counts is None         # no buffers of the caller's: tensors of this call
+        W = torch.empty((S, T), dtype=torch.float32, device=dev) if own else b.counts.detach()
+        mx = den = None
+        if keep:
+            mx, den = (torch.empty(S, dtype=torch.float32, device=dev), torch.empty(S, dtype=torch.float32, device=dev)) if own \
+                else (b.smax.detach(), b.sden.detach())
+        if b is None:
+            return W, mx, den
+        self._require_fresh("kernel")
+        with _timed("sjoin_key_counts_attn"):
+            d = self.desc()
+            check(lib().subgacc_sjoin_key_counts_attn(ctypes.byref(d), ptr(b.ukeys), ptr(b.status[2:3]), ptr(g), ptr(W), ptr(mx), ptr(den),
+                                                      ptr(b.sizes), stream_ptr()))
+        return W, mx, den
+
+    def backward(self, g, dW, W, mx, den):
+        # zeros, not empty: the kernel writes every row of every pair it joins, but a pair that raises a flag is left unwritten, Dg is
+        # summed over the segments at once and a buffered step reads no flag back before that sum
+        Dg = torch.zeros_like(W)
+        b = self.bufs
+        if b is None:
+            return Dg
+        self._require_fresh("backward")
+        with _timed("sjoin_key_counts_attn_backward"):
+            d = self.desc()
+            check(lib().subgacc_sjoin_key_counts_attn_backward(ctypes.byref(d), ptr(b.ukeys), ptr(b.status[2:3]), ptr(g), ptr(dW), ptr(W),
+                                                               ptr(mx), ptr(den), ptr(Dg), stream_ptr()))
+        return Dg
+
+
+def _step_attn(who, csr, edge, gate, bias, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers):
+    """sample_and_attn_counts with gate(table, count) -- count: the number of distinct LP rows c, int64 [1] on the device -- and the
+    gate's bias (None: none) as an input of the autograd function -> (W, sizes, table, sets, count)"""
+    e = _as_rows(edge, csr.device)
+    if e.dim() != 2 or e.shape[0] != 2:
+        raise ValueError(f"{who}: edge must be [2, B], not {list(e.shape)}")
+    if e.shape[1] == 0 and buffers is None:     # an empty batch: no step, the zero row alone
+        T = 2 if table_rows is None else int(table_rows)
+        _counts_stage_shape(who, num_walks, num_steps, True, T)
+        dev = csr.device
+        join = _StepAttnJoin(None, None, None, T, 0, None, dev)
+        sizes, table = torch.empty(0, dtype=torch.int32, device=dev), torch.zeros((T, int(num_steps) + 1), dtype=torch.float32, device=dev)
+        sets, count = None, torch.zeros(1, dtype=torch.int64, device=dev)
+    else:
+        join, sizes, table, sets = _step_counts(who, csr, e, False, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers,
+                                                stage="counts_attn")
+        count = join.bufs.status[2:3]
+    g = gate(table, count)
+    if not (torch.is_tensor(g) and g.shape == (join.T,) and g.dtype == torch.float32 and g.device == table.device):
+        raise ValueError(f"{who}: gate(table) must be a float32 [{join.T}] tensor on {table.device}, one logit per row of table")
+    if torch.is_grad_enabled() and (g.requires_grad or (bias is not None and bias.requires_grad)):
+        W = _CountsAttn.apply(g, bias, join)
+    else:
+        W = join.forward(g.detach().contiguous(), False)[0]
+    if buffers is None and sets is not None:
+        sets.resolve()
+    return W, sizes, table, sets, count
+
+
+def sample_and_attn_counts(csr, edge, gate, num_walks=200, num_steps=3, seed=111413, dedup_roots=False, order=None, table_rows=None,
+                           buffers=None):
+    """The attentional count form of the on-demand step: sample the endpoints of `edge` [2, B], number the batch's distinct LP rows as
+    sample_and_counts does, and join the key rows as SOFTMAX-WEIGHTED counts -> (W float32 [2B, T], sizes int32 [2B], table float32
+    [T, m+1], sets).  gate: a callable table -> g float32 [T], the gate's logit of every row of `table` (row 0 = partner absent; the rows
+    past the batch's distinct LP rows are zero rows, whose logits no segment reads).  Member t of segment j is the index pair (p_t,
+    q_t) of its own and its partner's row of `table`, its logit g[p_t] + g[q_t], and
+        W[j, r] = sum_t softmax_j(l)_t ([p_t = r] + [q_t = r])
+    -- what counts_attn_stage's kernel writes over the all-nodes store of the same seed, under the store's own numbering, bit for bit
+    (subgacc_sjoin_key_counts_attn: documented summation chains, no float atomics), so W[j] @ f(table) is the attentional aggregation
+    of f(xz).sum(-2) over segment j.  W is differentiable with respect to g (subgacc_sjoin_key_counts_attn_backward, summed over the
+    segments).  A column is its key's rank: one result whatever the schedule, the walk order, root dedup and buffers.
+    table_rows, buffers=StepBuffers(csr, B, ..., stage="counts_attn", table_rows=T), sets: as for sample_and_counts; without buffers the
+    step is checked (sets.resolve()) before the result is returned.  With buffers nothing is allocated by the sampling part and nothing
+    read back (capturable); W, sizes and table are views of the buffers, and the backward, which joins the step's rows again, must run
+    before the buffers take their next step: later it raises RuntimeError naming the step, it never answers from another batch."""
+    return _step_attn("sample_and_attn_counts", csr, edge, lambda table, count: gate(table), None, num_walks, num_steps, seed, dedup_roots, order, table_rows,
+                      buffers)[:4]
+
+
+def sample_and_attn_stage(csr, edge, embed, gate_nn, value_nn=None, num_walks=200, num_steps=3, seed=111413, dedup_roots=False,
+                          order=None, table_rows=None, buffers=None):
+    """The reference's first model stage of the LP encoder for --aggr attn (model.py:59-62,78-81: x = pe_embedding(xz).sum(dim=-2);
+    xl, xr = AttentionalAggregation(gate_nn, nn)(x, ptr=ptr).view(2, -1, H'')) on the on-demand step -- counts_attn_stage's algebra
+    without a resident store, and without xz [R,2,k], the [R,2,H] activations or the pair rows:
+        E = embed(table),  g = (E - centre) wg,  out_j = nn(W[j] @ E) [n_j > 0]     with (W, sizes, table) = sample_and_attn_counts(...)
+    centre is the detached mean of E over the LIVE rows 0 .. c of the table (c = the batch's distinct LP rows, taken on the device from
+    the step's count word as a mask: nothing is read back): softmax drops the constant, so the result does not depend analytically on
+    table_rows, and the dead rows past c -- embed of a zero row is not zero -- do not move the centre.  embed: any row-wise module;
+    gate_nn: nn.Linear(H, 1) or a one-Linear Sequential; value_nn: None or nn.Linear(H, H'') (PyG 2.2's MLP([H, 1]) / MLP([H, H]) is that
+    Linear, .lins[0]).  Every parameter of embed, gate_nn and value_nn receives a gradient; the gate bias's is exactly zero, as the
+    reference's is analytically.  Returns float32 [2, B, H''] (H without value_nn), empty segments as zero rows.  Keywords as
+    sample_and_attn_counts; with buffers= the step's SampledSets are `buffers.sets` (`.resolve()` raises when the step had more distinct
+    LP rows than table_rows - 1), and the backward must run before the buffers take their next step (RuntimeError otherwise)."""
+    name = "sample_and_attn_stage"
+    other = "sample_and_gather(csr, edge, ...) and the modules on xz"
+    gate = _one_linear(gate_nn, "gate_nn", None, 1, name, other)
+    H = gate.in_features
+    val = _one_linear(value_nn, "value_nn", H, None, name, other) if value_nn is not None else None
+    dev = csr.device
+    for mod in (gate, val, embed):
+        for prm in (mod.parameters() if mod is not None else ()):
+            if prm.device != dev or prm.dtype != torch.float32:
+                raise ValueError(f"{name}: embed, gate_nn and value_nn must hold float32 parameters on the graph's device ({dev})")
+    box = {}
+
+    def logits(table, count):
+        E = box["E"] = embed(table)
+        if E.ndim != 2 or E.shape[0] != table.shape[0] or E.shape[1] != H:
+            raise ValueError(f"{name}: embed(table) is {tuple(E.shape)}, gate_nn takes rows of {H}")
+        live = (torch.arange(table.shape[0], device=dev) <= count).to(torch.float32)        # rows 0 .. c, from the step's count word
+        centre = (E.detach() * live[:, None]).sum(0) / (count + 1).to(torch.float32)
+        return (E - centre) @ gate.weight.view(-1)
+
+    W, sizes, table, sets, _ = _step_attn(name, csr, edge, logits, gate.bias, num_walks, num_steps, seed, dedup_roots, order, table_rows,
+                                          buffers)
+    h = W @ box["E"]
+    if val is not None:
+        h = torch.nn.functional.linear(h, val.weight, val.bias)
+    out = h * (sizes > 0).to(h.dtype)[:, None]
+    return out.view(2, -1, out.shape[-1])
 
 
 def sample_and_gather_many(csr, edges, num_walks=200, num_steps=3, seed=111413, rng="philox", out=None, buffers=None, order=None,
