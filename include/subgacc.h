@@ -816,6 +816,35 @@ int subgacc_sjoin_key_counts_attn_backward(const subgacc_join_desc *d, const int
                                            const float *dw, const float *w, const float *max, const float *den, float *out_dg,
                                            void *stream);
 
+/* subgacc_sjoin_key_index: the index form of the row form over those rows -- out_idx of SUBGACC_JOIN_ROWS, which subgacc_sjoin_fill_v2
+ * writes for SFPTR payloads only, under the numbering of subgacc_keyrows_columns.  It replaces gather(ptr=...)'s rows (train.py:25-30,109)
+ * as the input of the LP encoder's LSTM aggregation (model.py:63-65: subgacc_lstm_aggr runs over these pairs and G = MLP(out_feat) W_ih^T).
+ *   out_idx  int32 [R, 2], 8-byte aligned (a pair leaves as one 8-byte store), R = seg[S]: row seg[j] + t is the index pair (p_t, q_t) of member t of segment j's own row, members in
+ *            ascending id order (gather()'s row order):
+ *                p_t = 1 + the rank of its own key in ukeys;   q_t = the same for the member of the partner row with the same id, 0 without one
+ *            so that out_feat[out_idx[r]] is, bit for bit, row xz[r] of the row form over the same key rows.
+ *   out_len  optional, int32 [S]: the length of every segment's own row.
+ *   d        as subgacc_sjoin_key_counts, with form SUBGACC_JOIN_ROWS: payload_kind SUBGACC_JOIN_KEY32, strided rows (row_len, row_stride,
+ *            ids, payload = the keys), own / partner (partner may be NULL), pair_block = P > 0, S a multiple of 2*P, table_rows = T >= 2,
+ *            num_walks, num_steps, flags (int32[4], caller zeroes); no out_* field, no seg field, no option bit.
+ *   ukeys / n_keys   out_ukeys / out_count of subgacc_keyrows_columns (at most min(*n_keys, T-1) keys are read; *n_keys < 0 reads none).
+ *   seg      int64 [S+1], as subgacc_sjoin_sizes_rows writes it over the same rows and lists: segment j has one output row per member
+ *            of its own row.
+ * One 256-lane workgroup per mirrored pair: the sorted keys lie in LDS and every member's key is mapped to its column once by a halving
+ * search; the longer row of the pair is staged (ids, columns, one word per member for its partner's column), the shorter is searched in
+ * it once -- a hit writes the shorter row's pair and leaves its column in the staged member's word --, and after a barrier the staged
+ * row's pairs leave as coalesced 8-byte stores.  Either row may be the staged one, the output is the same; no atomics on outputs.
+ * Flags: flags[3] |= 2 a key that is not in the list (that slot is written as column 0; nothing is read or written out of bounds), |= 1
+ * a row longer than row_stride, |= 4 a list that is not mirrored (the segments of such a pair are not written), |= 16 a row number
+ * outside the store (an empty row).
+ * LDS: 12 row_stride + 4 T bytes <= 160 KiB, else SUBGACC_ERR_LDS with a message that names table_rows and the row form, before
+ * anything is launched.  (row_stride = 608, T = 2,048: 15,488 B.)
+ * Refused with SUBGACC_ERR_BADARG before anything is launched, each message led by "sjoin_key_index: ": every refusal of
+ * subgacc_sjoin_key_counts; a form other than SUBGACC_JOIN_ROWS; a NULL ukeys / n_keys; a NULL seg / out_idx with S > 0;
+ * an out_idx that is not 8-byte aligned. */
+int subgacc_sjoin_key_index(const subgacc_join_desc *d, const int32_t *ukeys, const int64_t *n_keys, const int64_t *seg,
+                            int32_t *out_idx, int32_t *out_len, void *stream);
+
 /* ABI 4: subgacc_walk_spg over ALL n rows but in the order of a work list (worklist[0 .. *n_work) names every row once:
  * subgacc_worklist_by_root) -- either RNG mode: row i keeps its place in the batch AND in the rand_r stream (rng_pos[i] /
  * rng_seed[i] from subgacc_rng_positions over the n roots in batch order; NULL for Philox), only the order in which the kernel

@@ -40,7 +40,7 @@ SYMBOLS = (
     "subgacc_sjoin_relu_attn", "subgacc_sjoin_relu_attn_backward", "subgacc_sjoin_counts_attn", "subgacc_sjoin_counts_attn_backward",
     "subgacc_lstm_aggr", "subgacc_lstm_aggr_backward", "subgacc_lstm_aggr_hinge", "subgacc_lstm_aggr_hinge_backward",
     "subgacc_keyrows_columns_workspace_bytes", "subgacc_keyrows_columns", "subgacc_sjoin_key_counts",
-    "subgacc_sjoin_key_counts_attn", "subgacc_sjoin_key_counts_attn_backward",
+    "subgacc_sjoin_key_counts_attn", "subgacc_sjoin_key_counts_attn_backward", "subgacc_sjoin_key_index",
 )
 
 
@@ -179,6 +179,7 @@ def lib():
     sig["subgacc_sjoin_key_counts"] = (C.c_int, [C.POINTER(JoinDesc), vp, vp, vp, vp, vp])
     sig["subgacc_sjoin_key_counts_attn"] = (C.c_int, [C.POINTER(JoinDesc), vp, vp, vp, vp, vp, vp, vp, vp])
     sig["subgacc_sjoin_key_counts_attn_backward"] = (C.c_int, [C.POINTER(JoinDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp])
+    sig["subgacc_sjoin_key_index"] = (C.c_int, [C.POINTER(JoinDesc), vp, vp, vp, vp, vp, vp])
     assert set(sig) == set(SYMBOLS)
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

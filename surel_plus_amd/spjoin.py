@@ -523,17 +523,24 @@ class StepBuffers:
     stage="counts_attn": the step of sample_and_attn_counts / sample_and_attn_stage -- the same launches up to the columns, then the
     caller's gate g = gate(table) in torch and the attentional count form over the key rows (subgacc_sjoin_key_counts_attn).  The buffers
     are those of "counts", where `counts` holds the softmax-weighted count rows W, plus `smax` and `sden` float32 [S] (m_j and den_j, kept
-    for the backward, which rejoins the step's rows: it must run before the buffers take their next step).  Same refusals."""
+    for the backward, which rejoins the step's rows: it must run before the buffers take their next step).  Same refusals.
+    stage="index": the step of sample_and_index / sample_and_lstm_stage -- the same launches up to the columns, then the size pass
+    (subgacc_sjoin_sizes_rows) and the index form over the key rows (subgacc_sjoin_key_index): neither xz, nor an output buffer of the row
+    form, nor segment ids.  The buffers are those of "counts" without `counts`, plus `pairs` int32 [S * (M*m+1), 2] (the worst case; the
+    first seg[-1] rows are a step's result) and the size pass's workspace.  Same refusals, and triplets=True (HONet has no LSTM
+    aggregation, model_horder.py:56-57)."""
 
     def __init__(self, csr, pairs, num_walks=200, num_steps=3, uniq_capacity=1 << 17, out=None, dedup_roots=False, rng="philox",
                  key_rows=True, sort_roots=True, batch=None, align_rows=True, order=None, ptr=True, triplets=False, stage=None,
                  table_rows=2048):
         from .sampler import FUSED_MAX_Q, as_rank
         self.stage, self.T = stage, int(table_rows)
-        if stage not in (None,) + _COUNT_STAGES:
-            raise ValueError(f"StepBuffers: stage is None (the row form), 'counts' or 'counts_attn', not {stage!r}")
-        if stage in _COUNT_STAGES:  # refused before anything touches the device
+        if stage not in (None,) + _KEY_STAGES:
+            raise ValueError(f"StepBuffers: stage is None (the row form), 'counts', 'counts_attn' or 'index', not {stage!r}")
+        if stage in _KEY_STAGES:  # refused before anything touches the device
             who = f"StepBuffers(stage='{stage}')"
+            if stage == "index" and triplets:
+                raise ValueError(f"{who} joins pairs: triplets=True has no index form (HONet has no LSTM aggregation)")
             _counts_stage_shape(who, num_walks, num_steps, key_rows, self.T)
             if batch is not None and int(batch) != int(pairs):
                 raise ValueError(f"{who}: the columns are those of one batch (batch=None)")
@@ -604,9 +611,9 @@ class StepBuffers:
             self.worklist = torch.empty(n, dtype=torch.int32, device=dev)
             self.dedup_ws = torch.zeros(L.subgacc_step_dedup_workspace_bytes(n), dtype=torch.uint8, device=dev)
             self.dedup_steps = 0
-        if stage in _COUNT_STAGES:  # counts, sizes, the sorted keys and their feature rows; no output rows, no segment ids, no size pass
+        if stage in _KEY_STAGES:  # counts, sizes, the sorted keys and their feature rows; no output rows, no segment ids (a size pass for "index" alone)
             T = self.T
-            self.counts = self._counts_buffer(S, T, dev)
+            self.counts = self._counts_buffer(S, T, dev) if stage in _COUNT_STAGES else None
             if stage == "counts_attn":      # m_j and den_j of the softmax, for the backward
                 self.smax, self.sden = (None, None) if self.counts is None else \
                     (torch.empty(S, dtype=torch.float32, device=dev), torch.empty(S, dtype=torch.float32, device=dev))
@@ -615,6 +622,9 @@ class StepBuffers:
             self.feat = torch.empty((T, self.k), dtype=torch.float32, device=dev)
             self.col_ws = torch.zeros(L.subgacc_keyrows_columns_workspace_bytes(T), dtype=torch.uint8, device=dev)   # zeroed once
             self.ws = self.out = self.segid = None
+            if stage == "index":    # the index pairs of the worst case, and the size pass in front of them
+                self.pairs = torch.empty((S * self.Q, 2), dtype=torch.int32, device=dev)
+                self.ws = torch.empty(max(L.subgacc_sjoin_workspace_bytes(S), 8), dtype=torch.uint8, device=dev)
             return
         self.ws = torch.empty(max(L.subgacc_sjoin_workspace_bytes(S), 8), dtype=torch.uint8, device=dev)
         self.feat = None if self.keyrows else torch.empty((self.capacity + 1, self.k), dtype=torch.float32, device=dev)
@@ -638,7 +648,8 @@ class _FitStepBuffers(StepBuffers):
 
 
 COUNTS_MAX_TABLE_ROWS = 16384      # subgacc_keyrows_columns sorts the distinct keys of a step in LDS
-_COUNT_STAGES = ("counts", "counts_attn")       # the stages of a step that run over the columns of its LP keys
+_COUNT_STAGES = ("counts", "counts_attn")       # the stages of a step that run over the columns of its LP keys: the count forms
+_KEY_STAGES = _COUNT_STAGES + ("index",)        # ... and the index form
 
 
 def _counts_stage_shape(who, num_walks, num_steps, key_rows, table_rows):
@@ -685,7 +696,7 @@ def _step_sets(csr, bufs, cfg, rr, step_id):
     sets.status, sets._tail = bufs.status, bufs.tail[bufs.S: bufs.S + (6 if bufs.dedup else 5)]
     sets._rows_are_members = not bufs.triplets       # (the rows of w are joined twice: the join's rows are not the members)
     sets.walk_order = bufs.walk_order
-    if bufs.stage in _COUNT_STAGES: # no row form ran: the join's row count is not there, the members are counted on demand
+    if bufs.stage in _KEY_STAGES:   # no row form ran (the index form's row count is its caller's to read): the members are counted on demand
         sets._rows_are_members, sets._table_rows = False, bufs.T
     return sets
 
@@ -725,10 +736,26 @@ def _counts_tail(bufs, own, partner, flags, st, fit):
     return C, bufs.feat[:T]
 
 
+def _index_tail(bufs, own, partner, flags, st, fit):
+    """the end of a step with stage="index": the columns of the step's LP keys, the size pass, then the index form over the key rows --
+    four launches, nothing allocated, nothing read back -> (pairs, table), views of the buffers (fit: as _counts_tail, T = c + 1)"""
+    L = lib()
+    n, S = bufs.n, bufs.S
+    count, T = _step_columns(bufs, flags, st, fit)
+    check(L.subgacc_sjoin_sizes_rows(ptr(bufs.nsize), n, ptr(own), ptr(partner), S, ptr(bufs.seg), ptr(flags), ptr(bufs.ws),
+                                     bufs.ws.numel(), st))
+    d = _lib.join_desc(JOIN_ROWS, JOIN_KEY32, row_len=bufs.nsize, n_rows=n, row_stride=bufs.stride, ids=bufs.ids, payload=bufs.slot,
+                       own=own, partner=partner, S=S, pair_block=bufs.batch, table_rows=T, num_walks=bufs.M, num_steps=bufs.m, flags=flags)
+    with _timed("sjoin_key_index"):
+        check(L.subgacc_sjoin_key_index(ctypes.byref(d), ptr(bufs.ukeys), ptr(count), ptr(bufs.seg), ptr(bufs.pairs), ptr(bufs.sizes), st))
+    return bufs.pairs, bufs.feat[:T]
+
+
 def _buffered_step(csr, e, bufs, seed, out, fit=False):
     """sample_and_gather / sample_and_hgather through a StepBuffers: six launches, nothing allocated, nothing read back
     (StepBuffers(stage="counts"): the step of sample_and_counts / sample_and_hcounts -> (C, sizes, table, sets); fit: _counts_tail;
-    stage="counts_attn": the same with the step's _StepAttnJoin in the place of C)"""
+    stage="counts_attn": the same with the step's _StepAttnJoin in the place of C; stage="index": the step of sample_and_index ->
+    (pairs, indptr, table, sets))"""
     from .sampler import _timed, _walk, make_cfg, sorted_worklist, walk_kernel_name, worklist_buffers
     L, st, dev = lib(), stream_ptr(), csr.device
     B, M, m, k, n, S = bufs.B, bufs.M, bufs.m, bufs.k, bufs.n, bufs.S      # n roots (rows), S segments
@@ -795,9 +822,11 @@ def _buffered_step(csr, e, bufs, seed, out, fit=False):
         C, table = _StepAttnJoin(bufs, own, partner, T, step_id, flags), bufs.feat[:T]
     elif bufs.stage == "counts":
         C, table = _counts_tail(bufs, own, partner, flags, st, fit)
-    if bufs.stage in _COUNT_STAGES:
+    elif bufs.stage == "index":
+        C, table = _index_tail(bufs, own, partner, flags, st, fit)
+    if bufs.stage in _KEY_STAGES:
         bufs.sets = _step_sets(csr, bufs, cfg, rr, step_id)      # the step's status: what a caller of the stage functions resolves
-        return C, bufs.sizes, table, bufs.sets
+        return C, (bufs.seg if bufs.stage == "index" else bufs.sizes), table, bufs.sets
     check(L.subgacc_sjoin_sizes_rows(ptr(bufs.nsize), n, ptr(own), ptr(partner), S, ptr(bufs.seg), ptr(flags), ptr(bufs.ws),
                                      bufs.ws.numel(), st))
     if kr:
@@ -951,7 +980,7 @@ def _step_counts(who, csr, e, triplets, num_walks, num_steps, seed, dedup_roots,
     bufs = (_FitStepBuffers if fit else StepBuffers)(csr, e.shape[1], num_walks=num_walks, num_steps=num_steps, dedup_roots=dedup_roots,
                                                      order=order, triplets=triplets, stage=stage, table_rows=T)
     C, sizes, table, sets = _buffered_step(csr, e, bufs, seed, None, fit=fit)
-    if stage == "counts":
+    if stage != "counts_attn":
         sets.resolve()
     return C, sizes, table, sets
 
@@ -2000,6 +2029,111 @@ def index_lstm_stage(edge, x, encode, embed, lstm):
         join.checked()
     out = h.view(2, -1, H2)
     out.join_flags = join.flags
+    return out
+
+
+def sample_and_index(csr, edge, num_walks=200, num_steps=3, seed=111413, dedup_roots=False, order=None, table_rows=None, buffers=None):
+    """The index form of the on-demand step: sample the endpoints of `edge` [2, B], number the batch's distinct LP rows as
+    sample_and_counts does, and join the key rows as INDEX PAIRS -> (pairs int32 [R, 2], indptr int64 [2B+1], table float32 [T, m+1],
+    sets).  Row indptr[j] + t of `pairs` is (p_t, q_t) for member t of segment j (gather()'s segments and row order: members in ascending
+    node id): p_t the row of `table` of the member's own LP row, q_t that of the member of the partner's set with the same id, 0 -- the
+    zero row -- without one.  table[pairs.long()] is, bit for bit, the xz of sample_and_gather over the same seed, and indptr is its
+    indptr; what gather_index(edge, z) returns over the all-nodes store z of the same seed are these pairs under the store's own
+    numbering.  A column is its key's RANK among the batch's distinct keys, so (pairs, indptr, table) are the same bits whatever the
+    schedule, the walk order (order=), root dedup and whether buffers are used.  Neither xz nor an output buffer of the row form exists:
+    the step writes 8 bytes per row instead of 8 (m+1).
+    table_rows=None (no buffers): the number of distinct LP rows is read back once and T is exactly that + 1.  table_rows=T: T rows, the
+    rows past the batch's distinct LP rows zero; more distinct rows than T - 1 raise SubgAccError.  Without buffers the step is resolved
+    before it returns.
+    buffers=StepBuffers(csr, B, ..., stage="index", table_rows=T): nothing is allocated and nothing read back (capturable); the results
+    are views of the buffers -- `pairs` of the whole buffer, of which the first indptr[-1] rows are the result -- and
+    buffers.sets.resolve() raises SubgAccError naming table_rows when the step had more than T - 1 distinct LP rows (the pairs of the
+    others read row 0; nothing is written out of bounds).  Shapes: 32-bit key rows (2 to 4 hops, num_steps*SHIFT+1 <= 31), rng Philox."""
+    who = "sample_and_index"
+    e = _as_rows(edge, csr.device)
+    if e.dim() != 2 or e.shape[0] != 2:
+        raise ValueError(f"{who}: edge must be [2, B], not {list(e.shape)}")
+    if e.shape[1] == 0 and buffers is None:      # an empty batch: no step, the zero row alone
+        T = 2 if table_rows is None else int(table_rows)
+        _counts_stage_shape(who, num_walks, num_steps, True, T)
+        dev = csr.device
+        return (torch.zeros((0, 2), dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int64, device=dev),
+                torch.zeros((T, int(num_steps) + 1), dtype=torch.float32, device=dev), None)
+    pairs, indptr, table, sets = _step_counts(who, csr, e, False, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers,
+                                              stage="index")
+    if buffers is None:
+        pairs = pairs[: int(indptr[-1].item())]
+    return pairs, indptr, table, sets
+
+
+class _StepLstmJoin(_LstmJoin):
+    """_LstmJoin over the index pairs of ONE step of `bufs` (sample_and_lstm_stage with buffers=): pairs and indptr are views of the
+    buffers and live until the buffers take their next step: a kernel or a backward that comes later is refused, never answered from
+    another batch (_StepAttnJoin._require_fresh's rule)."""
+
+    def __init__(self, pairs, indptr, L, T, H2, bufs, step_id):
+        super().__init__(pairs, indptr, L, T, H2)
+        self.bufs, self.step_id = bufs, step_id
+
+    def _require_fresh(self, what):
+        now = getattr(self.bufs, "step_id", 0)
+        if now != self.step_id:
+            raise RuntimeError(f"sample_and_lstm_stage: the {what} of step {self.step_id} of these StepBuffers ran after they took "
+                               f"step {now}: the pairs it reads are gone (run a step's backward before the buffers' next step)")
+
+    def forward(self, G, b, w_hh, keep):
+        self._require_fresh("kernel")
+        return super().forward(G, b, w_hh, keep)
+
+    def backward(self, G, b, w_hh, hs, cs, dh):
+        self._require_fresh("backward")
+        return super().backward(G, b, w_hh, hs, cs, dh)
+
+
+def sample_and_lstm_stage(csr, edge, embed, lstm, num_walks=200, num_steps=3, seed=111413, dedup_roots=False, order=None,
+                          table_rows=None, buffers=None):
+    """The reference's first model stage of the LP encoder for --aggr lstm (model.py:63-65,78-83: x = pe_embedding(xz).sum(dim=-2);
+    xl, xr = LSTMAggregation(H, H')(x, index=ptr).view(2, -1, H'); main.py:217) on the on-demand step -- index_lstm_stage's algebra
+    without a resident store, and without xz [R,2,k], the packed copy of the step's rows or their registration:
+        E = embed(table),  G = E W_ih^T,  h_j = the recurrence gates = G[p_t] + G[q_t] + b + W_hh h_{t-1} over segment j, padded to L steps
+    with (pairs, indptr, table) = sample_and_index(...) and L = max(the longest segment, 1): the reference pads every segment to the
+    longest of its batch and takes the output at the last position, so L is part of its arithmetic.  The recurrence is subgacc_lstm_aggr
+    (under autograd subgacc_lstm_aggr_backward: dG, db, dW_hh; torch carries dG into embed and W_ih), so every parameter of embed and
+    lstm receives a gradient.  Because a row of `table` is its key's rank, output and gradients are the same bits whatever the
+    schedule, the walk order, root dedup and buffers.
+    embed: any row-wise module [T, m+1] -> [T, H]; lstm: a one-layer, unidirectional, batch_first, proj_size = 0, float32 nn.LSTM(H, H')
+    on the graph's device with hidden_size in 16, 32, .., 128 -- any other takes sample_and_gather(csr, edge, ...) and the modules on xz.
+    Returns float32 [2, B, H'] (left endpoints, right endpoints).  Keywords as sample_and_index.
+    The stage reads two words back, the row count R and L (L sizes the kept states h_t, c_t [2B, L, H']): it is NOT capturable, with or
+    without buffers.  With buffers= the sampling part allocates nothing, the step's SampledSets are `buffers.sets` (`.resolve()` raises
+    when the step had more distinct LP rows than table_rows - 1), and the backward reads the pairs from the buffers: it must run before
+    the buffers take their next step (RuntimeError naming the step otherwise).  The recurrent kernel's status words travel with the
+    result as .join_flags, as index_lstm_stage's do; the stage does not read them."""
+    name = "sample_and_lstm_stage"
+    dev = csr.device
+    w_ih, w_hh, b_ih, b_hh = _lstm_layer(lstm, dev, name, "sample_and_gather(csr, edge, ...) and the modules on xz")
+    H2 = lstm.hidden_size
+    for prm in embed.parameters():
+        if prm.device != dev or prm.dtype != torch.float32:
+            raise ValueError(f"{name}: embed must hold float32 parameters on the graph's device ({dev})")
+    pairs, indptr, table, _ = sample_and_index(csr, edge, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers)
+    S, T = indptr.numel() - 1, int(table.shape[0])
+    E = embed(table)
+    if E.ndim != 2 or E.shape[0] != T or E.shape[1] != lstm.input_size:
+        raise ValueError(f"{name}: embed(table) is {tuple(E.shape)}, the LSTM takes rows of {lstm.input_size}")
+    if S == 0:
+        return E.new_zeros((2, 0, H2))
+    R, L = torch.stack([indptr[-1], (indptr[1:] - indptr[:-1]).max()]).tolist()      # the stage's read-back: two words
+    G = E @ w_ih.t()
+    b = (b_ih + b_hh) if b_ih is not None else None
+    L = max(int(L), 1)
+    join = _LstmJoin(pairs[:R], indptr, L, T, H2) if buffers is None else _StepLstmJoin(pairs[:R], indptr, L, T, H2, buffers, buffers.step_id)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (G, b, w_hh)):
+        h = _LstmAggr.apply(G, b, w_hh, join)
+    else:
+        h = join.forward(G.detach().contiguous(), b.detach().contiguous() if b is not None else None, w_hh.detach().contiguous(), False)[0]
+    out = h.view(2, -1, H2)
+    out.join_flags = join.flags     # the recurrent kernel's status words, not read here: every pair is 1 + a rank < T by construction
     return out
 
 
