@@ -1,4 +1,4 @@
-// keycols.hip -- the count form of the join over the key rows of an on-demand step (gfx950).
+// keycols.hip -- the columns of the key rows of an on-demand step (gfx950).
 //
 // The default step writes key rows: a member's payload is its 32-bit LP key, and there is neither a table of distinct LP rows nor a
 // numbering.  The count form (sjoin_forms.hip: segment j as counts per LP row, so that mean aggregation of the first model stage is
@@ -13,12 +13,8 @@
 //                           the smallest of the batch while its distinct keys fit the set's slots.  Once they do not, the set
 //                           itself has dropped keys (kc_set_insert), which ones depends on the schedule: what is kept is then
 //                           a sorted subset of the batch's keys with the flag raised, not "the smallest".
-//   sjoin_key_counts_kernel the plan of sjoin_counts_kernel over strided key rows: the sorted keys copied to LDS, every member's key
-//                           mapped to its column once by a halving search, integer LDS histograms (no float is added atomically).
-// (Written out here instead of sharing code with keyrows.hip / sjoin_forms.hip: those kernels stay bit for bit what they were;
-// the column search, kc_column, is in sjoin_cols.hpp, which keyattn.hip shares.)
+// The joins that read these columns -- the count form, its attentional form and the index form over key rows -- are in sjoin_keys.hip.
 #include "sjoin.hpp"
-#include "sjoin_cols.hpp"
 
 namespace subgacc {
 
@@ -155,87 +151,6 @@ __global__ __launch_bounds__(kKcSortThreads) void keycols_finish_kernel(uint32_t
     }
 }
 
-// The count form over strided key rows.  The plan of sjoin_counts_kernel: the longer row T of the pair is staged (ids, and the COLUMN of
-// every member: its key is looked up once), the shorter row S is searched in it member by member, a hit counts for both blocks, and
-// n - hits members count for column 0 (partner absent) when the row is written.
-__global__ __launch_bounds__(kPairThreads) void sjoin_key_counts_kernel(const JoinArgs a, int64_t pb, const uint32_t *__restrict__ ukeys,
-                                                                        const int64_t *__restrict__ n_keys, float *__restrict__ out_counts,
-                                                                        int32_t *__restrict__ out_len) {
-    extern __shared__ __align__(16) unsigned char lds_raw[];
-    const int rows = (int)a.table_rows;
-    int32_t *colT = (int32_t *)lds_raw;               // [max_len] column of T's member (-1: its key is not in the list)
-    int32_t *idsT = colT + a.max_len;                 // [max_len]
-    int32_t *histS = idsT + a.max_len;                // [rows]
-    int32_t *histT = histS + rows;                    // [rows]
-    int32_t *nhit = histT + rows;                     // [1]
-    uint32_t *keys = (uint32_t *)(nhit + 1);          // [rows - 1]
-
-    MirroredPair m;
-    if (!mirrored_pair<true>(a, pb, m)) return;
-    const int tid = threadIdx.x;
-    const int ns = m.ns, nt = m.nt;
-    const int64_t sb = m.sb, tb = m.tb, jS = m.jS, jT = m.jT;
-    const int32_t *data = (const int32_t *)a.data;
-    int64_t c64 = *n_keys;
-    const int c = (int)(c64 < 0 ? 0 : (c64 > rows - 1 ? rows - 1 : c64));      // never more keys than columns
-    // S's first members are asked for before anything else: they are on their way while the keys and T are staged
-    constexpr int kTrips = 2;
-    int32_t sid[kTrips];
-    uint32_t skey[kTrips];
-#pragma unroll
-    for (int u = 0; u < kTrips; ++u) {
-        const int r = tid + u * kPairThreads;
-        sid[u] = 0, skey[u] = 0;
-        if (r < ns) sid[u] = stream_load(&a.indices[sb + r]), skey[u] = (uint32_t)stream_load(&data[sb + r]);
-    }
-    for (int x = tid; x < 2 * rows + 1; x += kPairThreads) histS[x] = 0;   // histS, histT and nhit are contiguous
-    for (int x = tid; x < c; x += kPairThreads) keys[x] = ukeys[x];
-    for (int r = tid; r < nt; r += kPairThreads) idsT[r] = stream_load(&a.indices[tb + r]);
-    __syncthreads();
-    for (int r = tid; r < nt; r += kPairThreads) {      // T: every member's column, and its own value
-        const int32_t col = kc_column(keys, c, (uint32_t)stream_load(&data[tb + r]));
-        colT[r] = col;
-        if (col < 0) atomicOr(&a.flags[3], 2);          // a key that is not in the list: not counted
-        else atomicAdd(&histT[col], 1);
-    }
-    __syncthreads();
-    int hits = 0;
-    for (int r0 = 0; r0 < ns; r0 += kPairThreads) {     // S: own value, and -- on a hit -- one partner value for each block
-        const int r = r0 + tid, u = r0 / kPairThreads;
-        if (r >= ns) break;
-        int32_t id;
-        uint32_t key;
-        if (u < kTrips) {
-            id = u == 0 ? sid[0] : sid[1];
-            key = u == 0 ? skey[0] : skey[1];
-        } else {
-            id = stream_load(&a.indices[sb + r]);
-            key = (uint32_t)stream_load(&data[sb + r]);
-        }
-        const int32_t v = kc_column(keys, c, key);
-        int b;
-        const bool hit = sorted_find(idsT, nt, id, true, b);
-        const int32_t pvT = hit ? colT[b] : 0;
-        if (v < 0 || pvT < 0) atomicOr(&a.flags[3], 2);     // a key that is not in the list: that feature slot is not counted
-        if (v >= 0) atomicAdd(&histS[v], 1);
-        if (hit) {
-            if (pvT >= 0) atomicAdd(&histS[pvT], 1);
-            if (v >= 0) atomicAdd(&histT[v], 1);
-            ++hits;
-        }
-    }
-    if (hits) atomicAdd(nhit, hits);
-    __syncthreads();
-    const int h = *nhit;
-    float *outS = out_counts + jS * (int64_t)rows, *outT = out_counts + jT * (int64_t)rows;
-    for (int x = tid; x < rows; x += kPairThreads) {
-        const int absent_s = x == 0 ? ns - h : 0, absent_t = x == 0 ? nt - h : 0;      // column 0 = partner absent (counted: MLP(0) != 0)
-        __builtin_nontemporal_store((float)(histS[x] + absent_s), outS + x);
-        __builtin_nontemporal_store((float)(histT[x] + absent_t), outT + x);
-    }
-    if (out_len && tid == 0) out_len[jS] = ns, out_len[jT] = nt;
-}
-
 static int64_t keycols_set_slots(int64_t T) {      // a power of two >= 2 T (the set is at most half full without an overflow), >= 1,024
     int64_t cap = 1024;
     while (cap < 2 * T) cap <<= 1;
@@ -289,31 +204,4 @@ extern "C" int subgacc_keyrows_columns(const int32_t *row_keys, const int32_t *n
     }
     return launch(keycols_finish_kernel, 1, kKcSortThreads, (size_t)cap * 4, (hipStream_t)stream, set, (int32_t)cap, table_rows,
                   (int)num_walks, (int)num_steps, shift, out_ukeys, out_count, out_feat, flags);
-}
-
-extern "C" int subgacc_sjoin_key_counts(const subgacc_join_desc *d, const int32_t *ukeys, const int64_t *n_keys, float *out_counts,
-                                        int32_t *out_len, void *stream) {
-    const char *name = "sjoin_key_counts";
-    RowLayout layout;
-    if (int rc = decode_desc(name, d, true, layout)) return rc;
-    SG_REQUIRE(d->options == 0, SUBGACC_ERR_BADARG, "%s: takes no option (options = %d)", name, (int)d->options);
-    SG_REQUIRE(d->payload_kind == SUBGACC_JOIN_KEY32, SUBGACC_ERR_BADARG,
-               "%s: joins rows of 32-bit LP keys (KEY32), not payload kind %d", name, (int)d->payload_kind);
-    SG_REQUIRE(layout == RowLayout::Strided, SUBGACC_ERR_BADARG,
-               "%s: joins the strided key rows of a step (row_len and row_stride set, row_off NULL), not packed or headed rows", name);
-    SG_REQUIRE(d->table_rows >= 2 && d->table_rows < (1ll << 31), SUBGACC_ERR_BADARG,
-               "%s: table_rows = %lld (the absent column and at least one LP row: >= 2)", name, (long long)d->table_rows);
-    SG_REQUIRE(ukeys && n_keys && out_counts, SUBGACC_ERR_BADARG, "%s: ukeys, n_keys and out_counts are required (a NULL one given)", name);
-    if (d->S == 0) return SUBGACC_OK;
-    SG_REQUIRE(d->flags && d->ids && d->payload, SUBGACC_ERR_BADARG, "%s: null argument (flags / ids / payload)", name);
-    JoinArgs a = join_args(d, layout);
-    a.table_rows = d->table_rows;
-    const size_t lds = (size_t)a.max_len * 8 + (size_t)a.table_rows * 12 + 16;
-    SG_REQUIRE(lds <= (size_t)kLdsBytes, SUBGACC_ERR_LDS,
-               "%s: %lld columns and rows of %d members need %zu B of LDS; use a smaller table_rows or the row form", name,
-               (long long)a.table_rows, (int)a.max_len, lds);
-    int64_t grid;
-    if (int rc = grid_of(d->S / 2, name, grid)) return rc;
-    return launch(sjoin_key_counts_kernel, grid, kPairThreads, lds, (hipStream_t)stream, a, d->pair_block, (const uint32_t *)ukeys, n_keys,
-                  out_counts, out_len);
 }

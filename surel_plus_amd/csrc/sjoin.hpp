@@ -1,6 +1,7 @@
 // sjoin.hpp -- what the files of SpJoin share (internal): the kernels' arguments, the streaming accesses, a segment's rows, the
-// mirrored-pair prologue of the count and pair forms, the sorted-set search, and on the host the checked launch and the decoding of
-// a descriptor.  sjoin.hip (the row form), sjoin_sizes.hip, sjoin_f64stage.hip, sjoin_forms.hip.
+// mirrored-pair prologue of the count and pair forms, the prefetch of a pair's shorter row, the sorted-set search, and on the host the
+// checked launch and the decoding of a descriptor.  sjoin.hip (the row form), sjoin_sizes.hip, sjoin_f64stage.hip, sjoin_forms.hip,
+// sjoin_keys.hip.
 #pragma once
 #include <cstdlib>
 #include "common.hpp"
@@ -150,6 +151,37 @@ __device__ __forceinline__ bool mirrored_pair(const JoinArgs &a, int64_t pb, Mir
     m.sb = swap ? bb : ab, m.tb = swap ? ab : bb, m.jS = swap ? j2 : j, m.jT = swap ? j : j2;
     return true;
 }
+
+// The first members of S, asked for before anything else is done: they are on their way while T is staged and LDS is cleared.  A lane's
+// member of trip r0 / kPairThreads comes from the two prefetched trips (rows of up to 512 members) and from memory after them.
+// The struct holds the prefetched words only; the store and S's offset are passed again, so that the kernels address S as they did
+// when each spelled this out (two more pointers kept here cost the count kernel 3 VGPRs).
+struct SPrefetch {
+    static constexpr int kTrips = 2;
+    int32_t sid[kTrips], sval[kTrips];
+    // sb: where S begins in the store's two planes
+    __device__ __forceinline__ void prefetch(const JoinArgs &a, int64_t sb, int ns) {
+        const int32_t *data = (const int32_t *)a.data;
+#pragma unroll
+        for (int u = 0; u < kTrips; ++u) {
+            const int r = threadIdx.x + u * kPairThreads;
+            sid[u] = 0, sval[u] = 0;
+            if (r < ns) sid[u] = stream_load(&a.indices[sb + r]), sval[u] = stream_load(&data[sb + r]);
+        }
+    }
+    // member r = r0 + threadIdx.x < ns of S: its id and its payload word
+    __device__ __forceinline__ void get(const JoinArgs &a, int64_t sb, int r0, int r, int32_t &id, int32_t &value) const {
+        const int u = r0 / kPairThreads;
+        const int32_t i0 = sid[0], i1 = sid[1], v0 = sval[0], v1 = sval[1];   // (read before the branch: they stay in registers)
+        if (u < kTrips) {
+            id = u == 0 ? i0 : i1;
+            value = u == 0 ? v0 : v1;
+        } else {
+            id = stream_load(&a.indices[sb + r]);
+            value = stream_load(&((const int32_t *)a.data)[sb + r]);
+        }
+    }
+};
 
 // Every kernel of the join is launched here: the dynamic-LDS limit is raised only for a kernel that asks for more than the 64 KiB it
 // gets by default, and the launch is checked

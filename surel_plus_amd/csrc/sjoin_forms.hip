@@ -2,10 +2,11 @@
 // not as output rows.  Kernels:
 //   sjoin_counts_kernel / sjoin_pairs_kernel   the count and pair forms of the join
 //   sjoin_counts_attn_kernel<BWD>       the count form with attentional aggregation (model.py:59-62,78-81, LP encoder): per segment the
-//                                       softmax-weighted count row W, and its backward (subgacc_sjoin_counts_attn[_backward])
+//                                       softmax-weighted count row W, and its backward (subgacc_sjoin_counts_attn[_backward]); its
+//                                       body is sjoin_attn.hpp's, shared with the key rows of a step (sjoin_keys.hip)
 // The count and pair forms are launched from subgacc_sjoin_fill_v2 (sjoin.hip); subgacc_sjoin_counts_attn / _backward are here.
 #include "sjoin.hpp"
-#include "sjoin_cols.hpp"
+#include "sjoin_attn.hpp"
 
 namespace subgacc {
 
@@ -33,18 +34,11 @@ __global__ __launch_bounds__(kPairThreads) void sjoin_counts_kernel(const JoinAr
     if (!mirrored_pair<false>(a, pb, m)) return;
     const int tid = threadIdx.x;
     const int ns = m.ns, nt = m.nt;
-    const int64_t sb = m.sb, tb = m.tb, jS = m.jS, jT = m.jT;
+    const int64_t tb = m.tb, jS = m.jS, jT = m.jT;
     const int32_t *data = (const int32_t *)a.data;
     const int rows = (int)a.table_rows;
-    // S's first members are asked for before anything else: they are on their way while T is staged and the histograms are cleared
-    constexpr int kTrips = 2;
-    int32_t sid[kTrips], sval[kTrips];
-#pragma unroll
-    for (int u = 0; u < kTrips; ++u) {
-        const int r = tid + u * kPairThreads;
-        sid[u] = 0, sval[u] = 0;
-        if (r < ns) sid[u] = stream_load(&a.indices[sb + r]), sval[u] = stream_load(&data[sb + r]);
-    }
+    SPrefetch s;
+    s.prefetch(a, m.sb, ns);
     for (int x = tid; x < 2 * rows + 1; x += kPairThreads) histS[x] = 0;   // histS, histT and nhit are contiguous
     for (int r = tid; r < nt; r += kPairThreads) {
         idsT[r] = stream_load(&a.indices[tb + r]);
@@ -58,16 +52,10 @@ __global__ __launch_bounds__(kPairThreads) void sjoin_counts_kernel(const JoinAr
     }
     int hits = 0;
     for (int r0 = 0; r0 < ns; r0 += kPairThreads) {     // S: own value, and -- on a hit -- one partner value for each block
-        const int r = r0 + tid, u = r0 / kPairThreads;
+        const int r = r0 + tid;
         if (r >= ns) break;
         int32_t id, v;
-        if (u < kTrips) {
-            id = u == 0 ? sid[0] : sid[1];
-            v = u == 0 ? sval[0] : sval[1];
-        } else {
-            id = stream_load(&a.indices[sb + r]);
-            v = stream_load(&data[sb + r]);
-        }
+        s.get(a, m.sb, r0, r, id, v);
         int b;
         const bool hit = sorted_find(idsT, nt, id, true, b);
         const int32_t pvT = hit ? valT[b] : 0;
@@ -93,187 +81,10 @@ __global__ __launch_bounds__(kPairThreads) void sjoin_counts_kernel(const JoinAr
     }
 }
 
-// Count form with attentional aggregation (model.py:59-62,78-81 for the LP encoder; include/subgacc.h: subgacc_sjoin_counts_attn).
-// Member t of segment j is the index pair (p_t, q_t) -- own LP row, partner LP row or 0 -- and its gate logit is l_t = g[p_t] + g[q_t]
-// with g = embed(encode) . wg, so the softmax-weighted sum of the rows collapses to W[j] @ embed(encode) with the softmax-weighted count
-// row W[j, r] = sum_t alpha_t ([p_t = r] + [q_t = r]).  The plan of sjoin_counts_kernel (the longer row staged, the shorter searched in
-// it once, a hit serving both blocks); every member's pair goes to LDS, the partner of a staged member from the hits (0 without one).
-// Then per block: the distinct LP rows are marked in a table-indexed array (integer writes and CAS: their LDS slots may come in any
-// order, nothing summed depends on it), and one lane per distinct row walks the block's members in ascending id order -- the documented
-// chain -- so no float is ever added atomically.  BWD: the same join, e_t recomputed from the forward's m_j, dW read at the block's
-// distinct rows only, kappa_j in ascending r (the distinct rows ranked by counting), beta_t per member, Dg_j[r] per distinct row.
-struct CountsAttnArgs {
-    const float *g;
-    float *out_w, *out_max, *out_den;           // forward
-    const float *dw, *w, *max, *den;            // backward
-    float *out_dg;
-};
-
-// LDS of sjoin_counts_attn_kernel in 4-byte words: ids of the staged row, own / partner values and l / e / beta of both blocks, the
-// two table-indexed arrays, the distinct rows of both blocks (the backward: with W and dW in ascending r), 8 words of block state
-static size_t counts_attn_lds(int64_t max_len, int64_t rows, int64_t dcap, bool bwd) {
-    return 4 * ((size_t)max_len * 7 + (size_t)rows * 2 + (size_t)dcap * (bwd ? 6 : 2) + 8);
-}
-
+// Count form with attentional aggregation over a packed SFptr store: the body of sjoin_attn.hpp with the member's SFptr as its column
 template <bool BWD>
 __global__ __launch_bounds__(kPairThreads) void sjoin_counts_attn_kernel(const JoinArgs a, int64_t pb, int32_t dcap, const CountsAttnArgs c) {
-    extern __shared__ __align__(16) unsigned char lds_raw[];
-    const int L = a.max_len, rows = (int)a.table_rows;
-    int32_t *idsT = (int32_t *)lds_raw;                     // [L]
-    int32_t *val = idsT + L;                                // [2][L] own LP row of every member: block 0 = S, block 1 = T
-    int32_t *par = val + 2 * L;                             // [2][L] partner LP row (0 = absent)
-    float *ex = (float *)(par + 2 * L);                     // [2][L] l_t, then e_t (BWD: then beta_t)
-    int32_t *mark = (int32_t *)(ex + 2 * L);                // [2][rows] 0 / 1 = occurs / 2 = listed; then the row's float
-    float *accf = (float *)mark;
-    int32_t *dist = mark + 2 * rows;                        // [2][dcap] the block's distinct rows, in slot order
-    float *srtW = (float *)(dist + 2 * dcap);               // BWD: [2][dcap] W[j, r] and dW[j, r] in ascending r
-    float *srtD = srtW + 2 * dcap;
-    int32_t *st = BWD ? (int32_t *)(srtD + 2 * dcap) : (int32_t *)srtW;   // [8]: distinct count, max (ordered), den, kappa per block
-    float *stf = (float *)st;
-
-    MirroredPair m;
-    if (!mirrored_pair<true>(a, pb, m)) return;
-    const int tid = threadIdx.x;
-    const int ns = m.ns, nt = m.nt;
-    const int64_t sb = m.sb, tb = m.tb, jS = m.jS, jT = m.jT;
-    const int32_t *data = (const int32_t *)a.data;
-    constexpr int kTrips = 2;
-    int32_t sid[kTrips], sval[kTrips];
-#pragma unroll
-    for (int u = 0; u < kTrips; ++u) {
-        const int r = tid + u * kPairThreads;
-        sid[u] = 0, sval[u] = 0;
-        if (r < ns) sid[u] = stream_load(&a.indices[sb + r]), sval[u] = stream_load(&data[sb + r]);
-    }
-    for (int x = tid; x < 2 * rows; x += kPairThreads) mark[x] = 0;
-    if (tid < 8) st[tid] = (tid == 2 || tid == 3) ? INT32_MIN : 0;
-    for (int r = tid; r < nt; r += kPairThreads) {
-        idsT[r] = stream_load(&a.indices[tb + r]);
-        int32_t v = stream_load(&data[tb + r]);
-        if ((uint32_t)v >= (uint32_t)rows) atomicOr(&a.flags[3], 2), v = 0;     // SFptr outside the table: never read out of bounds
-        val[L + r] = v, par[L + r] = 0;
-    }
-    __syncthreads();
-    for (int r0 = 0; r0 < ns; r0 += kPairThreads) {     // S: search T once; a hit gives each block its partner value
-        const int r = r0 + tid, u = r0 / kPairThreads;
-        if (r >= ns) break;
-        int32_t id, v;
-        if (u < kTrips) {
-            id = u == 0 ? sid[0] : sid[1];
-            v = u == 0 ? sval[0] : sval[1];
-        } else {
-            id = stream_load(&a.indices[sb + r]);
-            v = stream_load(&data[sb + r]);
-        }
-        if ((uint32_t)v >= (uint32_t)rows) atomicOr(&a.flags[3], 2), v = 0;
-        int b;
-        const bool hit = sorted_find(idsT, nt, id, true, b);
-        val[r] = v;
-        par[r] = hit ? val[L + b] : 0;
-        if (hit) par[L + b] = v;
-    }
-    __syncthreads();
-    const int ntot = ns + nt;
-    int32_t mo0 = INT32_MIN, mo1 = INT32_MIN;
-    for (int i = tid; i < ntot; i += kPairThreads) {    // logits, the rows that occur, the block max
-        const int blk = i >= ns, k = blk ? i - ns + L : i;
-        const int32_t pv = val[k], qv = par[k];
-        const float l = c.g[pv] + c.g[qv];
-        ex[k] = l;
-        mark[blk * rows + pv] = 1, mark[blk * rows + qv] = 1;
-        if (blk) mo1 = max(mo1, ord_of(l));
-        else mo0 = max(mo0, ord_of(l));
-    }
-    if (!BWD) {
-        if (mo0 != INT32_MIN) atomicMax(&st[2], mo0);
-        if (mo1 != INT32_MIN) atomicMax(&st[3], mo1);
-    }
-    __syncthreads();
-    const float m0 = BWD ? (ns ? c.max[jS] : 0.f) : (ns ? float_of(st[2]) : 0.f);
-    const float m1 = BWD ? (nt ? c.max[jT] : 0.f) : (nt ? float_of(st[3]) : 0.f);
-    for (int i = tid; i < ntot; i += kPairThreads) {    // e_t, and every distinct row listed once
-        const int blk = i >= ns, k = blk ? i - ns + L : i;
-        ex[k] = expf(ex[k] - (blk ? m1 : m0));
-        const int32_t rr[2] = {val[k], par[k]};
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-            if (atomicCAS(&mark[blk * rows + rr[s]], 1, 2) == 1) dist[blk * dcap + atomicAdd(&st[blk], 1)] = rr[s];
-    }
-    __syncthreads();
-    const int c0 = st[0], c1 = st[1];
-    if (!BWD) {
-        // one lane per distinct row of a block: den_j and sum_t e_t c_t(r), each an fp32 chain over the members in ascending id order
-        // (every lane of a block computes den_j in the same order: the same bits), then one division
-        for (int x = tid; x < c0 + c1; x += kPairThreads) {
-            const int blk = x >= c0, off = blk ? L : 0, n = blk ? nt : ns;
-            const int32_t r = dist[blk ? dcap + x - c0 : x];
-            float den = 0.f, s = 0.f;
-            for (int i = 0; i < n; ++i) {
-                const float e = ex[off + i];
-                den += e;
-                s += val[off + i] == r ? e : 0.f;
-                s += par[off + i] == r ? e : 0.f;
-            }
-            accf[blk * rows + r] = s / den;
-            if (x == (blk ? c0 : 0)) stf[4 + blk] = den;
-        }
-        __syncthreads();
-        float *outS = c.out_w + jS * (int64_t)rows, *outT = c.out_w + jT * (int64_t)rows;
-        for (int x = tid; x < rows; x += kPairThreads) {
-            __builtin_nontemporal_store(accf[x], outS + x);
-            __builtin_nontemporal_store(accf[rows + x], outT + x);
-        }
-        if (tid == 0 && c.out_max) {
-            c.out_max[jS] = m0, c.out_max[jT] = m1;
-            c.out_den[jS] = ns ? stf[4] : 0.f, c.out_den[jT] = nt ? stf[5] : 0.f;
-        }
-        return;
-    }
-    // ---- backward: dW and W at the distinct rows, each row's rank among them by counting (no sort; the ranks are distinct)
-    for (int x = tid; x < c0 + c1; x += kPairThreads) {
-        const int blk = x >= c0, cb = blk ? c1 : c0;
-        const int32_t *d = dist + blk * dcap;
-        const int32_t r = d[blk ? x - c0 : x];
-        const int64_t row = (blk ? jT : jS) * (int64_t)rows + r;
-        const float dwv = c.dw[row], wv = c.w[row];
-        int rank = 0;
-        for (int y = 0; y < cb; ++y) rank += d[y] < r;
-        srtW[blk * dcap + rank] = wv, srtD[blk * dcap + rank] = dwv;
-        accf[blk * rows + r] = dwv;
-    }
-    __syncthreads();
-    if (tid == 0 || tid == kWave) {       // kappa_j = sum_r W[j, r] dW[j, r]: an fmaf chain over the block's rows, r ascending
-        const int blk = tid == kWave, cb = blk ? c1 : c0;
-        float kap = 0.f;
-        for (int y = 0; y < cb; ++y) kap = fmaf(srtW[blk * dcap + y], srtD[blk * dcap + y], kap);
-        stf[6 + blk] = kap;
-    }
-    __syncthreads();
-    const float den0 = ns ? c.den[jS] : 1.f, den1 = nt ? c.den[jT] : 1.f;
-    for (int i = tid; i < ntot; i += kPairThreads) {    // beta_t = alpha_t (dW[p_t] + dW[q_t] - kappa_j), alpha_t = e_t / den_j
-        const int blk = i >= ns, k = blk ? i - ns + L : i;
-        const float alpha = ex[k] / (blk ? den1 : den0);
-        const float sdw = accf[blk * rows + val[k]] + accf[blk * rows + par[k]];
-        ex[k] = alpha * (sdw - stf[6 + blk]);
-    }
-    __syncthreads();
-    for (int x = tid; x < c0 + c1; x += kPairThreads) {  // Dg_j[r]: an fp32 chain over the members in ascending id order
-        const int blk = x >= c0, off = blk ? L : 0, n = blk ? nt : ns;
-        const int32_t r = dist[blk ? dcap + x - c0 : x];
-        float s = 0.f;
-        for (int i = 0; i < n; ++i) {
-            const float bt = ex[off + i];
-            s += val[off + i] == r ? bt : 0.f;
-            s += par[off + i] == r ? bt : 0.f;
-        }
-        accf[blk * rows + r] = s;
-    }
-    __syncthreads();
-    float *outS = c.out_dg + jS * (int64_t)rows, *outT = c.out_dg + jT * (int64_t)rows;
-    for (int x = tid; x < rows; x += kPairThreads) {
-        __builtin_nontemporal_store(accf[x], outS + x);
-        __builtin_nontemporal_store(accf[rows + x], outT + x);
-    }
+    counts_attn_body<BWD>(a, pb, dcap, c, TableColumns{});
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -459,20 +270,17 @@ static int counts_attn_launch(const char *name, const subgacc_join_desc *d, cons
     SG_REQUIRE(d->flags && d->ids && d->payload, SUBGACC_ERR_BADARG, "%s: null argument (flags / ids / payload)", name);
     JoinArgs a = join_args(d, RowLayout::Packed);      // (the only layout counts_attn_check admits)
     a.table_rows = d->table_rows;
-    const int64_t dcap = 2 * (int64_t)a.max_len < a.table_rows ? 2 * (int64_t)a.max_len : a.table_rows;   // distinct rows of a block
-    const size_t lds = counts_attn_lds(a.max_len, a.table_rows, dcap, bwd);
-    SG_REQUIRE(lds <= (size_t)kLdsBytes, SUBGACC_ERR_LDS,
-               "%s: %lld distinct LP rows and rows of %d members need %zu B of LDS; use attn_stage (the pair form)", name,
-               (long long)a.table_rows, (int)a.max_len, lds);
-    // a forward that keeps m / den is followed by the backward, which needs more LDS: refused here, not in the middle of a training step
-    const size_t lds_bwd = counts_attn_lds(a.max_len, a.table_rows, dcap, true);
-    SG_REQUIRE(bwd || !c.out_max || lds_bwd <= (size_t)kLdsBytes, SUBGACC_ERR_LDS,
-               "%s: %lld distinct LP rows and rows of %d members: the backward needs %zu B of LDS; use attn_stage (the pair form)", name,
-               (long long)a.table_rows, (int)a.max_len, lds_bwd);
+    int32_t dcap;
+    size_t lds;
+    if (int rc = counts_attn_fit(name, a, 0, bwd, c.out_max != nullptr,
+                                 "%s: %lld distinct LP rows and rows of %d members need %zu B of LDS; use attn_stage (the pair form)",
+                                 "%s: %lld distinct LP rows and rows of %d members: the backward needs %zu B of LDS; use attn_stage (the "
+                                 "pair form)", dcap, lds))
+        return rc;
     int64_t grid;
     if (int rc = grid_of(d->S / 2, name, grid)) return rc;
     return launch(bwd ? sjoin_counts_attn_kernel<true> : sjoin_counts_attn_kernel<false>, grid, kPairThreads, lds, (hipStream_t)stream, a,
-                  d->pair_block, (int32_t)dcap, c);
+                  d->pair_block, dcap, c);
 }
 
 extern "C" int subgacc_sjoin_counts_attn(const subgacc_join_desc *d, const float *g, float *out_w, float *out_max, float *out_den,

@@ -5,7 +5,7 @@ same argument meaning, same return values (xz float32 [R,2,k], indptr-or-segment
 `x` is an SpG (surel_plus_amd.spg.SpG) or a scipy CSR (uploaded once and cached), `encode` the Z_SF table
 as a float32 CUDA tensor or None for a float payload.  The work is done by csrc/sjoin.hip (the row form),
 csrc/sjoin_sizes.hip (the size pass), csrc/sjoin_f64stage.hip and csrc/sjoin_forms.hip (the fused stages, the count and pair forms),
-csrc/keycols.hip (the count form over the key rows of an on-demand step).
+csrc/keycols.hip and csrc/sjoin_keys.hip (the columns of an on-demand step's key rows and the joins over them).
 """
 import ctypes
 import os
@@ -718,19 +718,25 @@ def _step_columns(bufs, flags, st, fit):
     return count, T
 
 
+def _step_key_desc(bufs, form, own, partner, T, flags):
+    """the descriptor of a join over the key rows of a step of `bufs`: its strided rows of 32-bit LP keys, the mirrored list
+    (own, partner) and T columns"""
+    return _lib.join_desc(form, JOIN_KEY32, row_len=bufs.nsize, n_rows=bufs.n, row_stride=bufs.stride, ids=bufs.ids, payload=bufs.slot,
+                          own=own, partner=partner, S=bufs.S, pair_block=bufs.batch, table_rows=T, num_walks=bufs.M, num_steps=bufs.m,
+                          flags=flags)
+
+
 def _counts_tail(bufs, own, partner, flags, st, fit):
     """the end of a step with stage="counts": the columns of the step's LP keys, then the count form over the key rows -- three
     launches, nothing allocated, nothing read back -> (C, table), views of the buffers.  fit (sample_and_counts without buffers and
     without table_rows): the number of distinct LP rows c is read back once and the count kernel runs with T = c + 1 columns into a
     tensor of that width, so that the GEMM behind it has no dead column."""
     L = lib()
-    n, S = bufs.n, bufs.S
     count, T = _step_columns(bufs, flags, st, fit)
     C = bufs.counts
     if fit:
-        C = torch.empty((S, T), dtype=torch.float32, device=bufs.sizes.device)
-    d = _lib.join_desc(JOIN_COUNTS, JOIN_KEY32, row_len=bufs.nsize, n_rows=n, row_stride=bufs.stride, ids=bufs.ids, payload=bufs.slot,
-                       own=own, partner=partner, S=S, pair_block=bufs.batch, table_rows=T, num_walks=bufs.M, num_steps=bufs.m, flags=flags)
+        C = torch.empty((bufs.S, T), dtype=torch.float32, device=bufs.sizes.device)
+    d = _step_key_desc(bufs, JOIN_COUNTS, own, partner, T, flags)
     with _timed("sjoin_key_counts"):
         check(L.subgacc_sjoin_key_counts(ctypes.byref(d), ptr(bufs.ukeys), ptr(count), ptr(C), ptr(bufs.sizes), st))
     return C, bufs.feat[:T]
@@ -744,8 +750,7 @@ def _index_tail(bufs, own, partner, flags, st, fit):
     count, T = _step_columns(bufs, flags, st, fit)
     check(L.subgacc_sjoin_sizes_rows(ptr(bufs.nsize), n, ptr(own), ptr(partner), S, ptr(bufs.seg), ptr(flags), ptr(bufs.ws),
                                      bufs.ws.numel(), st))
-    d = _lib.join_desc(JOIN_ROWS, JOIN_KEY32, row_len=bufs.nsize, n_rows=n, row_stride=bufs.stride, ids=bufs.ids, payload=bufs.slot,
-                       own=own, partner=partner, S=S, pair_block=bufs.batch, table_rows=T, num_walks=bufs.M, num_steps=bufs.m, flags=flags)
+    d = _step_key_desc(bufs, JOIN_ROWS, own, partner, T, flags)
     with _timed("sjoin_key_index"):
         check(L.subgacc_sjoin_key_index(ctypes.byref(d), ptr(bufs.ukeys), ptr(count), ptr(bufs.seg), ptr(bufs.pairs), ptr(bufs.sizes), st))
     return bufs.pairs, bufs.feat[:T]
@@ -1053,10 +1058,7 @@ class _StepAttnJoin:
         self.dev = bufs.sizes.device if bufs is not None else dev
 
     def desc(self):
-        b = self.bufs
-        return _lib.join_desc(JOIN_COUNTS, JOIN_KEY32, row_len=b.nsize, n_rows=b.n, row_stride=b.stride, ids=b.ids, payload=b.slot,
-                              own=self.own, partner=self.partner, S=b.S, pair_block=b.batch, table_rows=self.T, num_walks=b.M,
-                              num_steps=b.m, flags=self.flags)
+        return _step_key_desc(self.bufs, JOIN_COUNTS, self.own, self.partner, self.T, self.flags)
 
     def _require_fresh(self, what):
         now = getattr(self.bufs, "step_id", 0)

@@ -98,6 +98,7 @@ _REFUSALS = [
     (dict(form=2), b"form ROWS"),                                           # PAIRS
     (dict(seg=None), b"seg and out_idx are required"),
     (dict(out_idx=None), b"seg and out_idx are required"),
+    (dict(form=1, options=1), b"form ROWS"),                                # both wrong: the form is looked at before the options
 ]
 
 
