@@ -557,7 +557,9 @@ int subgacc_rows_to_headed(const int64_t *row_off, int64_t n_rows, const int32_t
  *
  * One wavefront works on one root at a time in a private `slab` of 24 << table_log2 bytes (hash table of p, r
  * and the work list).  num_waves slabs = num_waves resident wavefronts; reset the slabs once, the kernel hands
- * them back clean (table_log2 in [10, 26]).  A root that touches more than (1 << table_log2) / 2 nodes (bounded by 1/(alpha*epsilon))
+ * them back clean (table_log2 in [10, 26]).  A root that touches T nodes in all (itself, the pushed nodes and their neighbours)
+ * always fits when 2 * T + 257 <= 1 << table_log2 and never when T + 256 > 3 / 4 of the table; 1/(alpha*epsilon) bounds the
+ * pushed nodes, not T (one push of a hub touches deg + 1 nodes; T <= num_nodes).  A root that does not fit
  * gets out_count = -1 and flags[2] |= 1: run those roots again with a larger table.
  *   out_count [n] int32, out_ids [n*topk] int32 ascending ids of row i at i*topk, out_vals [n*topk] float32
  *   pushes (optional, device uint64[2]) accumulates the number of pushes and of touched nodes.  topk <= 4096.

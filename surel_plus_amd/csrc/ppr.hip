@@ -10,9 +10,12 @@
 // threshold and append the nodes that pass to the work list in lane order (ballot + prefix popcount), which is the
 // order the sequential loop appends them in.
 //
-// State of one root (dicts p, r and list q of the reference) lives in a per-wave slab of HBM sized for the
-// worst case of the approximation (<= 1/(alpha*eps) touched nodes; 288 GB make 8192 x MBs affordable) -- open
-// addressing, cleaned by the list of touched slots, so a slab is cleared once per launch, not once per root.
+// State of one root (dicts p, r and list q of the reference) lives in a per-wave slab of HBM -- open addressing,
+// cleaned by the list of touched slots, so a slab is cleared once per launch, not once per root.  The approximation
+// bounds the nodes that are PUSHED (<= 1/(alpha*eps) besides the root), not the nodes that are touched: the table
+// also holds every neighbour of a pushed node, and one push of a hub touches deg + 1 of them.  A root that does not
+// fit is refused (out_count = -1) and the caller runs it again with a larger table; 2 * touched + 257 <= cap always
+// fits, and touched <= num_nodes (288 GB make 8192 x MBs affordable).
 // All slab accesses are workgroup-scope atomics: lanes of the wave hand values to each other through the XCD's L2.
 #include "common.hpp"
 

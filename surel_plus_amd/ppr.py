@@ -40,6 +40,24 @@ def _launch(csr, roots, alpha, eps, topk, table_log2, waves, cnt, ids, vals, fla
                                      ptr(vals), ptr(flags), ptr(pushes) if pushes is not None else None, stream_ptr()))
 
 
+def _waves(table_log2):
+    """wavefronts of one launch: as many as the slab budget holds at this table size, at least one, at most MAX_WAVES"""
+    return int(max(1, min(MAX_WAVES, SLAB_BUDGET // (24 << table_log2))))
+
+
+def _table_log2_max(csr, alpha, epsilon):
+    """(log2 slots of the table that no root of a simple graph overflows, False when the largest table, 2^26, is smaller).  The kernel accepts a root that touches T nodes in all
+    when 2 * T + 257 <= slots.  T <= num_nodes; and a node other than the root is pushed with a residual >= alpha*eps*deg, which
+    moves into p, and sum(p) <= 1: at most 1/(alpha*eps) nodes that have neighbours are ever PUSHED, and what is touched is the
+    root, the pushed nodes and their neighbours -- one push of a hub touches deg + 1 nodes."""
+    N = csr.num_nodes
+    pushed = int(math.ceil(1.0 / (float(alpha) * float(epsilon)))) + 1
+    max_deg = int((csr.indptr[1:] - csr.indptr[:-1]).max().item()) if N else 0
+    touched = min(N, 1 + pushed * max_deg)
+    log2 = max(10, (2 * touched + 257 - 1).bit_length())
+    return min(26, log2), log2 <= 26
+
+
 def _pilot_table_log2(csr, roots, alpha, epsilon, topk, log2_max):
     """smallest table (log2 slots) that holds >= 97 % of a sample of the roots"""
     n = roots.numel()
@@ -53,7 +71,7 @@ def _pilot_table_log2(csr, roots, alpha, epsilon, topk, log2_max):
     vals = torch.empty(m * topk, dtype=torch.float32, device=dev)
     flags = torch.zeros(4, dtype=torch.int32, device=dev)
     for log2 in range(10, log2_max):
-        _launch(csr, sample, alpha, epsilon, topk, log2, MAX_WAVES, cnt, ids, vals, flags, None)
+        _launch(csr, sample, alpha, epsilon, topk, log2, _waves(log2), cnt, ids, vals, flags, None)
         if int((cnt >= 0).sum()) >= 0.97 * m:
             return log2
     return log2_max
@@ -74,18 +92,17 @@ def ppr_topk(adj, alpha, epsilon, nodes, topk, table_log2=None, device=None):
     vals = torch.empty(n * topk, dtype=torch.float32, device=device)
     flags = torch.zeros(4, dtype=torch.int32, device=device)
     pushes = torch.zeros(2, dtype=torch.int64, device=device)      # pushes, touched nodes
-    # a push of u moves >= alpha*eps*deg(u) into p and sum(p) <= 1: at most 1/(alpha*eps) nodes are ever touched.
-    # Most roots need far less and dense tables are faster (more of them stay in L2), so a pilot over a sample of
-    # the roots picks the smallest table that holds ~all of them; the few roots that overflow are run again, larger.
-    worst = int(math.ceil(1.0 / (float(alpha) * float(epsilon)))) + 512
-    log2_max = min(26, max(10, int(math.ceil(math.log2(2 * worst)))))
+    # Most roots touch far fewer nodes than the ceiling allows and dense tables are faster (more of them stay in L2), so a pilot
+    # over a sample of the roots picks the smallest table that holds ~all of them; the few roots that overflow are run again,
+    # larger, up to the table that holds whatever a root of a simple graph can touch.
+    log2_max, holds_all = _table_log2_max(csr, alpha, epsilon)
     if table_log2 is None:
         log2 = _pilot_table_log2(csr, roots, alpha, epsilon, topk, log2_max)
     else:
         log2 = min(log2_max, max(10, int(table_log2)))
     todo, dst = roots, None
     while n:
-        waves = int(min(MAX_WAVES, max(64, SLAB_BUDGET // (24 << log2))))
+        waves = _waves(log2)
         if dst is None:
             _launch(csr, todo, alpha, epsilon, topk, log2, waves, cnt, ids, vals, flags, pushes)
         else:   # later rounds: the overflowed roots only, scattered back into their rows
@@ -100,7 +117,10 @@ def ppr_topk(adj, alpha, epsilon, nodes, topk, table_log2=None, device=None):
         if bad.numel() == 0:
             break
         if log2 >= log2_max:
-            raise MemoryError("ppr_topk: a root touched more nodes than 1/(alpha*eps) allows -- repeated entries in a CSR row?")
+            if not holds_all:
+                raise MemoryError("ppr_topk: a root overflowed the largest table (2^26 slots)")
+            raise MemoryError(f"ppr_topk: a root overflowed a table of 2^{log2} slots, which holds every node a root of this graph "
+                              "can touch -- repeated entries in a CSR row?")
         log2 = min(log2 + 2, log2_max)
         todo, dst = roots[bad].contiguous(), bad
         flags.zero_()
