@@ -187,6 +187,14 @@ int subgacc_compact_sets(const int32_t *set_ids, const uint64_t *set_keys, const
 /* ---------------------------------------------------------------------------------------------
  * Global first-occurrence dedup of LP rows (subg_acc.c:957-978): key -> index in order of first
  * appearance over the concatenated sets.  Open-addressing table in HBM, `capacity` a power of two.
+ * Limits (tests/test_gpu_uniq_edges.py pins each of them):
+ *   - the key 2^64 - 1 marks an empty slot and is NOT a key (subgacc_key_shift refuses the one (M, m) whose rows could pack to it);
+ *   - a probe chain ends after 128 slots (or `capacity`, if smaller): the 129th key of one home slot, or the (capacity+1)-th
+ *     distinct key, sets flags[2] |= 1 and is dropped -- grow the table and insert again; what was numbered meanwhile is void;
+ *   - the scan numbering (more than `small_limit` distinct keys) recognises a first occurrence by mintag == its position in
+ *     `slot`, so `slot` must be the concatenated out_slot of the inserts with positions EQUAL to the tags (tag_base + e); the
+ *     direct ranking reads the table alone.  With n = 0 (slot may be NULL) and more than small_limit distinct keys, nothing is
+ *     numbered: out_count is right, ids and out_ukeys are left as they were.
  * ------------------------------------------------------------------------------------------- */
 size_t subgacc_uniq_table_bytes(int64_t capacity);
 int subgacc_uniq_reset(void *table, int64_t capacity, void *stream);
@@ -649,7 +657,8 @@ int subgacc_step_prologue(void *uniq_table, int64_t capacity, int64_t *zero_word
 
 /* The same prologue for a step that samples every DISTINCT endpoint once.  Philox keys a walk by (seed, root id, walk, hop), so a
  * root's set does not depend on where or how often the root stands in the batch (the reference samples every node once, offline,
- * main.py:172-178; its sequential rand_r stream has no such property, so this form is Philox only).  Two launches:
+ * main.py:172-178; its sequential rand_r stream has no such property, so this form is Philox only).  Three launches (the first one
+ * returns at once but for one step in 2^32 - 1, see `workspace`):
  *   roots       int32 [n]: roots[j] = endpoint j where j is the FIRST occurrence of its node in the batch, SUBGACC_NO_ROOT
  *               elsewhere -- rows of the batch's sets stay where the plain step has them, the rows of repeated endpoints
  *               stay empty (subgacc_walk_spg_sparse passes over them), and the distinct LP rows keep their numbering
@@ -661,8 +670,13 @@ int subgacc_step_prologue(void *uniq_table, int64_t capacity, int64_t *zero_word
  *               sampler will not visit
  *   n_distinct  int64 [1] (device): the number of distinct endpoints = the length of the work list
  *   workspace   subgacc_step_dedup_workspace_bytes(n) bytes, ZEROED once by the caller before its first use and left alone
- *               afterwards: it keeps the stamp of the last step (slots are stamped, never cleared), so a captured (replayed)
- *               step works like a launched one
+ *               afterwards: it keeps the stamp of the last step (slots are stamped, not cleared from step to step), so a captured
+ *               (replayed) step works like a launched one.  Its first int64 IS that stamp: the low 32 bits count the steps made on
+ *               this workspace, 1, 2, .. 0xFFFFFFFF (0 = never used, and skipped afterwards).  The step after stamp 0xFFFFFFFF
+ *               clears the table on the device, in a launch that is a no-op in every other step, and takes stamp 1: an era of
+ *               2^32 - 1 steps ends and the next one starts from the zeroed state, with no host read and no action of the caller's
+ *               (two months of 1.1 ms steps on one workspace).  The rest of the workspace has no documented layout.
+ * The work list's ORDER is unspecified (compare it as a set); everything else the call writes is a function of `edge` alone.
  * ------------------------------------------------------------------------------------------- */
 #define SUBGACC_NO_ROOT (-2147483647 - 1)
 size_t subgacc_step_dedup_workspace_bytes(int64_t n);

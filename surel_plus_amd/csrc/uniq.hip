@@ -44,7 +44,8 @@ __global__ void step_prologue_kernel(UniqTable t, int64_t cap, int64_t *zero_wor
 
 // The same prologue for a step that samples every DISTINCT endpoint once (Philox keys a walk by its root's id: a root's set does
 // not depend on where or how often the root appears in the batch).  The n endpoints go into an open-addressing table in HBM
-// whose slots are stamped with the step's generation (kept in the workspace; nothing is ever cleared); every occurrence of a
+// whose slots are stamped with the step's generation (kept in the workspace; nothing is cleared but once in 2^32 - 1 steps, by
+// step_dedup_era_kernel below); every occurrence of a
 // root raises the slot's value to (generation, ~index) with a 64-bit atomicMax, so that the slot ends up naming the root's
 // FIRST occurrence.  The second kernel gives endpoint j the row of that first occurrence -- own[j], and partner[] of the other
 // end of its pair -- leaves roots[j] = the root where j is a first occurrence, SUBGACC_NO_ROOT elsewhere, and lists the first
@@ -52,6 +53,22 @@ __global__ void step_prologue_kernel(UniqTable t, int64_t cap, int64_t *zero_wor
 // matter: entry k names its row).  Rows are sparse in [0, n) but deterministic -- the sets of the batch sit where the plain step
 // has them, and the distinct LP rows keep the numbering they would have had with every endpoint sampled (a repeated root never
 // is the first to show a row) -- while the walk kernel runs over the dense list and never sees an empty row.
+// The stamp is 32 bits wide and 0 means "never used", so the step after stamp 0xFFFFFFFF takes stamp 1 again -- while every slot
+// still carries a stamp of the era that ends: an atomicMax on hvals with the small new stamp would lose against all of them, and the
+// slots of hkeys that were stamped 1, 2, ... long ago and never claimed since would look current.  This launch stands in front of
+// every claim kernel and returns at once (like uniq_count_kernel on `count`) unless the last stamp was 0xFFFFFFFF; then it puts the
+// table back into the zeroed state a workspace starts from, and the new era begins like the first one.  Nothing is read back on
+// the host: a captured step replays it with the rest.
+__global__ __launch_bounds__(256) void step_dedup_era_kernel(unsigned long long *__restrict__ hkeys,
+                                                             unsigned long long *__restrict__ hvals, int64_t c,
+                                                             const int64_t *__restrict__ last_gen) {
+    if ((uint32_t)*last_gen != 0xFFFFFFFFu) return;
+    for (int64_t h = (int64_t)blockIdx.x * 256 + threadIdx.x; h < c; h += (int64_t)gridDim.x * 256) {
+        hkeys[h] = 0ull;
+        hvals[h] = 0ull;
+    }
+}
+
 __global__ void step_dedup_claim_kernel(UniqTable t, int64_t cap, int64_t *zero_words, int64_t n_zero, const int64_t *edge,
                                         int32_t *slot_of, unsigned long long *hkeys, unsigned long long *hvals,
                                         uint32_t hmask, int hshift, const int64_t *last_gen, int64_t *n_distinct, int64_t n) {
@@ -219,7 +236,10 @@ __global__ __launch_bounds__(256) void uniq_insert_kernel(UniqTable t, const uin
         const int64_t e = base + (int64_t)k * 256 + threadIdx.x;
         if (e >= n) continue;
         const int32_t m = mine[k];
-        out_slot[e] = m >= 0 ? ls[m] : (m < -1 ? -m - 2 : 0);
+        // a key the over-full table dropped (flags[2]) gets slot 0 on both routes, never -1: the later passes index the table
+        // with it before anybody has looked at the flag
+        const int32_t g = m >= 0 ? ls[m] : (m < -1 ? -m - 2 : 0);
+        out_slot[e] = g >= 0 ? g : 0;
     }
 }
 
@@ -393,6 +413,12 @@ static int64_t dedup_slots(int64_t n) {
     return c;
 }
 
+// at most one workgroup per CU: the launch is a no-op 2^32 - 2 times out of 2^32 - 1
+static void launch_dedup_era(unsigned long long *hkeys, unsigned long long *hvals, int64_t c, const int64_t *last_gen, hipStream_t s) {
+    const int64_t blocks = ceil_div(c, 256) < 256 ? ceil_div(c, 256) : 256;
+    hipLaunchKernelGGL(step_dedup_era_kernel, dim3((unsigned)blocks), dim3(256), 0, s, hkeys, hvals, c, last_gen);
+}
+
 extern "C" size_t subgacc_step_dedup_workspace_bytes(int64_t n) {
     if (n < 0) n = 0;
     const int64_t c = dedup_slots(n);
@@ -419,6 +445,7 @@ extern "C" int subgacc_step_prologue_dedup(void *table, int64_t capacity, int64_
     int64_t span = capacity > n ? capacity : n;
     if (n_zero > span) span = n_zero;
     hipStream_t s = (hipStream_t)stream;
+    launch_dedup_era(hkeys, hvals, c, last_gen, s);
     hipLaunchKernelGGL(step_dedup_claim_kernel, dim3((unsigned)ceil_div(span, 256)), dim3(256), 0, s,
                        table ? uniq_view(table, capacity) : UniqTable{nullptr, nullptr, nullptr, 0}, capacity, zero_words, n_zero,
                        edge, slot_of, hkeys, hvals, (uint32_t)(c - 1), 32 - (63 - __builtin_clzll((unsigned long long)c)), last_gen,
@@ -462,6 +489,7 @@ extern "C" int subgacc_step_prologue_dedup_roles(void *table, int64_t capacity, 
     int64_t span = capacity > n ? capacity : n;
     if (n_zero > span) span = n_zero;
     hipStream_t st = (hipStream_t)stream;
+    launch_dedup_era(hkeys, hvals, c, last_gen, st);
     hipLaunchKernelGGL(step_dedup_claim_kernel, dim3((unsigned)ceil_div(span, 256)), dim3(256), 0, st,
                        table ? uniq_view(table, capacity) : UniqTable{nullptr, nullptr, nullptr, 0}, capacity, zero_words, n_zero,
                        edge, slot_of, hkeys, hvals, (uint32_t)(c - 1), 32 - (63 - __builtin_clzll((unsigned long long)c)), last_gen,
