@@ -1,4 +1,5 @@
-"""ctypes binding of libsubgacc_hip.so (the C ABI declared in include/subgacc.h).
+"""ctypes binding of libsubgacc_hip.so, derived from the declarations of include/subgacc.h (the C ABI) when this module is
+imported: an entry point is declared there and defined under csrc/, and nothing here names it.
 
 There is no CPU fallback: if the library is missing, or no gfx950 device is visible when a compute entry
 point is called, this module raises.  Error codes map onto the exceptions the reference raises for the
@@ -6,6 +7,7 @@ same condition (subg_acc/subg_acc.c:658, :688-721, :905-915).
 """
 import ctypes as C
 import os
+import re
 import subprocess
 import threading
 
@@ -17,31 +19,6 @@ CSRC = os.path.join(_HERE, "csrc")
 OK, ERR_BADARG, ERR_WORKSPACE, ERR_KEYWIDTH, ERR_CAPACITY, ERR_HIP, ERR_LDS, ERR_NODEVICE = 0, -1, -2, -3, -4, -5, -6, -7
 RNG_RAND_R, RNG_PHILOX = 0, 1
 ORDER_WALK_MAJOR, ORDER_STEP_MAJOR = 0, 1
-
-# every symbol include/subgacc.h declares (tests check the built library exports all of them)
-SYMBOLS = (
-    "subgacc_abi_version", "subgacc_last_error", "subgacc_device_count", "subgacc_key_shift",
-    "subgacc_rng_positions_workspace_bytes", "subgacc_rng_positions", "subgacc_walk_sets", "subgacc_walk_spg",
-    "subgacc_compact_rows",
-    "subgacc_scan_workspace_bytes", "subgacc_exclusive_scan_i32", "subgacc_compact_sets",
-    "subgacc_uniq_table_bytes", "subgacc_uniq_reset", "subgacc_uniq_insert",
-    "subgacc_uniq_number_workspace_bytes", "subgacc_uniq_number", "subgacc_uniq_translate", "subgacc_unpack_lp",
-    "subgacc_spg_build",
-    "subgacc_sjoin_workspace_bytes", "subgacc_sjoin_sizes",
-    "subgacc_ppr_slab_bytes", "subgacc_ppr_slab_reset", "subgacc_ppr_topk", "subgacc_ppr_normalize", "subgacc_ppr_encode",
-    "subgacc_walk_join", "subgacc_sjoin_sizes_rows",
-    "subgacc_encode_sizes", "subgacc_encode_fill", "subgacc_finish_rows",
-    "subgacc_batch_sampler_workspace_bytes", "subgacc_batch_sampler", "subgacc_step_prologue",
-    "subgacc_hop_records_format", "subgacc_hop_records_build", "subgacc_step_dedup_workspace_bytes",
-    "subgacc_step_prologue_dedup", "subgacc_step_prologue_dedup_roles", "subgacc_walk_spg_sparse",
-    "subgacc_keyrows_register", "subgacc_keyrows_cand_capacity", "subgacc_walk_tags", "subgacc_keyrows_compact", "subgacc_keyrows_translate", "subgacc_rng_replay", "subgacc_walk_keyrows64", "subgacc_worklist_workspace_bytes", "subgacc_worklist_by_root", "subgacc_walk_spg_list",
-    "subgacc_locality_round", "subgacc_worklist_by_rank",
-    "subgacc_sjoin_fill_v2", "subgacc_publish_words", "subgacc_rows_to_headed", "subgacc_sjoin_star_sizes", "subgacc_sjoin_relu_mean",
-    "subgacc_sjoin_relu_attn", "subgacc_sjoin_relu_attn_backward", "subgacc_sjoin_counts_attn", "subgacc_sjoin_counts_attn_backward",
-    "subgacc_lstm_aggr", "subgacc_lstm_aggr_backward", "subgacc_lstm_aggr_hinge", "subgacc_lstm_aggr_hinge_backward",
-    "subgacc_keyrows_columns_workspace_bytes", "subgacc_keyrows_columns", "subgacc_sjoin_key_counts",
-    "subgacc_sjoin_key_counts_attn", "subgacc_sjoin_key_counts_attn_backward", "subgacc_sjoin_key_index",
-)
 
 
 class WalkCfg(C.Structure):
@@ -76,6 +53,62 @@ class SubgAccError(RuntimeError):
     pass
 
 
+HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "subgacc.h"))
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64,
+            "size_t": C.c_size_t, "float": C.c_float, "double": C.c_double}
+_STRUCTS = {"const subgacc_walk_cfg *": WalkCfg, "const subgacc_join_desc *": JoinDesc}
+
+
+def parse_header(text):
+    """{name: (return type, [(argument name, C type)])} of every `ret subgacc_name(args);` of a header's text, in declaration
+    order.  Comments go first (the header's hold parentheses and semicolons), then the preprocessor lines."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+
+    def ctype(t):          # "const  float*" -> "const float *"
+        return " ".join(t.replace("*", " * ").split())
+
+    decls = {}
+    for ret, name, args in re.findall(r"([\w\s*]+?)\b(subgacc_\w+)\s*\(([^()]*)\)\s*;", text):
+        params = []
+        for arg in ([] if args.strip() == "void" else args.split(",")):
+            m = re.fullmatch(r"(.*[\s*])(\w+)", arg.strip())
+            if not m:
+                raise SubgAccError(f"{name}: cannot read the parameter `{arg.strip()}`")
+            params.append((m.group(2), ctype(m.group(1))))
+        if name in decls:
+            raise SubgAccError(f"{name} is declared twice")
+        decls[name] = (ctype(ret), params)
+    return decls
+
+
+def bind_types(decls):
+    """{name: (restype, argtypes)} for the declarations of parse_header()"""
+    return {name: (_ctype(ret, name, ret=True), [_ctype(t, name) for _, t in args]) for name, (ret, args) in decls.items()}
+
+
+def _ctype(ctype, decl, ret=False):
+    """the ctypes type of one C type -- a type the ABI does not use is an error that names the declaration, never a guess"""
+    if ctype in _SCALARS:
+        return _SCALARS[ctype]
+    if ret and ctype == "const char *":
+        return C.c_char_p
+    if not ret and ctype.endswith("*"):
+        return C.POINTER(_STRUCTS[ctype]) if ctype in _STRUCTS else C.c_void_p
+    raise SubgAccError(f"{decl}: no ctypes type for the {'return' if ret else 'parameter'} type `{ctype}`")
+
+
+try:
+    with open(HEADER) as _f:
+        _TEXT = _f.read()
+except OSError as e:
+    raise SubgAccError(f"{HEADER} is missing or unreadable: the binding is derived from it") from e
+DECLS = parse_header(_TEXT)
+_TYPES = bind_types(DECLS)
+SYMBOLS = tuple(DECLS)            # every entry point the header declares, in its order
+ABI_VERSION = int(re.search(r"^#define\s+SUBGACC_ABI_VERSION\s+(\d+)", _TEXT, re.M).group(1))
+
+
 _lib = None
 # the reference prints "#SubGAcc: ..." statistics to stdout (subg_acc.c:878,1009); SUBGACC_QUIET=1 silences ours
 VERBOSE = os.environ.get("SUBGACC_QUIET", "0") != "1"
@@ -101,92 +134,13 @@ def lib():
         raise SubgAccError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            f"(or `make -C surel_plus_amd/csrc`). There is no CPU fallback.")
     L = C.CDLL(LIB_PATH)
-    vp, i32, i64, u64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_size_t
-    cfgp = C.POINTER(WalkCfg)
-    sig = {
-        "subgacc_abi_version": (C.c_int, []),
-        "subgacc_last_error": (C.c_char_p, []),
-        "subgacc_device_count": (C.c_int, []),
-        "subgacc_key_shift": (C.c_int, [i32, i32]),
-        "subgacc_rng_positions_workspace_bytes": (sz, [i64]),
-        "subgacc_rng_positions": (C.c_int, [cfgp, vp, i64, vp, i64, i32, u64, vp, vp, vp, sz, vp]),
-        "subgacc_walk_sets": (C.c_int, [cfgp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]),
-        "subgacc_walk_spg": (C.c_int, [cfgp, vp, vp, i64, vp, i64, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp]),
-        "subgacc_compact_rows": (C.c_int, [vp, vp, vp, vp, i64, i32, vp, vp, vp, i64, vp]),
-        "subgacc_scan_workspace_bytes": (sz, [i64]),
-        "subgacc_exclusive_scan_i32": (C.c_int, [vp, i64, vp, vp, sz, vp]),
-        "subgacc_compact_sets": (C.c_int, [vp, vp, vp, vp, i64, i32, vp, vp, vp, i64, i64, vp, vp, vp]),
-        "subgacc_uniq_table_bytes": (sz, [i64]),
-        "subgacc_uniq_reset": (C.c_int, [vp, i64, vp]),
-        "subgacc_uniq_insert": (C.c_int, [vp, i64, vp, i64, i64, vp, vp, vp]),
-        "subgacc_uniq_number_workspace_bytes": (sz, [i64, i64]),
-        "subgacc_uniq_number": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i64, vp, sz, vp]),
-        "subgacc_uniq_translate": (C.c_int, [vp, i64, vp, i64, vp, i32, vp]),
-        "subgacc_unpack_lp": (C.c_int, [vp, i64, vp, i32, i32, vp, vp, vp, i32, vp]),
-        "subgacc_spg_build": (C.c_int, [vp, i64, vp, vp, vp, i64, i32, vp, vp, vp, vp]),
-        "subgacc_sjoin_workspace_bytes": (sz, [i64]),
-        "subgacc_sjoin_sizes": (C.c_int, [vp, i64, vp, vp, i64, vp, vp, vp, sz, vp]),
-    }
-    f32 = C.c_float
-    sig["subgacc_ppr_slab_bytes"] = (sz, [i32, i32])
-    sig["subgacc_ppr_slab_reset"] = (C.c_int, [vp, i32, i32, vp])
-    sig["subgacc_ppr_topk"] = (C.c_int, [vp, i32, vp, i64, vp, i64, f32, f32, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp])
-    sig["subgacc_ppr_normalize"] = (C.c_int, [vp, i32, vp, i64, vp, i64, vp, vp, i32, vp, vp, vp])
-    sig["subgacc_ppr_encode"] = (C.c_int, [vp, i64, vp, vp, vp])
-    sig["subgacc_walk_join"] = (C.c_int, [vp, i64, i32, vp, vp, vp, i32, vp, i64, vp, vp])
-    sig["subgacc_hop_records_format"] = (C.c_int, [i64, i64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)])
-    sig["subgacc_hop_records_build"] = (C.c_int, [vp, i32, vp, i64, i64, i32, i32, vp, vp])
-    sig["subgacc_step_dedup_workspace_bytes"] = (C.c_size_t, [i64])
-    sig["subgacc_step_prologue_dedup"] = (C.c_int, [vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, C.c_size_t, vp, vp])
-    sig["subgacc_step_prologue_dedup_roles"] = (C.c_int, [vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, i64, i32, i32, vp, C.c_size_t, vp, vp])
-    sig["subgacc_walk_spg_sparse"] = (C.c_int, [cfgp, vp, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp])
-    sig["subgacc_step_prologue"] = (C.c_int, [vp, i64, vp, i64, vp, vp, i64, vp])
-    sig["subgacc_batch_sampler_workspace_bytes"] = (sz, [i64])
-    sig["subgacc_batch_sampler"] = (C.c_int, [vp, i32, vp, i64, vp, i64, i32, i32, i32, C.c_uint32, vp, i64, vp, vp, sz, vp, vp])
-    sig["subgacc_sjoin_sizes_rows"] = (C.c_int, [vp, i64, vp, vp, i64, vp, vp, vp, sz, vp])
-    sig["subgacc_encode_sizes"] = (C.c_int, [vp, vp, i64, vp, i32, vp, i32, vp, vp, vp])
-    sig["subgacc_encode_fill"] = (C.c_int, [vp, vp, vp, i64, i32, vp, i32, vp, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp])
-    sig["subgacc_finish_rows"] = (C.c_int, [vp, vp, vp, i64, i32, i64, vp, i64, vp, vp, vp])
-    sig["subgacc_keyrows_register"] = (C.c_int, [vp, vp, i64, i32, i64, vp, i64, vp, i64, vp, vp, vp])
-    sig["subgacc_keyrows_cand_capacity"] = (i64, [i64])
-    sig["subgacc_walk_tags"] = (C.c_int, [cfgp, vp, vp, i64, vp, i64, i64, vp, vp, vp, vp, i64, vp, i64, vp, vp])
-    sig["subgacc_keyrows_compact"] = (C.c_int, [vp, vp, vp, vp, i64, i32, i64, vp, i64, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp])
-    sig["subgacc_keyrows_translate"] = (C.c_int, [vp, i64, vp, vp, i64, vp, vp, i64, vp])
-    sig["subgacc_walk_keyrows64"] = (C.c_int, [cfgp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp])
-    sig["subgacc_rng_replay"] = (C.c_int, [cfgp, vp, vp, i64, vp, i64, i32, u64, vp, vp, vp, vp])
-    sig["subgacc_worklist_workspace_bytes"] = (sz, [i64])
-    sig["subgacc_worklist_by_root"] = (C.c_int, [vp, i64, i64, vp, vp, vp, sz, vp])
-    sig["subgacc_worklist_by_rank"] = (C.c_int, [vp, i64, vp, i64, vp, vp, vp, sz, vp])
-    sig["subgacc_locality_round"] = (C.c_int, [vp, i32, vp, i64, vp, vp, i32, i32, vp])
-    sig["subgacc_walk_spg_list"] = (C.c_int, [cfgp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp])
-    sig["subgacc_sjoin_fill_v2"] = (C.c_int, [C.POINTER(JoinDesc), vp])
-    sig["subgacc_publish_words"] = (C.c_int, [vp, i64, vp, vp])
-    sig["subgacc_rows_to_headed"] = (C.c_int, [vp, i64, vp, vp, i32, i64, vp, vp, vp, vp])
-    sig["subgacc_sjoin_star_sizes"] = (C.c_int, [vp, i64, vp, vp, i64, i64, vp, vp, vp, sz, vp])
-    sig["subgacc_sjoin_relu_mean"] = (C.c_int, [C.POINTER(JoinDesc), vp, vp, i32, vp, vp, vp, vp])
-    sig["subgacc_sjoin_relu_attn"] = (C.c_int, [C.POINTER(JoinDesc), vp, vp, vp, i32, vp, vp, vp, vp])
-    sig["subgacc_sjoin_relu_attn_backward"] = (C.c_int, [C.POINTER(JoinDesc), vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp])
-    sig["subgacc_sjoin_counts_attn"] = (C.c_int, [C.POINTER(JoinDesc), vp, vp, vp, vp, vp])
-    sig["subgacc_sjoin_counts_attn_backward"] = (C.c_int, [C.POINTER(JoinDesc), vp, vp, vp, vp, vp, vp, vp])
-    sig["subgacc_lstm_aggr"] = (C.c_int, [vp, vp, i64, i32, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp])
-    sig["subgacc_lstm_aggr_backward"] = (C.c_int, [vp, vp, i64, i32, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp,
-                                                   vp, vp, vp])
-    sig["subgacc_lstm_aggr_hinge"] = (C.c_int, [vp, vp, vp, i64, i32, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp])
-    sig["subgacc_lstm_aggr_hinge_backward"] = (C.c_int, [vp, vp, vp, i64, i32, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp,
-                                                         vp, vp, vp, vp, vp, vp, vp, vp])
-    sig["subgacc_keyrows_columns_workspace_bytes"] = (sz, [i64])
-    sig["subgacc_keyrows_columns"] = (C.c_int, [vp, vp, i64, i32, i32, i32, i64, vp, vp, vp, vp, vp, sz, vp])
-    sig["subgacc_sjoin_key_counts"] = (C.c_int, [C.POINTER(JoinDesc), vp, vp, vp, vp, vp])
-    sig["subgacc_sjoin_key_counts_attn"] = (C.c_int, [C.POINTER(JoinDesc), vp, vp, vp, vp, vp, vp, vp, vp])
-    sig["subgacc_sjoin_key_counts_attn_backward"] = (C.c_int, [C.POINTER(JoinDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp])
-    sig["subgacc_sjoin_key_index"] = (C.c_int, [C.POINTER(JoinDesc), vp, vp, vp, vp, vp, vp])
-    assert set(sig) == set(SYMBOLS)
-    for name, (res, args) in sig.items():
+    for name, (res, args) in _TYPES.items():
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = args
-    if L.subgacc_abi_version() != 7:
-        raise SubgAccError("libsubgacc_hip.so ABI version mismatch")
+    if L.subgacc_abi_version() != ABI_VERSION:
+        raise SubgAccError(f"libsubgacc_hip.so ABI version mismatch: the library is {L.subgacc_abi_version()}, "
+                           f"include/subgacc.h is {ABI_VERSION}")
     _lib = L
     return L
 
