@@ -370,6 +370,7 @@ typedef struct subgacc_join_desc {
     int64_t *host_tail;
 } subgacc_join_desc;
 int subgacc_sjoin_fill_v2(const subgacc_join_desc *d, void *stream);
+/* The same rows written as fp16 or bf16, for callers that train in mixed precision: a second header, include/subgacc_half.h */
 
 /* The first model stage of the PPR / SPD / DEG encoders (utils.py:35-36 and main.py:170-196: a float payload, xz [R,2,1]) fused with
  * the join -- model.py:78-83, x = pe_embedding(xz).sum(dim=-2); xl, xr = MeanAggregation(x, ptr) -- for pe_embedding =

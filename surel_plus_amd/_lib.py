@@ -1,5 +1,6 @@
-"""ctypes binding of libsubgacc_hip.so, derived from the declarations of include/subgacc.h (the C ABI) when this module is
-imported: an entry point is declared there and defined under csrc/, and nothing here names it.
+"""ctypes binding of libsubgacc_hip.so, derived from the declarations of include/subgacc.h (the C ABI) and of include/subgacc_half.h
+(the join's rows in a 16-bit type) when this module is imported: an entry point is declared there and defined under csrc/, and
+nothing here names it.
 
 There is no CPU fallback: if the library is missing, or no gfx950 device is visible when a compute entry
 point is called, this module raises.  Error codes map onto the exceptions the reference raises for the
@@ -98,15 +99,26 @@ def _ctype(ctype, decl, ret=False):
     raise SubgAccError(f"{decl}: no ctypes type for the {'return' if ret else 'parameter'} type `{ctype}`")
 
 
-try:
-    with open(HEADER) as _f:
-        _TEXT = _f.read()
-except OSError as e:
-    raise SubgAccError(f"{HEADER} is missing or unreadable: the binding is derived from it") from e
+def _header_text(path):
+    try:
+        with open(path) as f:
+            return f.read()
+    except OSError as e:
+        raise SubgAccError(f"{path} is missing or unreadable: the binding is derived from it") from e
+
+
+_TEXT = _header_text(HEADER)
 DECLS = parse_header(_TEXT)
 _TYPES = bind_types(DECLS)
 SYMBOLS = tuple(DECLS)            # every entry point the header declares, in its order
 ABI_VERSION = int(re.search(r"^#define\s+SUBGACC_ABI_VERSION\s+(\d+)", _TEXT, re.M).group(1))
+# the second header (read after the first: a tree without include/ fails on subgacc.h): the same library, the same descriptor
+HALF_HEADER = os.path.join(os.path.dirname(HEADER), "subgacc_half.h")
+_HALF_TEXT = _header_text(HALF_HEADER)
+HALF_DECLS = parse_header(_HALF_TEXT)
+_TYPES.update(bind_types(HALF_DECLS))
+HALF_SYMBOLS = tuple(HALF_DECLS)
+HALF_F16, HALF_BF16 = (int(re.search(rf"^#define\s+SUBGACC_HALF_{n}\s+(\d+)", _HALF_TEXT, re.M).group(1)) for n in ("F16", "BF16"))
 
 
 _lib = None
@@ -117,7 +129,7 @@ VERBOSE = os.environ.get("SUBGACC_QUIET", "0") != "1"
 def build(force=False):
     """hipcc-compile csrc/*.hip for gfx950 into surel_plus_amd/libsubgacc_hip.so (in-tree)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))]
-    srcs.append(os.path.join(_HERE, "..", "include", "subgacc.h"))
+    srcs += [HEADER, HALF_HEADER]
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
         subprocess.check_call(["make", "-s", "-C", CSRC, "-j4", "all"])

@@ -86,20 +86,48 @@ def join_payload(z, encode, return_index=False):
     return JOIN_SFPTR, int(table.shape[1]), fields
 
 
-def _out_view(out, dev, k, R=None, worst=None):
-    """The join's float32 output [rows, 2, k]: a new tensor of R rows, or a view of the caller's buffer `out` -- its first R rows,
-    or, for a lazy join (R stays on the device), all of it, which must hold the worst case of `worst` rows."""
+def _out_view(out, dev, k, R=None, worst=None, dtype=torch.float32):
+    """The join's output [rows, 2, k] (float32; dtype=: the rows of the 16-bit form): a new tensor of R rows, or a view of the caller's
+    buffer `out` -- its first R rows, or, for a lazy join (R stays on the device), all of it, which must hold the worst case of
+    `worst` rows."""
     if out is None:
-        return torch.empty((R, 2, k), dtype=torch.float32, device=dev)
+        return torch.empty((R, 2, k), dtype=dtype, device=dev)
     need = R if worst is None else worst
-    if out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev or out.numel() < need * 2 * k:
-        raise ValueError(f"out= must be a contiguous float32 buffer on the store's device with room for {need} rows of 2 x {k} "
+    if out.dtype != dtype or not out.is_contiguous() or out.device != dev or out.numel() < need * 2 * k:
+        raise ValueError(f"out= must be a contiguous {str(dtype)[6:]} buffer on the store's device with room for {need} rows of 2 x {k} "
                          "(R rows; lazy=True: the worst case, S * max_len)")
     rows = R if worst is None else out.numel() // (2 * k)
     return out.view(-1)[: rows * 2 * k].view(rows, 2, k)
 
 
-def sjoin(spg, own, partner, encode=None, ptr_mode=True, return_index=False, pair_block=0, out=None, lazy=False, star=False):
+def _half_code(dtype, who, refused):
+    """0 for dtype None / torch.float32 (the f32 rows); SUBGACC_HALF_F16 / SUBGACC_HALF_BF16 (include/subgacc_half.h) for torch.float16 /
+    torch.bfloat16 -- after a ValueError for the first entry of `refused()` {what the call was given: bool} that holds: the 16-bit rows
+    are those of subgacc_sjoin_fill_half's scope, and what lies outside it is refused here, before any device work.  (`refused` is
+    called for a 16-bit dtype only: the f32 step pays one comparison.)"""
+    if dtype is None or dtype == torch.float32:
+        return 0
+    code = {torch.float16: _lib.HALF_F16, torch.bfloat16: _lib.HALF_BF16}.get(dtype)
+    if code is None:
+        raise ValueError(f"{who}: dtype is None, torch.float32, torch.float16 or torch.bfloat16, not {dtype!r}")
+    for what, given in refused().items():
+        if given:
+            raise ValueError(f"{who}: dtype={dtype} (16-bit rows: pairs with segment pointers over 32-bit LP keys or a packed SFptr "
+                             f"store) does not go with {what}")
+    return code
+
+
+def _half_store_refusals(x):
+    """what _half_code refuses about the store `x` (anything that is not one of the library's stores is uploaded as a packed SFptr
+    or float store: its payload type says which)"""
+    data = None if getattr(x, "payload_is_slot", False) else getattr(x, "data", None)
+    return {"a HeadedSpG (headed rows)": isinstance(x, HeadedSpG),
+            "a float64 store (the PPR payload)": data is not None and str(data.dtype).endswith("float64"),
+            "64-bit keys": bool(getattr(x, "key64", False)),
+            "key_rows=False (strided rows of table slots)": bool(getattr(x, "payload_is_slot", False)) and not getattr(x, "keyrows", False)}
+
+
+def sjoin(spg, own, partner, encode=None, ptr_mode=True, return_index=False, pair_block=0, out=None, lazy=False, star=False, dtype=None):
     """Generic segment join (include/subgacc.h: the layout's size pass + subgacc_sjoin_fill_v2) over any store: its rows are described
     by spg.join_rows(), its payload by join_payload().
 
@@ -114,9 +142,17 @@ def sjoin(spg, own, partner, encode=None, ptr_mode=True, return_index=False, pai
     ONE call; eagerly it runs alone first (no output), the host reads [R, status] from pinned memory, and the fill follows.
     star=True: a star list (SUBGACC_JOIN_OPT_STAR, gather_star): own = P source rows, partner = P*K target rows, pair_block = K;
     the S = 2*P*K segments are those of the expanded list [own.repeat_interleave(K) | partner] and its mirror.
+    dtype=torch.float16 / torch.bfloat16: xz in that type, bit for bit xz.to(dtype) of the float32 rows, written by
+    subgacc_sjoin_fill_half (include/subgacc_half.h) behind the same size pass -- half the bytes of the join's largest output, for
+    callers that train under autocast.  Mirrored lists (pair_block > 0) with segment pointers over a keyed store, the key rows of a
+    step or a packed SFptr store with its table, k = 2 .. 5; ValueError for ptr_mode=False, return_index, lazy, star, a HeadedSpG, a
+    float64 store, 64-bit keys and rows of table slots.  out=: a buffer of that dtype.  None / torch.float32: the rows as ever.
     Returns (xz, ind, flags): xz float32 [R,2,k] (or int32 [R,2] index pairs when return_index), ind = int64 [S+1]
     segment pointers (ptr_mode) or int64 [R] segment ids, flags the join's int32[4] status words.
     """
+    half = _half_code(dtype, "sjoin", lambda: {"ptr=False (segment ids)": not ptr_mode, "return_index": return_index, "lazy=True": lazy,
+                                               "star=True": star, "a list that is not mirrored (pair_block <= 0)": pair_block <= 0,
+                                               **_half_store_refusals(spg)})
     L, dev = lib(), spg.device
     S = 2 * partner.numel() if star else own.numel()
     own = own.contiguous()
@@ -163,6 +199,12 @@ def sjoin(spg, own, partner, encode=None, ptr_mode=True, return_index=False, pai
             check(getattr(L, fn)(ptr(lens), spg.n_rows, ptr(own), ptr(partner), S, ptr(seg), ptr(flags), ptr(ws), ws.numel(), st))
         if not lazy:
             R = _size_and_row_check(seg, S, flags, spg.n_rows)     # the one host round trip
+    if half:        # the rows in 16 bits: the same descriptor, no out_* field, the library's second entry point
+        res = _out_view(out, dev, k, R, dtype=dtype)
+        with _timed("sjoin_fill_half"):
+            if R:
+                check(L.subgacc_sjoin_fill_half(ctypes.byref(_lib.join_desc(JOIN_ROWS, kind, **desc)), half, ptr(res), st))
+        return res, seg, flags
     if return_index and kind == JOIN_SFPTR:          # (a float store answers with its xz, as bgather() wants it)
         res = desc["out_idx"] = torch.empty((R, 2), dtype=torch.int32, device=dev)
     else:
@@ -242,14 +284,16 @@ def _checked(out, ind, flags, lazy=False):
     return out, ind
 
 
-def gather(edge, x, device=None, ptr=True, encode=None, out=None, lazy=False):
+def gather(edge, x, device=None, ptr=True, encode=None, out=None, lazy=False, dtype=None):
     """train.py:13-45.  Left blocks (S_u with S_v looked up) then right blocks, per pair in batch order.
-    out= / lazy=: see sjoin (a serving loop's forms: caller-owned output buffer, no host round trip)."""
+    out= / lazy=: see sjoin (a serving loop's forms: caller-owned output buffer, no host round trip).
+    dtype=torch.float16 / torch.bfloat16: xz in that type (sjoin: what autocast would make of the float32 rows, bit for bit)."""
+    _half_code(dtype, "gather", lambda: {"ptr=False (segment ids)": not ptr, "lazy=True": lazy, **_half_store_refusals(x)})
     spg = _as_spg(x)
     e = _as_rows(edge, spg.device)
     # own = [u.. | v..] is the contiguous [2, B] tensor itself; the mirrored partner list [v.. | u..] is derived by the kernels
     own = e.contiguous().view(-1)
-    return _checked(*sjoin(spg, own, None, encode, ptr_mode=ptr, pair_block=e.shape[1], out=out, lazy=lazy), lazy=lazy)
+    return _checked(*sjoin(spg, own, None, encode, ptr_mode=ptr, pair_block=e.shape[1], out=out, lazy=lazy, dtype=dtype), lazy=lazy)
 
 
 def _star_rows(source, targets):
@@ -528,12 +572,22 @@ class StepBuffers:
     (subgacc_sjoin_sizes_rows) and the index form over the key rows (subgacc_sjoin_key_index): neither xz, nor an output buffer of the row
     form, nor segment ids.  The buffers are those of "counts" without `counts`, plus `pairs` int32 [S * (M*m+1), 2] (the worst case; the
     first seg[-1] rows are a step's result) and the size pass's workspace.  Same refusals, and triplets=True (HONet has no LSTM
-    aggregation, model_horder.py:56-57)."""
+    aggregation, model_horder.py:56-57).
+    dtype=torch.float16 / torch.bfloat16: `out` -- the largest buffer of the set -- is allocated in that type, half the bytes, and the
+    step's join writes it through subgacc_sjoin_fill_half (sjoin(dtype=)); sample_and_gather(buffers=) must ask for the same dtype.
+    The row form over 32-bit key rows with segment pointers: ValueError for ptr=False, triplets=True, a stage, key_rows=False, a shape
+    with 64-bit keys or none, and batch=."""
 
     def __init__(self, csr, pairs, num_walks=200, num_steps=3, uniq_capacity=1 << 17, out=None, dedup_roots=False, rng="philox",
                  key_rows=True, sort_roots=True, batch=None, align_rows=True, order=None, ptr=True, triplets=False, stage=None,
-                 table_rows=2048):
-        from .sampler import FUSED_MAX_Q, as_rank
+                 table_rows=2048, dtype=None):
+        from .sampler import FUSED_MAX_Q, as_rank, key_rows_form
+        self.half = _half_code(dtype, "StepBuffers", lambda: {
+            "ptr=False (segment ids)": not ptr, "triplets=True": triplets, f"stage={stage!r}": stage is not None,
+            "key_rows=False (strided rows of table slots)": not key_rows,
+            f"num_walks = {num_walks}, num_steps = {num_steps} (64-bit keys, or no key rows)": key_rows_form(int(num_walks), int(num_steps)) != 32,
+            "batch= (many batches per step)": batch is not None})
+        self.dtype = dtype if self.half else torch.float32
         self.stage, self.T = stage, int(table_rows)
         if stage not in (None,) + _KEY_STAGES:
             raise ValueError(f"StepBuffers: stage is None (the row form), 'counts', 'counts_attn' or 'index', not {stage!r}")
@@ -580,7 +634,6 @@ class StepBuffers:
         self.roots = torch.empty(n, dtype=torch.int32, device=dev)
         self.nsize = torch.empty(n, dtype=torch.int32, device=dev)
         self.ids = torch.empty(n * self.stride, dtype=torch.int32, device=dev)
-        from .sampler import key_rows_form
         form = key_rows_form(self.M, self.m) if key_rows else 0
         self.keyrows = bool(form)                 # rows of LP keys: no table, no feature table
         self.key64 = form == 64                   # ... 64-bit keys (4-hop walks with M >= 128): `slot` is int64
@@ -629,8 +682,8 @@ class StepBuffers:
         self.ws = torch.empty(max(L.subgacc_sjoin_workspace_bytes(S), 8), dtype=torch.uint8, device=dev)
         self.feat = None if self.keyrows else torch.empty((self.capacity + 1, self.k), dtype=torch.float32, device=dev)
         if out is not None:         # room for the worst case: S segments (2B; triplets: 4B) of M*m+1 members
-            _out_view(out, dev, self.k, worst=S * self.Q)
-        self.out = out if out is not None else torch.empty(S * self.Q * 2 * self.k, dtype=torch.float32, device=dev)
+            _out_view(out, dev, self.k, worst=S * self.Q, dtype=self.dtype)
+        self.out = out if out is not None else torch.empty(S * self.Q * 2 * self.k, dtype=self.dtype, device=dev)
         self.segid = None if self.ptr else torch.empty(S * self.Q, dtype=torch.int64, device=dev)
 
     def _counts_buffer(self, S, T, dev):
@@ -840,17 +893,22 @@ def _buffered_step(csr, e, bufs, seed, out, fit=False):
         keys = bufs.table[: bufs.capacity * 8].view(torch.int64)
         check(L.subgacc_unpack_lp(ptr(keys), bufs.capacity, None, M, m, None, None, ptr(bufs.feat), 1, st))
         kind, payload = JOIN_SFPTR, dict(table=bufs.feat, table_rows=bufs.capacity + 1, k=k)
-    xz = _out_view(out if out is not None else bufs.out, dev, k, worst=S * bufs.Q)
-    with _timed("sjoin_fill"):
-        join_fill(JOIN_ROWS, kind, st, row_len=bufs.nsize, n_rows=n, row_stride=bufs.stride, ids=bufs.ids, payload=bufs.slot, own=own,
-                  partner=partner, S=S, seg=bufs.seg, pair_block=PB, out_xz=xz, out_segid=bufs.segid, flags=flags, **payload)
+    xz = _out_view(out if out is not None else bufs.out, dev, k, worst=S * bufs.Q, dtype=bufs.dtype)
+    rows = dict(row_len=bufs.nsize, n_rows=n, row_stride=bufs.stride, ids=bufs.ids, payload=bufs.slot, own=own, partner=partner, S=S,
+                seg=bufs.seg, pair_block=PB, flags=flags)
+    if bufs.half:       # 16-bit rows (StepBuffers(dtype=): 32-bit key rows, segment pointers)
+        with _timed("sjoin_fill_half"):
+            check(L.subgacc_sjoin_fill_half(ctypes.byref(_lib.join_desc(JOIN_ROWS, kind, **rows, **payload)), bufs.half, ptr(xz), st))
+    else:
+        with _timed("sjoin_fill"):
+            join_fill(JOIN_ROWS, kind, st, out_xz=xz, out_segid=bufs.segid, **rows, **payload)
     sets = _step_sets(csr, bufs, cfg, rr, step_id)
     # ptr=False / triplets: the ids of the first seg[-1] rows (as xz: a view of the whole buffer, the row count stays on the device)
     return xz, (bufs.seg if bufs.ptr else _with_pointers(bufs.segid[: xz.shape[0]], bufs.seg)), sets
 
 
 def sample_and_gather(csr, edge, num_walks=200, num_steps=3, seed=111413, rng="philox", dedup_roots=False, out=None,
-                      lazy=False, strided=None, buffers=None, order=None, ptr=True, **kw):
+                      lazy=False, strided=None, buffers=None, order=None, ptr=True, dtype=None, **kw):
     """The on-demand form of the path in one call: sample the endpoints of `edge` [2, B] (node ids), build their SpG
     rows, join -> (xz, indptr, sets), the same (xz, indptr) as `gather(edge, subg_matrix(G, arange(N)))` would give for sets
     drawn with the same RNG (Philox keys every walk by (seed, root id, walk, step), so a root's set does not depend on
@@ -866,9 +924,19 @@ def sample_and_gather(csr, edge, num_walks=200, num_steps=3, seed=111413, rng="p
     ptr=False: the second result is the segment id (0 .. 2B-1) of every row of xz, int64 [R], with the pointers as its
     .seg_pointers -- gather(ptr=False) of train.py:25-30, what the reference's --aggrs lstm runs with (main.py:217); the join
     writes the ids next to the rows.  With buffers=StepBuffers(..., ptr=False): a view of the buffers' id buffer, as xz is of
-    the output buffer."""
-    from .sampler import as_rank
+    the output buffer.
+    dtype=torch.float16 / torch.bfloat16: xz in that type (sjoin(dtype=): bit for bit the float32 rows under .to(dtype), half the
+    bytes written); the step's rows of 32-bit LP keys with segment pointers -- ValueError for ptr=False, lazy=True, key_rows=False,
+    strided=False and a shape with 64-bit keys or without key rows.  buffers= must have been made with the same dtype."""
+    from .sampler import as_rank, key_rows_form
     from .spg import sample_spg
+    half = _half_code(dtype, "sample_and_gather", lambda: {
+        "ptr=False (segment ids)": not ptr, "lazy=True": lazy, "key_rows=False (strided rows of table slots)": not kw.get("key_rows", True),
+        "strided=False (a packed copy of the step's rows)": strided is False,
+        f"num_walks = {num_walks}, num_steps = {num_steps} (64-bit keys, or no key rows)": key_rows_form(int(num_walks), int(num_steps)) != 32})
+    if buffers is not None and half != getattr(buffers, "half", 0):
+        raise ValueError(f"sample_and_gather: dtype={dtype} but buffers= were made with dtype={getattr(buffers, 'dtype', None)}: "
+                         "StepBuffers(..., dtype=) allocates `out` in the type the step writes")
     order = as_rank(csr, order)
     e = _as_rows(edge, csr.device)
     if buffers is None and e.dim() != 2:
@@ -903,10 +971,11 @@ def sample_and_gather(csr, edge, num_walks=200, num_steps=3, seed=111413, rng="p
                          strided=strided, order=order, **kw)
     table = z.slot_table() if sets.strided else sets.feature_table()
     if rows is not None:
-        xz, ind = gather(rows, z, e.device, ptr=bool(ptr), encode=table, out=out, lazy=lazy)
+        xz, ind = gather(rows, z, e.device, ptr=bool(ptr), encode=table, out=out, lazy=lazy, dtype=dtype)
     else:
         own, partner = _arange_segments(B, e.device)
-        xz, ind = _checked(*sjoin(_as_spg(z), own, partner, table, ptr_mode=bool(ptr), pair_block=B, out=out, lazy=lazy), lazy=lazy)
+        xz, ind = _checked(*sjoin(_as_spg(z), own, partner, table, ptr_mode=bool(ptr), pair_block=B, out=out, lazy=lazy, dtype=dtype),
+                           lazy=lazy)
     if lazy:      # the join's status word travels with the sets' own: resolve() raises IndexError for a row outside the store
         sets._join_flags = getattr(ind, "join_flags", None)
     return xz, ind, sets
