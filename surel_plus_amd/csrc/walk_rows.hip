@@ -9,10 +9,18 @@
 // per-root table of 512 or 1,024 slots -- with the hop count MH and the slots per lane SPL as template parameters:
 //   * the walk is straight-line code (no step loop, no per-step mode tests), the later hops' Philox draws are issued
 //     while the first hop's neighbour is in flight, and each visit's LDS atomics run under the NEXT hop's row load;
-//   * a lane owns SPL consecutive table slots in the epilogue, read with 8/16-byte LDS loads;
+//   * a lane owns SPL table slots in the epilogue, in chunks of four, read with 16-byte LDS loads;
 //   * the bucket sort takes its in-bucket arrival order from the histogram's returning atomic (one atomic pass, not two);
 //   * 32-bit compares / shifts wherever the 64-bit ones of the general kernel were only generality.
-// Bit-identical rows, sizes and table tags (tests/test_gpu_parity.py runs both forms against the oracle).
+// Bit-identical rows, sizes and table tags: tests/test_gpu_walk_rows_edges.py runs every instantiation the launcher reaches at its
+// boundary shapes against the oracle (tests/walk_rows_edges.py restates the launcher and lists those instantiations);
+// tests/test_gpu_sampler.py, test_gpu_fuzz.py, test_gpu_round4.py and test_gpu_round6.py run whole batches of both forms.
+//
+// The kernel is ONE function on purpose.  Cut into phase functions -- as members of a struct of the workgroup's state, and as free
+// functions that take their operands by value -- every instantiation came out as different instructions, some with other register
+// counts and 12 bytes of scratch: the compiler optimises a function on its own before it inlines it.  The helpers in front of
+// the kernel are the pieces for which the instructions stayed the same (tools/kernel_digest.py, profiles/walk_rows_split_isa.log);
+// where a piece is still written out beside its helper, a comment says which caller changed.
 #include <stdlib.h>
 
 #include <type_traits>
@@ -61,6 +69,95 @@ namespace subgacc {
 #define SG_LAST_HOP_ID 1
 #endif
 
+// ------------------------------------------------------------------------------------ pieces the kernel's phases share
+// (free functions that take what they need by value: each is compiled on its own before it is inlined, and one that reached its
+//  operands through a pointer to the kernel's state came out as different instructions)
+
+// Slot ownership (the kernel's clears, and the epilogues' member fetch): a lane owns the 4-slot chunks g = c*NT + tid, c < SPL/4 --
+// consecutive lanes on consecutive 16-byte words, so the 16-byte LDS accesses are dense (a lane-contiguous
+// layout, 32 bytes apart, cost 39 % of the LDS cycles in bank conflicts at SPL = 8).
+// a lane's chunks into registers: ids, (MINQ) first-visit numbers, counts
+template <int SPL, int NT, bool K32, bool MINQ, class CntT>
+__device__ __forceinline__ void rows_fetch_slots(const int32_t *keys, const uint32_t *minq, const CntT *pk, int tid, int32_t (&idv)[SPL], uint32_t *mtag,
+                                                 CntT (&cv)[SPL]) {
+#pragma unroll
+    for (int c = 0; c < SPL / 4; ++c) {
+        const int g = c * NT + tid;
+        const int4 kk = ((const int4 *)keys)[g];
+        idv[4 * c] = kk.x, idv[4 * c + 1] = kk.y, idv[4 * c + 2] = kk.z, idv[4 * c + 3] = kk.w;
+        if (MINQ) {
+            const uint4 qq = ((const uint4 *)minq)[g];
+            mtag[4 * c] = qq.x, mtag[4 * c + 1] = qq.y, mtag[4 * c + 2] = qq.z, mtag[4 * c + 3] = qq.w;
+        }
+        if (K32) {
+            const uint4 v = ((const uint4 *)pk)[g];
+            cv[4 * c] = (CntT)v.x, cv[4 * c + 1] = (CntT)v.y, cv[4 * c + 2] = (CntT)v.z, cv[4 * c + 3] = (CntT)v.w;
+        } else {
+            const uint4 v0 = ((const uint4 *)pk)[2 * g], v1 = ((const uint4 *)pk)[2 * g + 1];
+            cv[4 * c] = (CntT)(((unsigned long long)v0.y << 32) | v0.x);
+            cv[4 * c + 1] = (CntT)(((unsigned long long)v0.w << 32) | v0.z);
+            cv[4 * c + 2] = (CntT)(((unsigned long long)v1.y << 32) | v1.x);
+            cv[4 * c + 3] = (CntT)(((unsigned long long)v1.w << 32) | v1.z);
+        }
+    }
+}
+
+// level 1's geometry: B <= min(T/4, NT) buckets of 2^bshift ids over the set's ns ids in [mn, mx]
+template <int T, int NT>
+__device__ __forceinline__ void rows_bucket_geometry(int32_t ns, int32_t mn, int32_t mx, int &B, int &bshift) {
+    int logb = 0;
+    while ((1 << logb) < ns && (2 << logb) <= T / 4 && (2 << logb) <= NT) ++logb;
+    B = 1 << logb;
+    const uint32_t range = (uint32_t)(mx - mn) + 1u;
+    const int Ls = (range <= 1u) ? 0 : (32 - __builtin_clz(range - 1u));
+    bshift = Ls > logb ? Ls - logb : 0;      // (id - mn) < 2^Ls, and ns <= range => logb <= Ls
+}
+
+// level 1 of the key rows' sort: exclusive scan over the B <= NT buckets, one bucket per lane: wave scan, then (two waves) the
+// wave totals through LDS -> the largest count
+// (a wave's base = the totals of the waves in front of it: at most NT / 64 - 1 of them, spelled out -- as a loop over
+//  tid / 64 the compiler vectorised it into 16-byte reads with a scalar tail, ~60 instructions for one addition)
+template <int NT>
+__device__ __forceinline__ int32_t rows_level1_scan(int32_t *start, int32_t *red, int B, int tid) {
+    const int32_t c = tid < B ? start[tid] : 0;
+    const int32_t inc = wave_scan_add_i32_incl(c);     // inclusive scan over the wave
+    const int32_t mc = wave_red_max_i32(c);
+    int32_t base = 0, maxc = mc;
+    if (NT > kWave) {
+        if ((tid & (kWave - 1)) == kWave - 1) red[12 + tid / kWave] = inc, red[4 + tid / kWave] = mc;
+        __syncthreads();
+#pragma unroll
+        for (int w2 = 0; w2 < NT / kWave - 1; ++w2) base += w2 < tid / kWave ? red[12 + w2] : 0;
+        maxc = red[4];
+#pragma unroll
+        for (int w2 = 1; w2 < NT / kWave; ++w2) maxc = max(maxc, red[4 + w2]);
+    }
+    const int32_t excl = base + inc - c;
+    if (tid < B) start[tid] = excl;
+    if (tid == B - 1) start[B] = excl + c;
+    return maxc;
+}
+
+// Where a member goes at level 2: its level-1 bucket b1 (from lo1 on, kb / fine members) is cut into kb parts of equal id width;
+// ido = id - min, off = the member's offset in the bucket's id window, sub = its part
+struct RowsPart {
+    uint32_t lo1, kb, off, sub;
+};
+__device__ __forceinline__ RowsPart rows_part(const int32_t *start, uint32_t ido, uint32_t b1, int bshift, uint32_t fine) {
+    RowsPart p;
+    p.lo1 = (uint32_t)start[b1];
+    p.kb = ((uint32_t)start[b1 + 1] - p.lo1) * fine;
+    p.off = ido - (b1 << bshift);                                                  // < 2^bshift
+    p.sub = bshift ? __umulhi(p.off << (32 - bshift), p.kb) : 0u;                 // floor(off * kb / 2^bshift) < kb
+    return p;
+}
+
+// one more member in the 16-bit counter idx (two per word) -> its arrival order
+__device__ __forceinline__ uint32_t rows_count16(uint32_t *cnt2, uint32_t idx) {
+    const uint32_t sh = (idx & 1u) * 16u;
+    return (atomicAdd(&cnt2[idx >> 1], 1u << sh) >> sh) & 0xFFFFu;
+}
+
 // NT lanes per workgroup (256, or 128 with two walks per lane: twice the roots per CU where the 512-slot table leaves the
 // LDS for them), SPL table slots per lane, T = NT * SPL.
 // REC: 0 = plain CSR; 8 = packed 8-byte hop records (int32 row offsets); 16 = 16-byte records (int64 row offsets)
@@ -81,11 +178,10 @@ template <bool IDX64, int RNG, int MH, int SPL, int NT, int REC = 0, bool K32 = 
 //  one word each, no loops over the wave index for the compiler to vectorise): all eight wave slots of a SIMD; how many roots a CU
 //  then holds is the launch's choice, through the LDS it asks for: SG_ROWS_KR_LDS_MIN)
 __global__ __launch_bounds__(NT, K32 ? (KR ? 6 : 5) : (KR ? 5 : (NT == 128 ? 7 : 8))) __attribute__((amdgpu_num_sgpr(SG_ROWS_SGPR))) void walk_rows_kernel(const WalkArgs a) {
-    static_assert(!KR || SPL % 4 == 0, "key rows: 4-slot chunks");
     constexpr bool KR64 = KR && !K32;      // rows of 64-bit LP keys
     extern __shared__ __align__(16) unsigned char lds_raw[];
     using CntT = typename std::conditional<K32, uint32_t, unsigned long long>::type;
-    static_assert(SPL % 4 == 0 || (SPL == 2 && !K32), "slot ownership: 4-slot chunks, or two slots with 64-bit counts");
+    static_assert(SPL % 4 == 0, "slot ownership: 4-slot chunks");
     constexpr CntT kNoKey = (CntT)~(CntT)0;                       // empty marker of the fold table
     constexpr int T = SPL * NT;                                   // 512 or 1,024 slots
     constexpr int TSHIFT = T == 1024 ? 22 : 23;                   // 32 - log2(T)
@@ -129,24 +225,18 @@ __global__ __launch_bounds__(NT, K32 ? (KR ? 6 : 5) : (KR ? 5 : (NT == 128 ? 7 :
         return;
     }
     // while the root's two dependent loads (query -> row pointer) are in flight: clear what does not depend on them
-    // Slot ownership (clears, and the epilogue's member fetch): a lane owns the 4-slot chunks g = c*NT + tid, c < SPL/4 --
-    // consecutive lanes on consecutive 16-byte words, so the 16-byte LDS accesses below are dense (a lane-contiguous
-    // layout, 32 bytes apart, cost 39 % of the LDS cycles in bank conflicts at SPL = 8).  SPL = 2: slots 2*tid, 2*tid+1.
-    if (SPL % 4 == 0) {
+    // (this clear and the one behind the first-hop shuffle are written out twice: as one function called from both places, the branch
+    //  around the repeated endpoint above came out with its sense swapped in every instantiation)
 #pragma unroll
-        for (int c = 0; c < SPL / 4; ++c) {
-            const int g = c * NT + tid;
-            if (K32) {
-                ((uint4 *)pk)[g] = make_uint4(0u, 0u, 0u, 0u);
-            } else {
-                ((uint4 *)pk)[2 * g] = make_uint4(0u, 0u, 0u, 0u);
-                ((uint4 *)pk)[2 * g + 1] = make_uint4(0u, 0u, 0u, 0u);
-            }
-            if (!KR) ((uint4 *)minq)[g] = make_uint4(~0u, ~0u, ~0u, ~0u);
+    for (int c = 0; c < SPL / 4; ++c) {
+        const int g = c * NT + tid;
+        if (K32) {
+            ((uint4 *)pk)[g] = make_uint4(0u, 0u, 0u, 0u);
+        } else {
+            ((uint4 *)pk)[2 * g] = make_uint4(0u, 0u, 0u, 0u);
+            ((uint4 *)pk)[2 * g + 1] = make_uint4(0u, 0u, 0u, 0u);
         }
-    } else {
-        ((uint4 *)pk)[tid] = make_uint4(0u, 0u, 0u, 0u);
-        ((uint2 *)minq)[tid] = make_uint2(~0u, ~0u);
+        if (!KR) ((uint4 *)minq)[g] = make_uint4(~0u, ~0u, ~0u, ~0u);
     }
     if (!KR && tid < kSpgFold) {
         fk[tid] = kNoKey;
@@ -167,19 +257,13 @@ __global__ __launch_bounds__(NT, K32 ? (KR ? 6 : 5) : (KR ? 5 : (NT == 128 ? 7 :
     {   // keys, with the root already in its slot as member 0 (its minq = 0 is stored after the barrier-free clear above:
         // same lane order is not guaranteed across waves, so the root's lane writes BOTH of its words here)
         const uint32_t hroot = ((uint32_t)root * 2654435761u) >> TSHIFT;
-        if (SPL % 4 == 0) {
 #pragma unroll
-            for (int c = 0; c < SPL / 4; ++c) {
-                const uint32_t x0 = 4u * (uint32_t)(c * NT + tid);
-                ((int4 *)keys)[c * NT + tid] = make_int4(x0 == hroot ? root : -1, x0 + 1u == hroot ? root : -1,
-                                                         x0 + 2u == hroot ? root : -1, x0 + 3u == hroot ? root : -1);
-            }
-            if (!KR && ((hroot >> 2) % (uint32_t)NT) == (uint32_t)tid) minq[hroot] = 0u;   // the lane that cleared this word, after its clear
-        } else {
-            const uint32_t x0 = 2u * (uint32_t)tid;
-            ((int2 *)keys)[tid] = make_int2(x0 == hroot ? root : -1, x0 + 1u == hroot ? root : -1);
-            if ((hroot >> 1) == (uint32_t)tid) minq[hroot] = 0u;
+        for (int c = 0; c < SPL / 4; ++c) {
+            const uint32_t x0 = 4u * (uint32_t)(c * NT + tid);
+            ((int4 *)keys)[c * NT + tid] = make_int4(x0 == hroot ? root : -1, x0 + 1u == hroot ? root : -1,
+                                                     x0 + 2u == hroot ? root : -1, x0 + 3u == hroot ? root : -1);
         }
+        if (!KR && ((hroot >> 2) % (uint32_t)NT) == (uint32_t)tid) minq[hroot] = 0u;   // the lane that cleared this word, after its clear
     }
     if (a.cap_root && rdeg64 > kNeighCap) rdeg64 = kNeighCap;
     const int64_t obase = i * (int64_t)a.pitch;
@@ -300,19 +384,15 @@ __global__ __launch_bounds__(NT, K32 ? (KR ? 6 : 5) : (KR ? 5 : (NT == 128 ? 7 :
         }
         __syncthreads();
         // the scratch hash goes back to being an empty count table (the same lanes on the same words as the clear above)
-        if (SPL % 4 == 0) {
 #pragma unroll
-            for (int c = 0; c < SPL / 4; ++c) {
-                const int g = c * NT + tid;
-                if (K32) {
-                    ((uint4 *)pk)[g] = make_uint4(0u, 0u, 0u, 0u);
-                } else {
-                    ((uint4 *)pk)[2 * g] = make_uint4(0u, 0u, 0u, 0u);
-                    ((uint4 *)pk)[2 * g + 1] = make_uint4(0u, 0u, 0u, 0u);
-                }
+        for (int c = 0; c < SPL / 4; ++c) {
+            const int g = c * NT + tid;
+            if (K32) {
+                ((uint4 *)pk)[g] = make_uint4(0u, 0u, 0u, 0u);
+            } else {
+                ((uint4 *)pk)[2 * g] = make_uint4(0u, 0u, 0u, 0u);
+                ((uint4 *)pk)[2 * g + 1] = make_uint4(0u, 0u, 0u, 0u);
             }
-        } else {
-            ((uint4 *)pk)[tid] = make_uint4(0u, 0u, 0u, 0u);
         }
     } else {
         // w % deg for w < 256 and deg <= M <= 256 without a division per walk: with inv = ceil(2^16 / deg), floor(w * inv / 2^16) is the
@@ -490,22 +570,7 @@ __global__ __launch_bounds__(NT, K32 ? (KR ? 6 : 5) : (KR ? 5 : (NT == 128 ? 7 :
         int cnt = 0;
         uint32_t umn = ~0u;         // an empty slot is -1: the largest unsigned value, the smallest signed one
         int32_t vmax = -1;
-#pragma unroll
-        for (int c = 0; c < SPL / 4; ++c) {
-            const int g = c * NT + tid;
-            const int4 kk = ((const int4 *)keys)[g];
-            idv[4 * c] = kk.x, idv[4 * c + 1] = kk.y, idv[4 * c + 2] = kk.z, idv[4 * c + 3] = kk.w;
-            if (K32) {
-                const uint4 v = ((const uint4 *)pk)[g];
-                kv[4 * c] = (CntT)v.x, kv[4 * c + 1] = (CntT)v.y, kv[4 * c + 2] = (CntT)v.z, kv[4 * c + 3] = (CntT)v.w;
-            } else {
-                const uint4 v0 = ((const uint4 *)pk)[2 * g], v1 = ((const uint4 *)pk)[2 * g + 1];
-                kv[4 * c] = (CntT)(((unsigned long long)v0.y << 32) | v0.x);
-                kv[4 * c + 1] = (CntT)(((unsigned long long)v0.w << 32) | v0.z);
-                kv[4 * c + 2] = (CntT)(((unsigned long long)v1.y << 32) | v1.x);
-                kv[4 * c + 3] = (CntT)(((unsigned long long)v1.w << 32) | v1.z);
-            }
-        }
+        rows_fetch_slots<SPL, NT, K32, false>(keys, minq, pk, tid, idv, nullptr, kv);
 #pragma unroll
         for (int u = 0; u < SPL; ++u) {
             cnt += idv[u] != -1 ? 1 : 0;
@@ -558,12 +623,8 @@ __global__ __launch_bounds__(NT, K32 ? (KR ? 6 : 5) : (KR ? 5 : (NT == 128 ? 7 :
         constexpr int kFineAbove = 12;                 // a finer level from this many members in one (sub-)bucket on
         int32_t *start = (int32_t *)(lds_raw + (KR64 ? 16 : 8) * (size_t)a.stride);      // [B+1] level-1 counts, then offsets
         uint32_t *cnt2 = (uint32_t *)(start + NT + 4);                                   // [CW * NT] 16-bit counters of levels 2 and 3 (0 .. ns used), then offsets; 16-byte aligned
-        int logb = 0;
-        while ((1 << logb) < ns && (2 << logb) <= T / 4 && (2 << logb) <= NT) ++logb;
-        const int B = 1 << logb;
-        const uint32_t range = (uint32_t)(mx - mn) + 1u;
-        const int Ls = (range <= 1u) ? 0 : (32 - __builtin_clz(range - 1u));
-        const int bshift = Ls > logb ? Ls - logb : 0;
+        int B, bshift;
+        rows_bucket_geometry<T, NT>(ns, mn, mx, B, bshift);
         if (tid < B) start[tid] = 0;
         if (SG_SORT_ZERO_UPFRONT) ((uint4 *)cnt2)[tid] = make_uint4(0u, 0u, 0u, 0u);
         {
@@ -645,15 +706,7 @@ __global__ __launch_bounds__(NT, K32 ? (KR ? 6 : 5) : (KR ? 5 : (NT == 128 ? 7 :
             }
             __syncthreads();
             SG_HOOK_RSTAMP(12);
-            int32_t maxc;
-            {
-                const int32_t c = tid < B ? start[tid] : 0;
-                const int32_t inc = wave_scan_add_i32_incl(c);
-                maxc = wave_red_max_i32(c);
-                const int32_t excl = inc - c;
-                if (tid < B) start[tid] = excl;
-                if (tid == B - 1) start[B] = excl + c;
-            }
+            const int32_t maxc = rows_level1_scan<NT>(start, red, B, tid);
             __syncthreads();
             SG_HOOK_RSTAMP(13);
             int blo[EPL], bhi[EPL];
@@ -676,16 +729,15 @@ __global__ __launch_bounds__(NT, K32 ? (KR ? 6 : 5) : (KR ? 5 : (NT == 128 ? 7 :
                 for (int e = 0; e < EPL; ++e) {
                     if (e * NT >= ns) break;
                     if (e * NT + tid < ns) {
-                        const uint32_t lo1 = (uint32_t)start[bk[e]], kb = (uint32_t)start[bk[e] + 1] - lo1;
-                        const uint32_t off = ((uint32_t)(el[e] >> 32) - (uint32_t)mn) - (bk[e] << bshift);      // < 2^bshift
-                        const uint32_t sub = bshift ? __umulhi(off << (32 - bshift), kb) : 0u;                 // floor(off * kb / 2^bshift) < kb
-                        idx2[e] = lo1 + sub;
-                        const uint32_t sh = (idx2[e] & 1u) * 16u;
-                        pos[e] = (int32_t)((atomicAdd(&cnt2[idx2[e] >> 1], 1u << sh) >> sh) & 0xFFFFu);
+                        const RowsPart p = rows_part(start, (uint32_t)(el[e] >> 32) - (uint32_t)mn, bk[e], bshift, 1u);
+                        idx2[e] = p.lo1 + p.sub;
+                        pos[e] = (int32_t)rows_count16(cnt2, idx2[e]);
                     }
                 }
                 __syncthreads();
                 {   // exclusive scan of the ns + 1 level-2 counters, in place (offsets <= ns < 2^16): CW1 consecutive words per lane
+                    // (the table form's scan below is this one plus the waves' bases; as one function with that part under
+                    //  `if (NT > kWave)`, called from both, this kernel came out as different instructions)
                     uint32_t w[CW1];
                     int32_t s2 = 0;
 #pragma unroll
@@ -737,20 +789,16 @@ __global__ __launch_bounds__(NT, K32 ? (KR ? 6 : 5) : (KR ? 5 : (NT == 128 ? 7 :
             }
         } else {
             // A member's state across the phases of the sort: where its (sub-)bucket begins (while counting: the bucket's number), where it
-            // ends, the member's arrival order inside it -- positions and counts are <= ns <= 1,020 (checked at launch).  PACK: ONE word per
+            // ends, the member's arrival order inside it -- positions and counts are <= ns <= 1,020 (checked at launch).  ONE word per
             // member, 10 bits each, and the member's level-1 bucket worked out again wherever it is needed -- three more registers per
-            // member were 14 more VGPRs and a wave slot per SIMD, which the graph with id locality feels.  (!PACK, the plain registers of
-            // rounds 3-5, is kept as a form for the one-wave kernel, which loses ~4 % on collab to the new epilogue as a whole
-            // (profiles/r54_collab_bisect.log, r57_collab_levels_ab.log: not to the finer levels, not to occupancy, not to the unroll) --
-            // but unpacked it needs 80 VGPRs and spills, so it is off.)
+            // member were 14 more VGPRs and a wave slot per SIMD, which the graph with id locality feels.  (The plain registers of rounds
+            // 3-5 were tried here once more for the one-wave kernel's sake and lost: unpacked, this form needs 80 VGPRs and spills.)
             // What an LDS operation returns is never used in the pass that issued it outside the level loop: a lane's reads and returning
             // atomics of a pass are all in flight together.
-            constexpr bool PACK = true;
-            uint32_t s_hi[PACK ? 1 : EPL], s_pos[PACK ? 1 : EPL], s_bk[PACK ? 1 : EPL];
-            auto LO = [&](int e) -> uint32_t { return PACK ? (st[e] & 0x3FFu) : st[e]; };
-            auto HI = [&](int e) -> uint32_t { return PACK ? ((st[e] >> 10) & 0x3FFu) : s_hi[e]; };
-            auto POS = [&](int e) -> uint32_t { return PACK ? (st[e] >> 20) : s_pos[e]; };
-            auto BK = [&](int e) -> uint32_t { return PACK ? (((uint32_t)(el[e] >> 32) - (uint32_t)mn) >> bshift) : s_bk[e]; };
+            auto LO = [&](int e) -> uint32_t { return st[e] & 0x3FFu; };
+            auto HI = [&](int e) -> uint32_t { return (st[e] >> 10) & 0x3FFu; };
+            auto POS = [&](int e) -> uint32_t { return st[e] >> 20; };
+            auto BK = [&](int e) -> uint32_t { return ((uint32_t)(el[e] >> 32) - (uint32_t)mn) >> bshift; };
 #pragma unroll
             for (int e = 0; e < EPL; ++e) {
                 if (e * NT >= ns) break;
@@ -758,40 +806,19 @@ __global__ __launch_bounds__(NT, K32 ? (KR ? 6 : 5) : (KR ? 5 : (NT == 128 ? 7 :
                 if (x < ns) {
                     el[e] = A[x];
                     const uint32_t b1 = ((uint32_t)(el[e] >> 32) - (uint32_t)mn) >> bshift;
-                    if (!PACK) s_bk[e] = b1;
-                    (PACK ? st[e] : s_pos[e]) = (uint32_t)atomicAdd(&start[b1], 1);     // (the arrival order, as it comes)
+                    st[e] = (uint32_t)atomicAdd(&start[b1], 1);     // (the arrival order, as it comes)
                 }
             }
             __syncthreads();
             SG_HOOK_RSTAMP(12);
-            int32_t maxc;
-            {   // level 1: exclusive scan over the B <= NT buckets, one bucket per lane
-                const int32_t c = tid < B ? start[tid] : 0;
-                const int32_t inc = wave_scan_add_i32_incl(c);
-                const int32_t mc = wave_red_max_i32(c);
-                int32_t base = 0;
-                maxc = mc;
-                if (NT > kWave) {
-                    if ((tid & (kWave - 1)) == kWave - 1) red[12 + tid / kWave] = inc, red[4 + tid / kWave] = mc;
-                    __syncthreads();
-#pragma unroll
-                    for (int w2 = 0; w2 < NT / kWave - 1; ++w2) base += w2 < tid / kWave ? red[12 + w2] : 0;
-                    maxc = red[4];
-#pragma unroll
-                    for (int w2 = 1; w2 < NT / kWave; ++w2) maxc = max(maxc, red[4 + w2]);
-                }
-                const int32_t excl = base + inc - c;
-                if (tid < B) start[tid] = excl;
-                if (tid == B - 1) start[B] = excl + c;
-            }
+            int32_t maxc = rows_level1_scan<NT>(start, red, B, tid);
             __syncthreads();
             SG_HOOK_RSTAMP(13);
             const uint16_t *off2 = (const uint16_t *)cnt2;
             // (a crowded set's first trip through the level loop works the level-1 bounds out for itself and overwrites the state:
             //  the pass below is for the sets that skip the loop -- maxc is workgroup-uniform)
             const bool finer = SG_SORT_LEVELS > 0 && maxc > kFineAbove;
-            if (finer) {
-            } else if (PACK) {
+            if (!finer) {
                 uint32_t ta[EPL], tb[EPL];         // what the first pass asked the LDS for, until the second packs it
 #pragma unroll
                 for (int e = 0; e < EPL; ++e) {
@@ -802,12 +829,6 @@ __global__ __launch_bounds__(NT, K32 ? (KR ? 6 : 5) : (KR ? 5 : (NT == 128 ? 7 :
                 for (int e = 0; e < EPL; ++e) {
                     if (e * NT >= ns) break;
                     if (e * NT + tid < ns) st[e] = (st[e] << 20) | ta[e] | (tb[e] << 10);
-                }
-            } else {
-#pragma unroll
-                for (int e = 0; e < EPL; ++e) {
-                    if (e * NT >= ns) break;
-                    if (e * NT + tid < ns) st[e] = (uint32_t)start[BK(e)], s_hi[e] = (uint32_t)start[BK(e) + 1];
                 }
             }
             // levels 2 and 3: the counters are the same words, scanned by the same code.  A (sub-)bucket of k members is cut into FINE * k
@@ -832,13 +853,10 @@ __global__ __launch_bounds__(NT, K32 ? (KR ? 6 : 5) : (KR ? 5 : (NT == 128 ? 7 :
                         if (e * NT >= ns) break;
                         if (e * NT + tid < ns) {
                             const uint32_t ido = (uint32_t)(el[e] >> 32) - (uint32_t)mn, b1 = ido >> bshift;       // (not BK(e): the cold path keeps no register for it)
-                            const uint32_t lo1 = (uint32_t)start[b1], kb = ((uint32_t)start[b1 + 1] - lo1) * FINE;
-                            const uint32_t off = ido - (b1 << bshift);                                             // < 2^bshift
-                            const uint32_t idx = lo1 * FINE + (bshift ? __umulhi(off << (32 - bshift), kb) : 0u);  // + floor(off * kb / 2^bshift) < kb
-                            const uint32_t sh = (idx & 1u) * 16u;
-                            const uint32_t arrived = (atomicAdd(&cnt2[idx >> 1], 1u << sh) >> sh) & 0xFFFFu;
-                            if (PACK) st[e] = idx | (arrived << 20);
-                            else st[e] = idx, s_pos[e] = arrived;
+                            const RowsPart p = rows_part(start, ido, b1, bshift, FINE);
+                            const uint32_t idx = p.lo1 * FINE + p.sub;
+                            const uint32_t arrived = rows_count16(cnt2, idx);
+                            st[e] = idx | (arrived << 20);
                         }
                     }
                 } else {
@@ -847,18 +865,14 @@ __global__ __launch_bounds__(NT, K32 ? (KR ? 6 : 5) : (KR ? 5 : (NT == 128 ? 7 :
                         if (e * NT >= ns) break;
                         if (e * NT + tid < ns) {
                             const uint32_t ido = (uint32_t)(el[e] >> 32) - (uint32_t)mn, b1 = ido >> bshift;
-                            const uint32_t lo1 = (uint32_t)start[b1], kb = ((uint32_t)start[b1 + 1] - lo1) * FINE;
-                            const uint32_t off = ido - (b1 << bshift);
-                            const uint32_t sub = bshift ? __umulhi(off << (32 - bshift), kb) : 0u;
+                            const RowsPart p = rows_part(start, ido, b1, bshift, FINE);
                             // off * kb / 2^bshift - sub: where inside its level-2 sub-bucket's id window the member lies, [0, 1)
-                            const float fr = (float)off * __builtin_ldexpf((float)kb, -bshift) - (float)sub;
+                            const float fr = (float)p.off * __builtin_ldexpf((float)p.kb, -bshift) - (float)p.sub;
                             const uint32_t lo2 = LO(e);
                             const int k2 = ((int)HI(e) - (int)lo2) * (int)FINE;
                             const uint32_t idx = lo2 * FINE + (uint32_t)min(max((int)(fr * (float)k2), 0), k2 - 1);
-                            const uint32_t sh = (idx & 1u) * 16u;
-                            const uint32_t arrived = (atomicAdd(&cnt2[idx >> 1], 1u << sh) >> sh) & 0xFFFFu;
-                            if (PACK) st[e] = idx | (arrived << 20);
-                            else st[e] = idx, s_pos[e] = arrived;
+                            const uint32_t arrived = rows_count16(cnt2, idx);
+                            st[e] = idx | (arrived << 20);
                         }
                     }
                 }
@@ -870,8 +884,7 @@ __global__ __launch_bounds__(NT, K32 ? (KR ? 6 : 5) : (KR ? 5 : (NT == 128 ? 7 :
                     if (e * NT >= ns) break;
                     if (e * NT + tid < ns) {
                         const uint32_t idx = LO(e);
-                        if (PACK) st[e] = (st[e] & 0x3FF00000u) | (uint32_t)off2[idx] | ((uint32_t)off2[idx + 1] << 10);
-                        else st[e] = (uint32_t)off2[idx], s_hi[e] = (uint32_t)off2[idx + 1];
+                        st[e] = (st[e] & 0x3FF00000u) | (uint32_t)off2[idx] | ((uint32_t)off2[idx + 1] << 10);
                     }
                 }
             }
@@ -949,34 +962,7 @@ __global__ __launch_bounds__(NT, K32 ? (KR ? 6 : 5) : (KR ? 5 : (NT == 128 ? 7 :
     int32_t idv[SPL];
     uint32_t mtag[SPL];
     CntT mkey[SPL];
-    if (SPL % 4 == 0) {
-#pragma unroll
-        for (int c = 0; c < SPL / 4; ++c) {
-            const int g = c * NT + tid;
-            const int4 kk = ((const int4 *)keys)[g];
-            const uint4 qq = ((const uint4 *)minq)[g];
-            idv[4 * c] = kk.x, idv[4 * c + 1] = kk.y, idv[4 * c + (SPL > 2 ? 2 : 0)] = kk.z, idv[4 * c + (SPL > 2 ? 3 : 1)] = kk.w;
-            mtag[4 * c] = qq.x, mtag[4 * c + 1] = qq.y, mtag[4 * c + (SPL > 2 ? 2 : 0)] = qq.z, mtag[4 * c + (SPL > 2 ? 3 : 1)] = qq.w;
-            if (K32) {
-                const uint4 v = ((const uint4 *)pk)[g];
-                mkey[4 * c] = (CntT)v.x, mkey[4 * c + 1] = (CntT)v.y, mkey[4 * c + (SPL > 2 ? 2 : 0)] = (CntT)v.z, mkey[4 * c + (SPL > 2 ? 3 : 1)] = (CntT)v.w;
-            } else {
-                const uint4 v0 = ((const uint4 *)pk)[2 * g], v1 = ((const uint4 *)pk)[2 * g + 1];
-                mkey[4 * c] = (CntT)(((unsigned long long)v0.y << 32) | v0.x);
-                mkey[4 * c + 1] = (CntT)(((unsigned long long)v0.w << 32) | v0.z);
-                mkey[4 * c + (SPL > 2 ? 2 : 0)] = (CntT)(((unsigned long long)v1.y << 32) | v1.x);
-                mkey[4 * c + (SPL > 2 ? 3 : 1)] = (CntT)(((unsigned long long)v1.w << 32) | v1.z);
-            }
-        }
-    } else {
-        const int2 kk = ((const int2 *)keys)[tid];
-        const uint2 qq = ((const uint2 *)minq)[tid];
-        const uint4 v = ((const uint4 *)pk)[tid];
-        idv[0] = kk.x, idv[1] = kk.y;
-        mtag[0] = qq.x, mtag[1] = qq.y;
-        mkey[0] = (CntT)(((unsigned long long)v.y << 32) | v.x);
-        mkey[1] = (CntT)(((unsigned long long)v.w << 32) | v.z);
-    }
+    rows_fetch_slots<SPL, NT, K32, true>(keys, minq, pk, tid, idv, mtag, mkey);
     bool ok[SPL];
     uint32_t mf[SPL];
     int32_t slv[SPL];
@@ -1050,12 +1036,8 @@ __global__ __launch_bounds__(NT, K32 ? (KR ? 6 : 5) : (KR ? 5 : (NT == 128 ? 7 :
     // the bucket counts / offsets [B+1] (B <= min(T/4, NT)) over the ids -- K32: over the visit numbers
     unsigned long long *A = (unsigned long long *)lds_raw;
     int32_t *start = K32 ? (int32_t *)minq : keys;
-    int logb = 0;
-    while ((1 << logb) < ns && (2 << logb) <= T / 4 && (2 << logb) <= NT) ++logb;
-    const int B = 1 << logb;
-    const uint32_t range = (uint32_t)(mx - mn) + 1u;
-    const int Ls = (range <= 1u) ? 0 : (32 - __builtin_clz(range - 1u));
-    const int bshift = Ls > logb ? Ls - logb : 0;      // (id - mn) < 2^Ls, and ns <= range => logb <= Ls
+    int B, bshift;
+    rows_bucket_geometry<T, NT>(ns, mn, mx, B, bshift);
     if (tid <= B) start[tid] = 0;
     if (tid < kSpgFold)    // flush the fold table to HBM (latency overlaps the sort)
         if (fk[tid] != kNoKey) fs[tid] = uniq_global_insert(a.table, (unsigned long long)fk[tid], tag0 + ft[tid], a.flags);
@@ -1074,6 +1056,7 @@ __global__ __launch_bounds__(NT, K32 ? (KR ? 6 : 5) : (KR ? 5 : (NT == 128 ? 7 :
     SG_HOOK_RSTAMP(5);
     int32_t maxc;
     {   // exclusive scan over the B <= 256 buckets, one bucket per lane: wave scan, then the wave totals through LDS
+        // (rows_level1_scan, written out: called here, the table form's kernels came out as different instructions)
         const int32_t c = tid < B ? start[tid] : 0;
         const int32_t inc = wave_scan_add_i32_incl(c);     // inclusive scan over the wave
         const int32_t mc = wave_red_max_i32(c);
@@ -1112,12 +1095,9 @@ __global__ __launch_bounds__(NT, K32 ? (KR ? 6 : 5) : (KR ? 5 : (NT == 128 ? 7 :
 #pragma unroll
         for (int u = 0; u < SPL; ++u) {      // (bk[u] becomes the member's sub-bucket: the level-1 bucket is not needed again)
             if (!ok[u]) continue;
-            const uint32_t lo1 = (uint32_t)start[bk[u]], kb = (uint32_t)start[bk[u] + 1] - lo1;
-            const uint32_t off = (uint32_t)(idv[u] - mn) - (bk[u] << bshift);                      // < 2^bshift
-            const uint32_t sub = bshift ? __umulhi(off << (32 - bshift), kb) : 0u;                 // floor(off * kb / 2^bshift) < kb
-            bk[u] = lo1 + sub;
-            const uint32_t sh = (bk[u] & 1u) * 16u;
-            arr[u] = (int32_t)((atomicAdd(&cnt2[bk[u] >> 1], 1u << sh) >> sh) & 0xFFFFu);
+            const RowsPart p = rows_part(start, (uint32_t)(idv[u] - mn), bk[u], bshift, 1u);
+            bk[u] = p.lo1 + p.sub;
+            arr[u] = (int32_t)rows_count16(cnt2, bk[u]);
         }
         __syncthreads();
         {   // exclusive scan of the ns + 1 level-2 counters, in place (offsets <= ns < 2^16): CW consecutive words per lane
@@ -1173,6 +1153,8 @@ __global__ __launch_bounds__(NT, K32 ? (KR ? 6 : 5) : (KR ? 5 : (NT == 128 ? 7 :
         if (ok[u]) {
             const int lo = blo[u], hi = bhi[u];
             int rank = 0;       // ids are distinct within a set: the high word of A decides
+            // (the one-wave key rows' ranking loop once more: as one function called from both, the table form's kernels came out as
+            //  different instructions)
 #pragma unroll 1         // a bucket holds one to a handful of members: an unrolled loop is all prologue
             for (int t2 = lo; t2 < hi; ++t2) rank += (Ahi[2 * t2 + 1] < (uint32_t)idv[u]) ? 1 : 0;
             if (staged) {
@@ -1192,6 +1174,101 @@ __global__ __launch_bounds__(NT, K32 ? (KR ? 6 : 5) : (KR ? 5 : (NT == 128 ? 7 :
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------- the launcher
+// Dev builds: -DSG_DEV_ROWS_NT=128 keeps two waves for the 2-hop key rows of a 512-slot table, =64 takes one wave with int64
+// offsets too.  (=256, one walk per lane over a 512-slot table with two slots per lane, lost its A/B in round 3 and is gone.)
+#ifndef SG_DEV_ROWS_NT
+#define SG_DEV_ROWS_NT 0
+#endif
+// (SG_ROWS_KR_LDS_MIN, dev builds: LDS asked for per two-wave workgroup at least -- 160 KB / n roots per CU; A/B of 12 / 14 / 16 roots)
+#ifndef SG_ROWS_KR_LDS_MIN
+#define SG_ROWS_KR_LDS_MIN 0
+#endif
+
+struct RowsLaunch {
+    const WalkArgs &a;
+    int64_t grid;
+    size_t lds;         // what launch_walk sized for the table forms with 64-bit counts
+    hipStream_t s;
+    bool rec;           // hop records of the form that goes with the row offsets: one dependent read per hop
+};
+
+// one launch: with hop records (16 bytes with int64 row offsets, 8 with int32) or over plain CSR
+template <bool I64, int RNG, int MH, int SPL, int NT, bool K32, bool KR, int EPLP>
+static int rows_launch(const RowsLaunch &l, size_t lds) {
+    if (l.rec) hipLaunchKernelGGL((walk_rows_kernel<I64, RNG, MH, SPL, NT, I64 ? 16 : 8, K32, KR, EPLP>), dim3((unsigned)l.grid), dim3(NT), lds, l.s, l.a);
+    else hipLaunchKernelGGL((walk_rows_kernel<I64, RNG, MH, SPL, NT, 0, K32, KR, EPLP>), dim3((unsigned)l.grid), dim3(NT), lds, l.s, l.a);
+    return 1;
+}
+
+// The forms, each with its admission test and its LDS size.  Every `if constexpr` stands for a form that no shape with these
+// row offsets and this hop count reaches (tests/walk_rows_edges.py: REACHABLE): it is not instantiated, and the launch declines.
+//
+//   rows          counts  slots   lanes x slots per lane        hops   row offsets   members per lane (EPLP)
+//   64-bit keys   64-bit  1,024   128 x 8                       4      both          7
+//   32-bit keys   32-bit  1,024   128 x 8                       2-4    both          5; at 3 hops above 640 members: 8
+//   32-bit keys   32-bit    512   64 x 8 (one wave per root)    2      int32         7
+//   32-bit keys   32-bit    512   128 x 4                       2-4    both (2 hops: int64)   4
+//   table         32-bit  1,024   128 x 8                       2-3    int32
+//   table         64-bit  1,024   256 x 4                       2-4    int64; int32 at 4 hops
+//   table         64-bit    512   128 x 4                       2-4    both
+template <bool I64, int RNG, int MH>
+static int rows_form(const RowsLaunch &l) {
+    const WalkArgs &a = l.a;
+    const int bits = a.m * a.shift + 1;
+    if (a.keyrows && bits > 31) {
+        // 64-bit key rows (round 4): the 4-hop shapes whose keys need 33+ bits (M = 128 .. 204: 4 x 8 + 1) -- 64-bit counts in the
+        // walk tables, the keys leave through set_keys.  1,024-slot table, 128 lanes x 2 walks x 8 slots, ~15 KB of LDS per root.
+        // Seven members per lane in the sort: a 1,024-slot table never holds more than 7 * 128 (its strides end at 817).
+        if constexpr (MH == 4) {
+            if (bits > 63 || a.T != 1024 || !a.set_keys || ((int64_t)a.stride + 2) / 2 + 1 > 4 * 128 || a.stride > 7 * 128) return 0;
+            return rows_launch<I64, RNG, 4, 8, 128, false, true, 7>(l, kr_red_offset(1024, a.M, a.stride, 128, true) + 64 + 16);
+        }
+        return 0;
+    }
+    if (a.keyrows) {      // rows that carry the LP key itself: 32-bit counts, 2 to 4 hops -- or not at all
+        // (the epilogue's sort lives over the dead walk tables AND the Fisher-Yates draws behind them: packed members 8*stride,
+        //  level-1 offsets 4*(128+1) [start + NT + 1: NT <= 128], level-2 counters 2 bytes each; CW * NT words cover them)
+        if (((int64_t)a.stride + 2) / 2 + 1 > 4 * (a.T == 512 ? 64 : 128)) return 0;
+        // key rows, 512-slot table, 2 hops, int32 row offsets: ONE wave per root (64 lanes x 4 walks x 8 slots, 55 VGPRs) -- no
+        // barrier is a real one, the per-wave prologue and the scans are paid once: collab walk 0.296 -> 0.262 ms; neutral with
+        // int64 offsets (twitter), and 13 % slower for the 1,024-slot table (16 slots per lane: 95 VGPRs), so only here.
+        constexpr bool one_wave = MH == 2 && (SG_DEV_ROWS_NT == 64 || (!I64 && SG_DEV_ROWS_NT != 128));
+        // (the reduction words sit behind the walk tables and behind the epilogue's sort, whichever reaches further: kr_red_offset)
+        size_t ldsk = kr_red_offset(a.T, a.M, a.stride, one_wave && a.T == 512 ? 64 : 128, false) + 64 + 16;
+        if (!(one_wave && a.T == 512) && ldsk < (size_t)SG_ROWS_KR_LDS_MIN) ldsk = SG_ROWS_KR_LDS_MIN;
+        if (a.T == 1024) {
+            // five members per lane in the sort up to 640 members; only the 3-hop strides go further (2 hops: 513, 4 hops: 509)
+            if (a.stride <= 5 * 128) return rows_launch<I64, RNG, MH, 8, 128, true, true, 5>(l, ldsk);
+            if constexpr (MH == 3) return rows_launch<I64, RNG, 3, 8, 128, true, true, 0>(l, ldsk);
+            return 0;
+        }
+        if constexpr (one_wave) return rows_launch<I64, RNG, 2, 8, 64, true, true, 0>(l, ldsk);
+        else return rows_launch<I64, RNG, MH, 4, 128, true, true, 0>(l, ldsk);
+    }
+    if (a.T == 1024) {
+        // counts that fit 32 bits: 128 lanes x 8 slots, 12 bytes of LDS per slot -> 11 roots per CU.  int32 row offsets +
+        // 8-byte records / plain CSR only, 2 and 3 hops (M <= 256: at most 3 x 9 + 1 = 28 bits)
+        if constexpr (!I64 && MH <= 3) {
+            if (bits > 31) return 0;
+            return rows_launch<false, RNG, MH, 8, 128, true, false, 0>(l, (size_t)a.T * 12 + (size_t)a.M * 4 + 8 + (size_t)kSpgFold * 12 + 64 + 16);
+        } else {
+            return rows_launch<I64, RNG, MH, 4, 256, false, false, 0>(l, l.lds);
+        }
+    }
+    return rows_launch<I64, RNG, MH, 4, 128, false, false, 0>(l, l.lds);      // 512-slot table: 128 lanes x 2 walks
+}
+
+template <bool I64, int RNG>
+static int rows_hops(const RowsLaunch &l) {
+    switch (l.a.m) {
+        case 2: return rows_form<I64, RNG, 2>(l);
+        case 3: return rows_form<I64, RNG, 3>(l);
+        case 4: return rows_form<I64, RNG, 4>(l);
+    }
+    return 0;
+}
+
 // returns 1 when this specialised form took the launch (else the caller launches walk_sets_kernel<SPG>)
 int launch_walk_rows(const WalkArgs &a, bool indptr64, int rng_mode, size_t lds, hipStream_t s) {
 #ifdef SG_DEV_NO_WALK_ROWS      // dev builds only: every shape through walk_sets_kernel<SPG> (A/B)
@@ -1201,155 +1278,10 @@ int launch_walk_rows(const WalkArgs &a, bool indptr64, int rng_mode, size_t lds,
     if (a.m < 2 || a.m > 4 || (a.T != 512 && a.T != 1024)) return 0;
     const int64_t grid = xcd_grid(a.worklist && a.work_cap > 0 && a.work_cap < a.n ? a.work_cap : a.n);
     if (grid >= (1ll << 31)) return 0;
+    const RowsLaunch l{a, grid, lds, s, a.recs != nullptr && indptr64 == (a.rec.id_bits == 0)};
     const bool rr = rng_mode == SUBGACC_RNG_RAND_R;
-    // 512-slot tables: 128 lanes x 2 walks (dev builds: -DSG_DEV_ROWS_NT=256 forces one walk per lane)
-#ifndef SG_DEV_ROWS_NT
-#define SG_DEV_ROWS_NT 0
-#endif
-    constexpr bool nt256 = SG_DEV_ROWS_NT == 256;
-    // key rows, 512-slot table, 2 hops, int32 row offsets: ONE wave per root (64 lanes x 4 walks x 8 slots, 55 VGPRs) -- no
-    // barrier is a real one, the per-wave prologue and the scans are paid once: collab walk 0.296 -> 0.262 ms; neutral with
-    // int64 offsets (twitter), and 13 % slower for the 1,024-slot table (16 slots per lane: 95 VGPRs), so only here.
-    // (dev builds: -DSG_DEV_ROWS_NT=128 keeps two waves, =64 takes one wave with int64 offsets too)
-    constexpr bool nt64 = SG_DEV_ROWS_NT == 64;
-    constexpr bool nt128 = SG_DEV_ROWS_NT == 128;
-    const bool half = a.T == 512 && !nt256;
-    const bool rec = a.recs != nullptr && indptr64 == (a.rec.id_bits == 0);   // hop records: one dependent read per hop
-    if (a.keyrows && a.m * a.shift + 1 > 31) {
-        // 64-bit key rows (round 4): the 4-hop shapes whose keys need 33+ bits (M = 128 .. 204: 4 x 8 + 1) -- 64-bit counts in the
-        // walk tables, the keys leave through set_keys.  1,024-slot table, 128 lanes x 2 walks x 8 slots, ~15 KB of LDS per root.
-        if (a.m != 4 || a.m * a.shift + 1 > 63 || a.T != 1024 || !a.set_keys || ((int64_t)a.stride + 2) / 2 + 1 > 4 * 128) return 0;
-        const size_t lds64 = kr_red_offset(1024, a.M, a.stride, 128, true) + 64 + 16;
-#define SG_KR64W_E(I64, RNGM, EP)                                                                                     \
-    do {                                                                                                             \
-        if (rec)                                                                                                     \
-            hipLaunchKernelGGL((walk_rows_kernel<I64, RNGM, 4, 8, 128, I64 ? 16 : 8, false, true, EP>), dim3((unsigned)grid), dim3(128), lds64, s, a); \
-        else                                                                                                         \
-            hipLaunchKernelGGL((walk_rows_kernel<I64, RNGM, 4, 8, 128, 0, false, true, EP>), dim3((unsigned)grid), dim3(128), lds64, s, a); \
-        return 1;                                                                                                    \
-    } while (0)
-#define SG_KR64W(I64, RNGM)                                  \
-    do {                                                     \
-        if (a.stride <= 7 * 128) SG_KR64W_E(I64, RNGM, 7);   \
-        SG_KR64W_E(I64, RNGM, 0);                            \
-    } while (0)
-        if (indptr64) {
-            if (rr) SG_KR64W(true, SUBGACC_RNG_RAND_R);
-            SG_KR64W(true, SUBGACC_RNG_PHILOX);
-        }
-        if (rr) SG_KR64W(false, SUBGACC_RNG_RAND_R);
-        SG_KR64W(false, SUBGACC_RNG_PHILOX);
-#undef SG_KR64W
-#undef SG_KR64W_E
-    }
-    if (a.keyrows) {      // rows that carry the LP key itself: 32-bit counts, 128 lanes, 2 to 4 hops -- or not at all
-        // (the epilogue's sort lives over the dead walk tables AND the Fisher-Yates draws behind them: packed members 8*stride,
-        //  level-1 offsets 4*(128+1) [start + NT + 1: NT <= 128], level-2 counters 2 bytes each; CW * NT words cover them)
-        if (a.m * a.shift + 1 > 31 || a.m > 4 || ((int64_t)a.stride + 2) / 2 + 1 > 4 * (a.T == 512 ? 64 : 128)) return 0;
-        // (the reduction words sit behind the walk tables and behind the epilogue's sort, whichever reaches further: kr_red_offset)
-        const bool one_wave = (nt64 || (!indptr64 && !nt128)) && a.m == 2 && a.T == 512;
-        // (SG_ROWS_KR_LDS_MIN, dev builds: LDS asked for per two-wave workgroup at least -- 160 KB / n roots per CU; A/B of 12 / 14 / 16 roots)
-#ifndef SG_ROWS_KR_LDS_MIN
-#define SG_ROWS_KR_LDS_MIN 0
-#endif
-        size_t ldsk = kr_red_offset(a.T, a.M, a.stride, one_wave ? 64 : 128, false) + 64 + 16;
-        if (!one_wave && ldsk < (size_t)SG_ROWS_KR_LDS_MIN) ldsk = SG_ROWS_KR_LDS_MIN;
-#define SG_KR_E(I64, RNGM, MHH, SPLL, EP)                                                                            \
-    do {                                                                                                             \
-        if (rec)                                                                                                     \
-            hipLaunchKernelGGL((walk_rows_kernel<I64, RNGM, MHH, SPLL, 128, I64 ? 16 : 8, true, true, EP>), dim3((unsigned)grid), dim3(128), ldsk, s, a); \
-        else                                                                                                         \
-            hipLaunchKernelGGL((walk_rows_kernel<I64, RNGM, MHH, SPLL, 128, 0, true, true, EP>), dim3((unsigned)grid), dim3(128), ldsk, s, a); \
-        return 1;                                                                                                    \
-    } while (0)
-#define SG_KR(I64, RNGM, MHH, SPLL) SG_KR_E(I64, RNGM, MHH, SPLL, 0)
-#define SG_KR8(I64, RNGM, MHH)                                           \
-    do {                                                                 \
-        if (a.stride <= 5 * 128) SG_KR_E(I64, RNGM, MHH, 8, 5);          \
-        SG_KR_E(I64, RNGM, MHH, 8, 0);                                   \
-    } while (0)
-#define SG_KR64(I64, RNGM, MHH, SPLL)                                                                                \
-    do {                                                                                                             \
-        if (rec)                                                                                                     \
-            hipLaunchKernelGGL((walk_rows_kernel<I64, RNGM, MHH, SPLL, 64, I64 ? 16 : 8, true, true>), dim3((unsigned)grid), dim3(64), ldsk, s, a); \
-        else                                                                                                         \
-            hipLaunchKernelGGL((walk_rows_kernel<I64, RNGM, MHH, SPLL, 64, 0, true, true>), dim3((unsigned)grid), dim3(64), ldsk, s, a); \
-        return 1;                                                                                                    \
-    } while (0)
-#define SG_KR_MH(I64, RNGM)                                  \
-    do {                                                     \
-        if (a.T == 1024) {                                   \
-            if (a.m == 2) SG_KR8(I64, RNGM, 2);              \
-            if (a.m == 3) SG_KR8(I64, RNGM, 3);              \
-            SG_KR8(I64, RNGM, 4);                            \
-        }                                                    \
-        if ((nt64 || (!I64 && !nt128)) && a.m == 2) SG_KR64(I64, RNGM, 2, 8); \
-        if (a.m == 2) SG_KR(I64, RNGM, 2, 4);                \
-        if (a.m == 3) SG_KR(I64, RNGM, 3, 4);                \
-        SG_KR(I64, RNGM, 4, 4);                              \
-    } while (0)
-        if (indptr64) {
-            if (rr) SG_KR_MH(true, SUBGACC_RNG_RAND_R);
-            SG_KR_MH(true, SUBGACC_RNG_PHILOX);
-        }
-        if (rr) SG_KR_MH(false, SUBGACC_RNG_RAND_R);
-        SG_KR_MH(false, SUBGACC_RNG_PHILOX);
-#undef SG_KR_MH
-#undef SG_KR64
-#undef SG_KR
-#undef SG_KR8
-#undef SG_KR_E
-    }
-    // 1,024-slot table with counts that fit 32 bits: 128 lanes x 8 slots, 12 bytes of LDS per slot -> 11 roots per CU
-    // (dev builds: -DSG_DEV_ROWS_NT=256 keeps the 256-lane form).  int32 row offsets + 8-byte records / plain CSR only.
-    if (a.T == 1024 && !nt256 && !indptr64 && a.m * a.shift + 1 <= 31 && a.m <= 3) {
-        const size_t lds32 = (size_t)a.T * 12 + (size_t)a.M * 4 + 8 + (size_t)kSpgFold * 12 + 64 + 16;
-#define SG_ROWS32(RNGM, MHH)                                                                                        \
-    do {                                                                                                            \
-        if (rec)                                                                                                    \
-            hipLaunchKernelGGL((walk_rows_kernel<false, RNGM, MHH, 8, 128, 8, true>), dim3((unsigned)grid), dim3(128), lds32, s, a); \
-        else                                                                                                        \
-            hipLaunchKernelGGL((walk_rows_kernel<false, RNGM, MHH, 8, 128, 0, true>), dim3((unsigned)grid), dim3(128), lds32, s, a); \
-        return 1;                                                                                                   \
-    } while (0)
-        if (rr) {
-            if (a.m == 2) SG_ROWS32(SUBGACC_RNG_RAND_R, 2);
-            SG_ROWS32(SUBGACC_RNG_RAND_R, 3);
-        }
-        if (a.m == 2) SG_ROWS32(SUBGACC_RNG_PHILOX, 2);
-        SG_ROWS32(SUBGACC_RNG_PHILOX, 3);
-#undef SG_ROWS32
-    }
-#define SG_ROWS(I64, RNGM, MHH, SPLL, NTT)                                                                         \
-    do {                                                                                                           \
-        if (rec)                                                                                                   \
-            hipLaunchKernelGGL((walk_rows_kernel<I64, RNGM, MHH, SPLL, NTT, I64 ? 16 : 8>), dim3((unsigned)grid), dim3(NTT), lds, s, a); \
-        else                                                                                                       \
-            hipLaunchKernelGGL((walk_rows_kernel<I64, RNGM, MHH, SPLL, NTT>), dim3((unsigned)grid), dim3(NTT), lds, s, a); \
-        return 1;                                                                                                  \
-    } while (0)
-#define SG_ROWS_MH(I64, RNGM, SPLL, NTT)                      \
-    do {                                                      \
-        if (a.m == 2) SG_ROWS(I64, RNGM, 2, SPLL, NTT);       \
-        if (a.m == 3) SG_ROWS(I64, RNGM, 3, SPLL, NTT);       \
-        SG_ROWS(I64, RNGM, 4, SPLL, NTT);                     \
-    } while (0)
-#define SG_ROWS_SPL(I64, RNGM)                                \
-    do {                                                      \
-        if (a.T == 1024) SG_ROWS_MH(I64, RNGM, 4, 256);       \
-        if (half) SG_ROWS_MH(I64, RNGM, 4, 128);              \
-        SG_ROWS_MH(I64, RNGM, 2, 256);                        \
-    } while (0)
-    if (indptr64) {
-        if (rr) SG_ROWS_SPL(true, SUBGACC_RNG_RAND_R);
-        SG_ROWS_SPL(true, SUBGACC_RNG_PHILOX);
-    }
-    if (rr) SG_ROWS_SPL(false, SUBGACC_RNG_RAND_R);
-    SG_ROWS_SPL(false, SUBGACC_RNG_PHILOX);
-#undef SG_ROWS_SPL
-#undef SG_ROWS_MH
-#undef SG_ROWS
-    return 0;
+    if (indptr64) return rr ? rows_hops<true, SUBGACC_RNG_RAND_R>(l) : rows_hops<true, SUBGACC_RNG_PHILOX>(l);
+    return rr ? rows_hops<false, SUBGACC_RNG_RAND_R>(l) : rows_hops<false, SUBGACC_RNG_PHILOX>(l);
 }
 
 }  // namespace subgacc

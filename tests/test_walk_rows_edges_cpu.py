@@ -110,8 +110,9 @@ def test_the_gpu_launches_cover_every_reachable_instantiation():
     launched = _all_launches()
     assert {(i, t) for i, _, t in launched} == W.REACHABLE
     assert launched == {(i, r, t) for i, t in W.REACHABLE for r in ("rand_r", "philox")}
-    # arms of the source no shape reaches: EPLP = 0 of the 64-bit key rows and of the 2- and 4-hop 32-bit key rows
-    # at 1,024 slots, two slots per lane x 256 lanes, 64-bit counts at 1,024 slots for 2 and 3 hops over int32 offsets
+    # forms the source no longer has because no shape reaches them: EPLP = 0 of the 64-bit key rows and of the 2- and
+    # 4-hop 32-bit key rows at 1,024 slots, two slots per lane x 256 lanes, 64-bit counts at 1,024 slots for 2 and 3 hops over int32
+    # offsets -- an invariant of the launcher now (rows_form declines them), not only of the shapes
     assert not any(t[:3] == (4, 8, 128) and t[5] and not t[4] and t[6] == 0 for _, t in brute)
     assert not any(t[1] == 2 for _, t in brute)
     assert all(max(M * 4 + 1 for M in range(128, 205)) <= 7 * 128 for _ in (0,))

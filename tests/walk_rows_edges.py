@@ -111,8 +111,9 @@ def outcome(M, m, form, idx64=False, records=False, bucket=-1):
 
 
 def _reachable():
-    """every (idx64, instantiation) launch_walk_rows can reach in a product build, written out: the arms of its macros crossed with
-    the shapes that can stand in front of them (see DESIGN.md 4.1 for the arms that no shape reaches)"""
+    """every (idx64, instantiation) launch_walk_rows can reach in a product build, written out: the forms of rows_form crossed with
+    the shapes that can stand in front of them.  These are also all the instantiations a product build of walk_rows.hip holds: the
+    launcher no longer names a form that no shape reaches"""
     out = set()
     for idx64 in (False, True):
         recs = (0, 16) if idx64 else (0, 8)
