@@ -86,8 +86,7 @@ __global__ __launch_bounds__(NT, NT == 256 ? 8 : SG_PIPE_MINW) __attribute__((am
         const bool bad = (uint64_t)(int64_t)rootB >= (uint64_t)a.num_nodes;
         int64_t d64;
         load_row<IDX64>(a.indptr, bad ? 0 : rootB, rbegB, d64);
-        if (bad) d64 = 0;                              // handled like an isolated root ...
-        sawBad |= bad;                                 // ... and flagged once, after the loop (no atomic inside it)
+        if (bad) d64 = 0;                              // walks nothing, like an isolated root: its turn as A tells the two apart
         if (a.cap_root && d64 > kNeighCap) d64 = kNeighCap;
         rdegB = (uint32_t)d64;
         if (RNG == SUBGACC_RNG_RAND_R) {
@@ -233,12 +232,21 @@ __global__ __launch_bounds__(NT, NT == 256 ? 8 : SG_PIPE_MINW) __attribute__((am
         SG_BSTEP(1);
 
         if (isolated) {   // one member, every count = M (subg_acc.c:753-761); id = the root
+            // ... or a root outside the graph (degree forced to 0 above): an empty set, nsize = 0 and nothing else (include/subgacc.h),
+            // flagged once, after the loop (no atomic inside it); SUBGACC_NO_ROOT is a row without a root, not an error.  Told apart
+            // here, in the rare branch, from the root id A holds anyway: load_root carries nothing for it
+            const bool badA = (uint64_t)(int64_t)root >= (uint64_t)a.num_nodes;
+            sawBad |= badA && root != SUBGACC_NO_ROOT;
             if (tid == 0) {
-                unsigned long long k = lead;
-                for (int s = 0; s < MH; ++s) k |= (unsigned long long)M << (s * a.shift);
-                a.set_ids[obase] = root;
-                a.set_keys[obase] = k;
-                a.nsize[i] = 1;
+                if (badA) {
+                    a.nsize[i] = 0;               // never looked up: nothing of its row is written
+                } else {
+                    unsigned long long k = lead;
+                    for (int s = 0; s < MH; ++s) k |= (unsigned long long)M << (s * a.shift);
+                    a.set_ids[obase] = root;
+                    a.set_keys[obase] = k;
+                    a.nsize[i] = 1;
+                }
             }
             SG_BSTEP(2); SG_BSTEP(3); SG_BSTEP(4); SG_BSTEP(5); SG_BSTEP(6);
             SG_BSTEP(7); SG_BSTEP(8); SG_BSTEP(9); SG_BSTEP(10); SG_BSTEP(11);
