@@ -734,7 +734,20 @@ int subgacc_walk_spg_sparse(const subgacc_walk_cfg *cfg, const void *indptr, con
  *      (n_dev, optional: only the first min(n, *n_dev) entries).
  * Shapes: what the key-rows form of subgacc_walk_spg serves (num_steps*SHIFT+1 <= 31, 2 to 4 hops, M <= 256, no bucket).
  * rng_pos / rng_seed as for subgacc_walk_spg (RAND_R: positions of ALL n roots of the chunk; row i reads entry i).
- * cand: subgacc_keyrows_cand_capacity(n) entries (cand_cap says how many there are; every row is listed at most once). */
+ * cand: subgacc_keyrows_cand_capacity(n) entries (cand_cap says how many there are; every row is listed at most once).
+ * Limits (tests/test_gpu_keyrows_edges.py pins each of them):
+ *   - the 32-bit pattern 0xFFFFFFFF marks a free entry of the pass's dictionary and is NOT a key (the shapes above keep bit 31
+ *     clear); any other pattern is a key, zero-extended to 64 bits in `uniq_table` and `ukeys` -- with bit 31 set it is a negative
+ *     int32 as row_keys entry and as the payload of the ukeys = NULL form;
+ *   - nsize[i] > stride is read as `stride`; row_off must be the prefix sum of those clamped lengths;
+ *   - cand lists a SUPERSET of the rows that show a key first, each row once, in arrival order: which other rows it lists, and the
+ *     order, differ from run to run; entries at and beyond *n_cand are not written.  The look-up form (ukeys != NULL) touches
+ *     neither cand nor *n_cand nor the table;
+ *   - the look-up form and subgacc_keyrows_translate read min(*n_ukeys, max_ukeys) entries of ukeys and ask `uniq_table` (numbered
+ *     by subgacc_uniq_number, which numbers every key whatever max_unique says) for any other key; a key that is in no table
+ *     gives the payload 0; subgacc_keyrows_translate leaves the entries at and beyond min(n, *n_dev) as they are;
+ *   - more distinct keys than `uniq_table` takes (see the limits of subgacc_uniq_insert): flags[2] |= 1, every call still returns
+ *     and writes its outputs only, and what was registered, numbered or copied meanwhile is void. */
 int64_t subgacc_keyrows_cand_capacity(int64_t n);
 int subgacc_keyrows_register(const int32_t *row_keys, const int32_t *nsize, int64_t n, int32_t stride,
                              int64_t root_base, void *uniq_table, int64_t uniq_capacity, int32_t *cand, int64_t cand_cap,
