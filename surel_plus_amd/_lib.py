@@ -1,5 +1,5 @@
-"""ctypes binding of libsubgacc_hip.so, derived from the declarations of include/subgacc.h (the C ABI) and of include/subgacc_half.h
-(the join's rows in a 16-bit type) when this module is imported: an entry point is declared there and defined under csrc/, and
+"""ctypes binding of libsubgacc_hip.so, derived from the declarations of include/subgacc.h (the C ABI), of include/subgacc_half.h
+(the join's rows in a 16-bit type) and of include/subgacc_small.h (key rows for the small walk shapes) when this module is imported: an entry point is declared there and defined under csrc/, and
 nothing here names it.
 
 There is no CPU fallback: if the library is missing, or no gfx950 device is visible when a compute entry
@@ -118,6 +118,11 @@ _HALF_TEXT = _header_text(HALF_HEADER)
 HALF_DECLS = parse_header(_HALF_TEXT)
 _TYPES.update(bind_types(HALF_DECLS))
 HALF_SYMBOLS = tuple(HALF_DECLS)
+# the third header: key rows for the small walk shapes (csrc/walk_small.hip), the same library
+SMALL_HEADER = os.path.join(os.path.dirname(HEADER), "subgacc_small.h")
+SMALL_DECLS = parse_header(_header_text(SMALL_HEADER))
+_TYPES.update(bind_types(SMALL_DECLS))
+SMALL_SYMBOLS = tuple(SMALL_DECLS)
 HALF_F16, HALF_BF16 = (int(re.search(rf"^#define\s+SUBGACC_HALF_{n}\s+(\d+)", _HALF_TEXT, re.M).group(1)) for n in ("F16", "BF16"))
 
 
@@ -129,7 +134,7 @@ VERBOSE = os.environ.get("SUBGACC_QUIET", "0") != "1"
 def build(force=False):
     """hipcc-compile csrc/*.hip for gfx950 into surel_plus_amd/libsubgacc_hip.so (in-tree)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))]
-    srcs += [HEADER, HALF_HEADER]
+    srcs += [HEADER, HALF_HEADER, SMALL_HEADER]
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
         subprocess.check_call(["make", "-s", "-C", CSRC, "-j4", "all"])

@@ -85,6 +85,14 @@ def key_rows_form(num_walks, num_steps):
     return 0
 
 
+def small_rows_form(num_walks, num_steps):
+    """does the one-wave key-row kernel (csrc/walk_small.hip: subgacc_walk_keyrows_small) take this shape?  1 to 4 hops and a set of at
+    most 204 members -- a per-root table of 64, 128 or 256 slots: m = 1 with M <= 203, m = 2 with M <= 101, m = 3 with M <= 67, m = 4
+    with M <= 50 (the reference's mag, DBLP-coauthor and vessel configurations).  The key has at most 25 bits.  Disjoint from
+    key_rows_form != 0, whose tables have 512 or 1,024 slots."""
+    return num_walks >= 1 and 1 <= num_steps <= 4 and _table_slots(num_walks, num_steps) <= 256
+
+
 def key_rows_ok(num_walks, num_steps):
     """32-bit key rows for this shape? (what the batched registration of a kept store, csrc/keyrows.hip, works on)"""
     return key_rows_form(num_walks, num_steps) == 32
@@ -236,6 +244,7 @@ class SampledSets:
     n_distinct: int = None       # StepBuffers(dedup_roots=True): so many rows (the first occurrences of the endpoints) hold sets
     keyrows: bool = False        # strided rows whose payload (`slot`) is the member's LP key: no table, no numbering
     key64: bool = False          # ... a 64-bit key (`slot` is int64: 4-hop walks with M >= 128), else 32 bits
+    small_rows: bool = False     # ... 32-bit keys of a small shape (small_rows_form: subgacc_walk_keyrows_small wrote them); numbered like key64
     _table_form: object = None   # key64: the same batch sampled again with the table form, once number() / to_csr() needed it
     _rows_are_members: bool = True   # False: the join emits some rows twice (triplets: w), so its row count is not the member count
     _fresh: object = None        # sets of a buffered step: () -> do the step buffers still hold THIS batch? (spjoin._buffered_step)
@@ -350,7 +359,7 @@ class SampledSets:
         if self.ukeys is not None:
             return self
         self.resolve()
-        if self.keyrows and self.key64:
+        if self.keyrows and (self.key64 or self.small_rows):      # (subgacc_walk_tags is the fused-row kernel's alone)
             self.ukeys = self.table_form().ukeys
             return self
         if self.keyrows:        # the keys are all there: register them now, and ask the few candidate roots for their order
@@ -369,7 +378,8 @@ class SampledSets:
         return self
 
     def table_form(self):
-        """64-bit key rows: csrc/keyrows.hip registers 32-bit keys, so what such a batch does not carry -- the numbering of its
+        """64-bit key rows, and the key rows of a small shape (only the fused-row kernel registers tags alone): csrc/keyrows.hip registers
+        32-bit keys of the fused-row kernel's shapes, so what such a batch does not carry -- the numbering of its
         distinct LP rows, enc, the packed CSR rows -- comes from sampling the batch AGAIN with the table form of the walk kernel
         (a set is a function of (seed, root) under Philox, of the root's place in the stream under rand_r: the same rows)."""
         if self._table_form is None:
@@ -619,9 +629,10 @@ def _rng_positions(L, cfg, csr, q, n, rng_streams, calls_before, st):
 def _walk(cfg, csr, roots, n, flags, st, form, ids=None, payload=None, nsize=None, walks=None, rng=(None, None), table=None,
           capacity=0, work=None, select=False, root_base=0, work_cap=0):
     """The subgacc_walk_* call of every walk (csrc/walk.hip).  form: "sets" (ids + LP keys in first-visit order, the raw walks with
-    cfg.emit_walks), "fused" (ids sorted + table slots, without a table 32-bit LP keys), "keys64" (ids sorted + 64-bit LP keys) or
+    cfg.emit_walks), "fused" (ids sorted + table slots, without a table 32-bit LP keys), "keys64" (ids sorted + 64-bit LP keys),
+    "keys_small" (ids sorted + 32-bit LP keys of a small shape, small_rows_form: csrc/walk_small.hip) or
     "tags" (no rows: the listed roots' LP keys go into `table` with their first-visit tags).  rng = (rng_pos, rng_seed) under rand_r;
-    work = (list, its length on the device): the rows to sample with select=True, "keys64" and "tags", else an order over all rows."""
+    work = (list, its length on the device): the rows to sample with select=True, "keys64", "keys_small" and "tags", else an order over all rows."""
     L, g = lib(), (cfg, ptr(csr.indptr), ptr(csr.indices), csr.num_nodes, ptr(roots), n)
     rp, rs, tab = ptr(rng[0]), ptr(rng[1]), (ptr(table), capacity)
     wl, nwl = (ptr(work[0]), ptr(work[1])) if work is not None else (None, None)
@@ -632,6 +643,8 @@ def _walk(cfg, csr, roots, n, flags, st, form, ids=None, payload=None, nsize=Non
         return check(L.subgacc_walk_tags(*g, root_base, rp, rs, wl, nwl, work_cap, *tab, *rows[3:]))
     if form == "keys64":
         return check(L.subgacc_walk_keyrows64(*g, rp, rs, wl, nwl, *rows))
+    if form == "keys_small":
+        return check(L.subgacc_walk_keyrows_small(*g, rp, rs, wl, nwl, *rows))
     if work is None:
         return check(L.subgacc_walk_spg(*g, root_base, rp, rs, *tab, *rows))
     if select:

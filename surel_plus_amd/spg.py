@@ -271,7 +271,8 @@ class StridedSpG:
         return self.sets.X
 
     def to_csr(self):
-        if self.keyrows and self.sets.key64:      # 64-bit key rows: the packed rows come from the table form of the same batch
+        # 64-bit key rows, and the key rows of a small shape: the packed rows come from the table form of the same batch
+        if self.keyrows and (self.sets.key64 or getattr(self.sets, "small_rows", False)):
             return StridedSpG(self.sets.table_form(), self.shape[1]).to_csr()
         self.sets.number()           # the packed rows carry SFptr+1: the table must be numbered by now (key rows: registered now)
         n, dev = self.n_rows, self.device

@@ -563,7 +563,9 @@ class StepBuffers:
     key rows (subgacc_sjoin_key_counts): no size pass, no scan, no row form.  Instead of `out` and `segid` the buffers hold `counts`
     float32 [S, table_rows], `sizes` int32 [S], `ukeys` int32 [table_rows - 1] and `feat` float32 [table_rows, m+1]; table_rows - 1 is
     the number of distinct LP rows a step may show (more: sets.resolve() raises and names table_rows).  Needs 32-bit key rows and one
-    batch per step (ValueError otherwise, before any device work).
+    batch per step (ValueError otherwise, before any device work).  A small shape (sampler.small_rows_form: 1 to 4 hops, M*m+1 <= 204)
+    has such rows for the stages alone: subgacc_walk_keyrows_small writes them (self.small), with root dedup, order= and triplets as
+    at the larger shapes; stage=None of such a shape stays the table form on the general kernel.
     stage="counts_attn": the step of sample_and_attn_counts / sample_and_attn_stage -- the same launches up to the columns, then the
     caller's gate g = gate(table) in torch and the attentional count form over the key rows (subgacc_sjoin_key_counts_attn).  The buffers
     are those of "counts", where `counts` holds the softmax-weighted count rows W, plus `smax` and `sden` float32 [S] (m_j and den_j, kept
@@ -581,7 +583,7 @@ class StepBuffers:
     def __init__(self, csr, pairs, num_walks=200, num_steps=3, uniq_capacity=1 << 17, out=None, dedup_roots=False, rng="philox",
                  key_rows=True, sort_roots=True, batch=None, align_rows=True, order=None, ptr=True, triplets=False, stage=None,
                  table_rows=2048, dtype=None):
-        from .sampler import FUSED_MAX_Q, as_rank, key_rows_form
+        from .sampler import FUSED_MAX_Q, as_rank, key_rows_form, small_rows_form
         self.half = _half_code(dtype, "StepBuffers", lambda: {
             "ptr=False (segment ids)": not ptr, "triplets=True": triplets, f"stage={stage!r}": stage is not None,
             "key_rows=False (strided rows of table slots)": not key_rows,
@@ -635,6 +637,11 @@ class StepBuffers:
         self.nsize = torch.empty(n, dtype=torch.int32, device=dev)
         self.ids = torch.empty(n * self.stride, dtype=torch.int32, device=dev)
         form = key_rows_form(self.M, self.m) if key_rows else 0
+        # a stage over a small shape (sampler.small_rows_form): its 32-bit key rows come from subgacc_walk_keyrows_small, which reads a
+        # selecting work list; the row form (stage=None) of such a shape stays the table form on the general kernel
+        self.small = stage in _KEY_STAGES and bool(key_rows) and small_rows_form(self.M, self.m)
+        if self.small:
+            form = 32
         self.keyrows = bool(form)                 # rows of LP keys: no table, no feature table
         self.key64 = form == 64                   # ... 64-bit keys (4-hop walks with M >= 128): `slot` is int64
         self.slot = torch.empty(n * self.stride, dtype=torch.int64 if self.key64 else torch.int32, device=dev)
@@ -656,7 +663,7 @@ class StepBuffers:
             self.rng_ws = torch.empty(L.subgacc_rng_positions_workspace_bytes(n), dtype=torch.uint8, device=dev)
         if self.dedup:
             from .sampler import walk_kernel_name
-            if walk_kernel_name(csr, self.M, self.m, True) != "walk_rows_kernel":
+            if walk_kernel_name(csr, self.M, self.m, True) != "walk_rows_kernel" and not self.small:
                 raise ValueError("StepBuffers(dedup_roots=True) needs a shape the fused-row walk kernel serves (2..4 hops, M <= 256)")
             self.own = torch.empty(S, dtype=torch.int64, device=dev)
             # (triplets: no partner list -- the roles prologue leaves it to the kernels, the list is mirrored)
@@ -708,11 +715,11 @@ _KEY_STAGES = _COUNT_STAGES + ("index",)        # ... and the index form
 def _counts_stage_shape(who, num_walks, num_steps, key_rows, table_rows):
     """what the count stage of a step refuses before any device work: a shape without 32-bit key rows, key_rows=False, a table_rows
     the columns pass does not hold"""
-    from .sampler import key_rows_form
+    from .sampler import key_rows_form, small_rows_form
     if not key_rows:
         raise ValueError(f"{who} runs over the key rows of the step: key_rows=False has none")
     form = key_rows_form(int(num_walks), int(num_steps))
-    if form != 32:
+    if form != 32 and not small_rows_form(int(num_walks), int(num_steps)):
         raise ValueError(f"{who} needs 32-bit LP keys: num_walks = {num_walks}, num_steps = {num_steps} " +
                          ("has 64-bit keys (key_rows_form == 64)" if form == 64 else "has no key-rows form"))
     if not 2 <= int(table_rows) <= COUNTS_MAX_TABLE_ROWS:
@@ -735,7 +742,7 @@ def _step_sets(csr, bufs, cfg, rr, step_id):
     sets = SampledSets(bufs.nsize, None, bufs.ids, None, None, None, bufs.M, bufs.m, bufs.stride, None)
     sets.slot, sets.table, sets.capacity, sets.strided = bufs.slot, bufs.table, (0 if kr else bufs.capacity), True
     if kr:
-        sets.keyrows, sets.key64 = True, bufs.key64
+        sets.keyrows, sets.key64, sets.small_rows = True, bufs.key64, bool(getattr(bufs, "small", False))
         # number() registers the keys of the rows as they stand in the buffers (root dedup: the rows of repeated endpoints are
         # empty, and a repeated endpoint never is the first to show an LP row, so the numbering is the one of the whole batch);
         # once the buffers have taken a later batch -- or a captured step has been replayed -- the answer would describe that
@@ -826,7 +833,8 @@ def _buffered_step(csr, e, bufs, seed, out, fit=False):
                          f"these StepBuffers were made for [{B // PB}, 2, {PB}] pairs")
     e = e.contiguous()
     flags = bufs.status.view(torch.int32)[:4]
-    cfg = make_cfg(csr, M, m, -1, seed, bufs.rng, records=(2 <= m <= 4),     # (only the fused-row kernel of 2..4 hops reads hop records)
+    small = bool(getattr(bufs, "small", False))      # a stage over a small shape: subgacc_walk_keyrows_small writes the key rows
+    cfg = make_cfg(csr, M, m, -1, seed, bufs.rng, records=(2 <= m <= 4) and not small,     # (only the fused-row kernel of 2..4 hops reads hop records)
                    row_pitch=bufs.stride if bufs.stride != bufs.Q else 0)
     rr = bufs.rng == "rand_r"
     check(L.subgacc_key_shift(cfg.num_walks, cfg.num_steps))
@@ -855,7 +863,7 @@ def _buffered_step(csr, e, bufs, seed, out, fit=False):
     if bufs.dedup and bufs.order is None:
         work, bufs.walk_order = (bufs.worklist, bufs.n_distinct), "batch"
     elif bufs.dedup or (((bufs.order is not None) or (bufs.sort_roots and n >= SORT_ROOTS_MIN))
-                        and walk_kernel_name(csr, M, m, True) == "walk_rows_kernel"):
+                        and (small or walk_kernel_name(csr, M, m, True) == "walk_rows_kernel")):
         if not hasattr(bufs, "sort_bufs"):        # (made on first use)
             bufs.sort_bufs = worklist_buffers(n, dev)
         work = sorted_worklist(csr, bufs.roots, n, bufs.order.rank if bufs.order is not None else None, bufs.sort_bufs, st)
@@ -866,7 +874,7 @@ def _buffered_step(csr, e, bufs, seed, out, fit=False):
         check(L.subgacc_rng_positions(cfg, ptr(csr.indptr), csr.num_nodes, ptr(bufs.roots), n, 1, 0, ptr(bufs.rng_pos),
                                       ptr(bufs.rng_seed), ptr(bufs.rng_ws), bufs.rng_ws.numel(), st))
     with _timed("walk_sets"):         # (root dedup: the list selects the first occurrences, the other rows are passed over)
-        _walk(cfg, csr, bufs.roots, n, flags, st, "keys64" if bufs.key64 else "fused", ids=bufs.ids, payload=bufs.slot,
+        _walk(cfg, csr, bufs.roots, n, flags, st, "keys_small" if small else "keys64" if bufs.key64 else "fused", ids=bufs.ids, payload=bufs.slot,
               nsize=bufs.nsize, rng=(bufs.rng_pos, bufs.rng_seed) if rr else (None, None), table=bufs.table,
               capacity=0 if kr else bufs.capacity, work=work, select=bufs.dedup)
     if bufs.dedup:
@@ -1072,7 +1080,9 @@ def sample_and_counts(csr, edge, num_walks=200, num_steps=3, seed=111413, dedup_
     the columns past the batch's distinct rows zero; more distinct rows than T - 1 raise SubgAccError.
     buffers=StepBuffers(csr, B, ..., stage="counts", table_rows=T): nothing is allocated and nothing read back (capturable); C, sizes
     and table are views of the buffers, and sets.resolve() raises SubgAccError naming table_rows when the step had more distinct LP
-    rows than columns (C is then not to be used).  Shapes: 32-bit key rows (2 to 4 hops, num_steps*SHIFT+1 <= 31), rng Philox."""
+    rows than columns (C is then not to be used).  Shapes: 32-bit key rows -- 2 to 4 hops with num_steps*SHIFT+1 <= 31 over a 512- or
+    1,024-slot table (sampler.key_rows_form == 32), and the small shapes, 1 to 4 hops with M*m+1 <= 204 (sampler.small_rows_form:
+    csrc/walk_small.hip writes their rows); rng Philox."""
     e = _as_rows(edge, csr.device)
     if e.dim() != 2 or e.shape[0] != 2:
         raise ValueError(f"sample_and_counts: edge must be [2, B], not {list(e.shape)}")
