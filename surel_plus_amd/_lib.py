@@ -1,5 +1,6 @@
 """ctypes binding of libsubgacc_hip.so, derived from the declarations of include/subgacc.h (the C ABI), of include/subgacc_half.h
-(the join's rows in a 16-bit type) and of include/subgacc_small.h (key rows for the small walk shapes) when this module is imported: an entry point is declared there and defined under csrc/, and
+(the join's rows in a 16-bit type), of include/subgacc_small.h (key rows for the small walk shapes) and of include/subgacc_packed.h
+(the step's key rows as one word per member) when this module is imported: an entry point is declared there and defined under csrc/, and
 nothing here names it.
 
 There is no CPU fallback: if the library is missing, or no gfx950 device is visible when a compute entry
@@ -123,6 +124,11 @@ SMALL_HEADER = os.path.join(os.path.dirname(HEADER), "subgacc_small.h")
 SMALL_DECLS = parse_header(_header_text(SMALL_HEADER))
 _TYPES.update(bind_types(SMALL_DECLS))
 SMALL_SYMBOLS = tuple(SMALL_DECLS)
+# the fourth header: the step's key rows as one word per member (csrc/walk_rows.hip's packed store, csrc/sjoin_packed.hip), the same library
+PACKED_HEADER = os.path.join(os.path.dirname(HEADER), "subgacc_packed.h")
+PACKED_DECLS = parse_header(_header_text(PACKED_HEADER))
+_TYPES.update(bind_types(PACKED_DECLS))
+PACKED_SYMBOLS = tuple(PACKED_DECLS)
 HALF_F16, HALF_BF16 = (int(re.search(rf"^#define\s+SUBGACC_HALF_{n}\s+(\d+)", _HALF_TEXT, re.M).group(1)) for n in ("F16", "BF16"))
 
 
@@ -134,7 +140,7 @@ VERBOSE = os.environ.get("SUBGACC_QUIET", "0") != "1"
 def build(force=False):
     """hipcc-compile csrc/*.hip for gfx950 into surel_plus_amd/libsubgacc_hip.so (in-tree)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))]
-    srcs += [HEADER, HALF_HEADER, SMALL_HEADER]
+    srcs += [HEADER, HALF_HEADER, SMALL_HEADER, PACKED_HEADER]
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
         subprocess.check_call(["make", "-s", "-C", CSRC, "-j4", "all"])

@@ -21,16 +21,7 @@
 
 namespace subgacc {
 
-// Workgroups per pair of sjoin_pair_kernel: batches far below the chip's ~4,096 resident workgroups are split in two
-// (B = 1,024 pairs: 22 -> 18 us; four or eight parts pay more for the repeated row loads than they gain: 21 / 25 us)
-static inline int pair_split(int64_t pairs) {
-#ifdef SG_DEV_JOIN_SPLIT      // dev builds only (tools/ab.py: -DSG_DEV_JOIN_SPLIT=n)
-    return SG_DEV_JOIN_SPLIT;
-#endif
-    int sp = 1;
-    while (sp < 2 && pairs * sp * 2 <= 4096) sp *= 2;
-    return sp;
-}
+// (pair_split and key_stage_bytes live in sjoin.hpp: sjoin_packed.hip sizes its launches by them too)
 
 // Emit up to 64 consecutive output rows of one segment (one per lane): look the lane's member up in the
 // partner row (binary search over sorted ids held in LDS) and write the feature pairs of the whole 64-row span
@@ -187,110 +178,8 @@ __global__ __launch_bounds__(kJoinThreads) void sjoin_fill_kernel(const JoinArgs
 //     num_walks divide (main.py:174's IEEE division either way);
 //   * partner absent == key 0, whose unpacked row IS the zero row (flag 0, every count 0): no special case;
 //   * every width goes through the per-wave staging area and leaves as aligned 16-byte words.
-struct KeyQuot {
-    float fm, rcp;
-    bool divide;
-};
-__device__ __forceinline__ float lp_quotient(uint32_t c, const KeyQuot &q) {
-    const float a = (float)c;
-    if (q.divide) return a / q.fm;
-    const float q0 = a * q.rcp;
-    return __fmaf_rn(__fmaf_rn(-q.fm, q0, a), q.rcp, q0);
-}
-template <bool K64>
-__device__ __forceinline__ float key_field(typename std::conditional<K64, unsigned long long, uint32_t>::type key, int c, int m, int shift,
-                                           const KeyQuot &q) {
-    if (c == 0) return (float)(uint32_t)((key >> (m * shift)) & 1u);
-    return lp_quotient((uint32_t)(key >> ((m - c) * shift)) & ((1u << shift) - 1u), q);
-}
-
-// one 64-row span of the output: the lane's row (own key ka, partner key kb; 0 = absent) unpacked into the wave's staging area at
-// the span's offset modulo 16 bytes, then out as aligned 16-byte words (a head / tail of up to three floats from one lane each)
-// TAB: the payload is not a key but SFptr+1 (0 = absent = the table's zero row): the two feature rows are read from the Z_SF table
-// (a few KB..MB, L2-resident; KV = 4: one 16-byte read each), the index pair itself leaves through out_idx when asked for
-template <int KV, bool K64, bool TAB, typename Key>
-__device__ __forceinline__ void emit_key_span(const JoinArgs &a, int lane, bool live, Key ka, Key kb, int nrows, int64_t row0, int64_t segj,
-                                              int kc, const KeyQuot &q, float *stage) {
-    const int w = 2 * kc, m = kc - 1, shift = a.key_shift;
-    if (TAB) {
-        if (a.out_idx && live) {
-            int2 v;
-            v.x = (int32_t)ka, v.y = (int32_t)kb;
-            stream_store(reinterpret_cast<int2 *>(a.out_idx) + row0 + lane, v);
-        }
-        if (!a.out_xz) {      // index pairs only: no table is consulted
-            if (a.out_segid && live) __builtin_nontemporal_store(segj, a.out_segid + row0 + lane);
-            return;
-        }
-        if (live && ((uint64_t)ka >= (uint64_t)a.table_rows || (uint64_t)kb >= (uint64_t)a.table_rows)) {
-            atomicOr(&a.flags[3], 2);  // SFptr outside the table: never read out of bounds
-            ka = kb = 0;
-        }
-    }
-    float *dst = a.out_xz + row0 * w;
-    const int mis = (int)(((uintptr_t)dst >> 2) & 3);       // floats between the 16-byte boundary in front and the span
-    const int head = (4 - mis) & 3;                         // floats of the span in front of its first aligned word
-    if (live) {
-        float *mine = stage + mis + lane * w;
-        if (TAB && KV == 4) {
-            const float4 fa = reinterpret_cast<const float4 *>(a.table)[(uint32_t)ka], fb = reinterpret_cast<const float4 *>(a.table)[(uint32_t)kb];
-            mine[0] = fa.x, mine[1] = fa.y, mine[2] = fa.z, mine[3] = fa.w;
-            mine[4] = fb.x, mine[5] = fb.y, mine[6] = fb.z, mine[7] = fb.w;
-        } else if (TAB && KV > 0) {      // a compile-time width: all 2*KV reads leave together, then the writes
-            const float *ta = a.table + (int64_t)(uint32_t)ka * KV, *tb = a.table + (int64_t)(uint32_t)kb * KV;
-            float f[2 * (KV > 0 ? KV : 1)];
-#pragma unroll
-            for (int c = 0; c < KV; ++c) f[c] = ta[c], f[KV + c] = tb[c];
-#pragma unroll
-            for (int c = 0; c < 2 * KV; ++c) mine[c] = f[c];
-        } else if (TAB) {
-            const float *ta = a.table + (int64_t)(uint32_t)ka * kc, *tb = a.table + (int64_t)(uint32_t)kb * kc;
-            for (int c = 0; c < kc; ++c) {
-                mine[c] = ta[c];
-                mine[kc + c] = tb[c];
-            }
-        } else if (KV > 0) {
-            float f[2 * (KV > 0 ? KV : 1)];
-#pragma unroll
-            for (int c = 0; c < KV; ++c) {
-                f[c] = key_field<K64>(ka, c, m, shift, q);
-                f[KV + c] = key_field<K64>(kb, c, m, shift, q);
-            }
-#pragma unroll
-            for (int c = 0; c < 2 * KV; ++c) mine[c] = f[c];
-        } else
-            for (int c = 0; c < kc; ++c) {
-                mine[c] = key_field<K64>(ka, c, m, shift, q);
-                mine[kc + c] = key_field<K64>(kb, c, m, shift, q);
-            }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const int total = nrows * w;                            // floats of the span
-    const int nbody = SJ_HOOK_SPAN_STORES(total > head ? (total - head) >> 2 : 0);       // aligned 16-byte words
-    const int ntail = total > head ? (total - head) & 3 : 0;
-    const float *src = stage + mis;                         // float i of the span
-    const float4 *src4 = reinterpret_cast<const float4 *>(src + head);   // stage, or stage + 4: 16-byte aligned
-    float4 *dst4 = reinterpret_cast<float4 *>(dst + head);
-    if (mis | ntail) {                                      // (never for rows of 16 or 32 bytes in an aligned buffer)
-        const int i = kWave - 1 - lane;                     // the last lanes have the fewest body words
-        if (i < head && i < total) __builtin_nontemporal_store(src[i], dst + i);
-        const int t2 = kWave - 4 - lane, at = head + 4 * nbody;
-        if (t2 >= 0 && t2 < ntail) __builtin_nontemporal_store(src[at + t2], dst + at + t2);
-    }
-    if (KV > 0) {
-#pragma unroll
-        for (int qd = 0; qd < (KV + 1) / 2; ++qd) {         // 64 rows x 2*KV floats = 32*KV words
-            const int f = lane + qd * kWave;
-            if (f < nbody) stream_store(dst4 + f, src4[f]);
-        }
-    } else
-        for (int f = lane; f < nbody; f += kWave) stream_store(dst4 + f, src4[f]);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");     // the next span of this wave re-uses the area
-    __builtin_amdgcn_wave_barrier();
-    if (a.out_segid && live) __builtin_nontemporal_store(segj, a.out_segid + row0 + lane);
-}
+// (KeyQuot, lp_quotient, key_field and emit_key_span -- a key's fields as floats, one 64-row span of the output -- live in sjoin.hpp:
+//  sjoin_packed.hip emits its rows through the same functions)
 
 template <int KV, int NT, bool K64, bool TAB = false>
 __global__ __launch_bounds__(NT) void sjoin_keypair_kernel(const JoinArgs a, uint32_t pb, uint32_t pairs) {
@@ -703,8 +592,6 @@ __global__ __launch_bounds__(NT) void sjoin_star_kernel(const JoinArgs a, uint32
 
 using namespace subgacc;
 
-// LDS of the per-wave staging areas of emit_key_span: [4 + 64 x 2k] floats per wave + the round-up to a 16-byte boundary
-static inline size_t key_stage_bytes(int waves, int k) { return 16 + (size_t)waves * (kWave * 2 * k + 4) * 4; }
 
 // Table payload (SFptr+1, or slots of the table of distinct rows) over a mirrored list: the pair kernel of the key rows with the
 // feature rows read from the Z_SF table instead of unpacked (round 5: the resident-store join of the reference's own flow,

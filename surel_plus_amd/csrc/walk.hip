@@ -23,6 +23,7 @@
 #include "blockscan.hpp"
 #include "uniq_table.hpp"
 #include "walk_common.hpp"
+#include "../../include/subgacc_packed.h"
 #include <stdlib.h>
 
 namespace subgacc {
@@ -785,6 +786,8 @@ struct WalkLaunch {
     const int32_t *worklist = nullptr;
     const int64_t *n_work = nullptr;
     int64_t work_cap = 0;
+    int32_t *nesc = nullptr;      // kRowsKeys32 as packed rows (subgacc_walk_keyrows_packed): ids = the words, slot = the escape lists
+    int32_t pk_cb = 0, pk_fb = 0;
 };
 
 static int launch_walk(const WalkLaunch &w) {
@@ -845,6 +848,8 @@ static int launch_walk(const WalkLaunch &w) {
     a.table = table ? uniq_view(w.uniq_table, w.uniq_capacity) : UniqTable{nullptr, nullptr, nullptr, 0};
     a.keyrows = (w.form == kRowsKeys32 || w.form == kRowsKeys64) ? 1 : 0;
     a.root_base = w.root_base;
+    a.pk_fmt = 0;
+    if (w.nesc) a.nesc = w.nesc, a.pk_fmt = w.pk_cb | (w.pk_fb << 8);
     a.recs = (const unsigned long long *)cfg->hop_records;
     a.rec.id_bits = cfg->rec_id_bits, a.rec.beg_bits = cfg->rec_beg_bits;
     SG_REQUIRE(!a.recs || (a.rec.id_bits == 0 && a.rec.beg_bits == 0) ||
@@ -875,6 +880,8 @@ static int launch_walk(const WalkLaunch &w) {
         SG_LAUNCH_CHECK();
         return SUBGACC_OK;
     }
+    SG_REQUIRE(!a.pk_fmt, SUBGACC_ERR_BADARG,
+               "walk_keyrows_packed: packed rows are written by the two-wave key-row forms of the fused-row kernel alone; M = %d, m = %d", M, m);
     SG_REQUIRE(!tags_only, SUBGACC_ERR_BADARG,
                "walk_tags: only the fused-row kernel registers tags alone (2..4 hops, M <= 256, a 512- or 1,024-slot table, no "
                "bucket); M = %d, m = %d", M, m);
@@ -984,6 +991,44 @@ extern "C" int subgacc_walk_keyrows64(const subgacc_walk_cfg *cfg, const void *i
     WalkLaunch w{cfg, indptr, indices, num_nodes, query, n, rng_pos, rng_seed, flags, stream, kRowsKeys64};
     w.ids = row_ids, w.keys = row_keys, w.nsize = nsize;
     if (worklist) w.list = kListSelect, w.worklist = worklist, w.n_work = n_work;
+    return launch_walk(w);
+}
+
+// Packed key rows (include/subgacc_packed.h): the 32-bit key rows of subgacc_walk_spg(uniq_table = NULL) as one word per member and
+// an escape list per row.  The shape must be one the packed store exists for (subgacc_packed_rows_format)
+extern "C" int subgacc_packed_rows_format(int64_t num_nodes, int32_t num_walks, int32_t num_steps, int32_t indptr64, int32_t *code_bits,
+                                          int32_t *field_bits) {
+    SG_REQUIRE(num_nodes >= 0 && code_bits && field_bits, SUBGACC_ERR_BADARG, "packed_rows_format: bad arguments");
+    const PackFmt f = pack_format(num_nodes, num_steps);
+    *code_bits = f.cb, *field_bits = f.fb;
+    if (num_walks < 1 || num_walks > kWalkThreads || num_steps < 2 || num_steps > 4) return 0;
+    int shift = 0;
+    while ((1 << shift) <= num_walks) ++shift;
+    const int T = table_size_for((int64_t)num_walks * num_steps + 1);
+    if (num_steps * shift + 1 > 31 || (T != 512 && T != 1024)) return 0;      // 32-bit key rows of walk_rows_kernel
+    if (T == 512 && num_steps == 2 && !indptr64) return 0;                    // the one-wave form keeps its two planes
+    return f.fb >= 3 ? 1 : 0;
+}
+
+extern "C" int subgacc_walk_keyrows_packed(const subgacc_walk_cfg *cfg, const void *indptr, const int32_t *indices, int64_t num_nodes,
+                                           const int32_t *query, int64_t n, const uint32_t *rng_pos, const uint32_t *rng_seed,
+                                           const int32_t *worklist, const int64_t *n_work, int32_t list_selects, int32_t *row_words,
+                                           int32_t *row_esc, int32_t *nsize, int32_t *nesc, int32_t *flags, void *stream) {
+    SG_REQUIRE(row_words && row_esc && nesc && (worklist != nullptr) == (n_work != nullptr), SUBGACC_ERR_BADARG,
+               "walk_keyrows_packed: null row_words / row_esc / nesc, or a work list without its length (or the reverse)");
+    SG_REQUIRE(cfg && !cfg->emit_walks && cfg->order == SUBGACC_ORDER_WALK_MAJOR && cfg->bucket <= 0, SUBGACC_ERR_BADARG,
+               "walk_keyrows_packed: set_sampler order only, no raw walks, no bucket");
+    SG_REQUIRE(!(worklist && list_selects) || cfg->rng_mode == SUBGACC_RNG_PHILOX, SUBGACC_ERR_BADARG,
+               "walk_keyrows_packed: a selecting work list goes with Philox mode (a root's set must not depend on its place in the batch)");
+    int32_t cb = 0, fb = 0;
+    const int ok = subgacc_packed_rows_format(num_nodes, cfg->num_walks, cfg->num_steps, cfg->indptr64, &cb, &fb);
+    if (ok < 0) return ok;
+    SG_REQUIRE(ok == 1, SUBGACC_ERR_BADARG,
+               "walk_keyrows_packed: no packed rows for %lld nodes, M = %d, m = %d (32-bit key rows of a two-wave form, 2 to 4 hops, "
+               "(31 - id bits) / m >= 3: subgacc_packed_rows_format)", (long long)num_nodes, cfg->num_walks, cfg->num_steps);
+    WalkLaunch w{cfg, indptr, indices, num_nodes, query, n, rng_pos, rng_seed, flags, stream, kRowsKeys32};
+    w.ids = row_words, w.slot = row_esc, w.nsize = nsize, w.nesc = nesc, w.pk_cb = cb, w.pk_fb = fb;
+    if (worklist) w.list = list_selects ? kListSelect : kListOrder, w.worklist = worklist, w.n_work = n_work;
     return launch_walk(w);
 }
 

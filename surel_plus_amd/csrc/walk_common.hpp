@@ -4,6 +4,7 @@
 #include "common.hpp"
 #include "blockscan.hpp"
 #include "uniq_table.hpp"
+#include "packed_rows.hpp"
 
 namespace subgacc {
 
@@ -107,7 +108,10 @@ struct WalkArgs {
     int64_t num_nodes;   // a root outside [0, num_nodes) is never looked up: empty set, flags[3] |= 16 (the host raises)
     const uint32_t *rng_pos, *rng_seed;
     int32_t *set_ids;
-    uint64_t *set_keys;
+    union {                  // (never both: 64-bit key rows | packed 32-bit key rows)
+        uint64_t *set_keys;
+        int32_t *nesc;       // packed key rows (pk_fmt != 0): the lengths of the rows' escape lists
+    };
     int32_t *nsize;
     int32_t *walks;
     int32_t *flags;
@@ -129,7 +133,12 @@ struct WalkArgs {
     int64_t work_cap;    // with a work list: the launch covers min(n, work_cap) rows (0 = n); a longer list raises flags[3] |= 32
     int32_t tags_only;   // table-form fused rows (subgacc_walk_tags): register the set's LP keys with their exact first-visit tags
                          // and leave -- no row, no nsize is written (the rows exist already, as key rows)
+    // packed key rows (subgacc_walk_keyrows_packed, packed_rows.hpp): cb | fb << 8 -- set_ids takes the words (id << cb | code),
+    // set_slot the rows' escape lists, nesc their lengths; 0: the two planes of ids and keys.  (In the struct's tail padding, as nesc
+    // shares set_keys' place: the arguments of every kernel that takes a WalkArgs keep their size and offsets.)
+    int32_t pk_fmt;
 };
+static_assert(sizeof(WalkArgs) == 264, "WalkArgs is every walk kernel's argument: a new field belongs into its padding, or every kernel's code changes");
 
 constexpr int kSpgFoldBits = 7;
 constexpr int kSpgFold = 1 << kSpgFoldBits;   // block-local table of the set's distinct LP keys

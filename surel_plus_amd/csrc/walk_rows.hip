@@ -171,7 +171,9 @@ __device__ __forceinline__ uint32_t rows_count16(uint32_t *cnt2, uint32_t idx) {
 // global atomics) and the first-visit bookkeeping (minq: one LDS atomic per visit, 4 bytes of LDS per slot) fall away.
 // EPLP (key rows): members per lane the epilogue's sort provides registers for, ns <= EPLP * NT (0: SPL, or 7 for one wave x 8 slots:
 // a 512-slot table holds 408) -- every reference shape has M * m + 1 <= 640, five members per lane of 128: 69 VGPRs instead of 80 + scratch.
-template <bool IDX64, int RNG, int MH, int SPL, int NT, int REC = 0, bool K32 = false, bool KR = false, int EPLP = 0>
+// PK (32-bit key rows of two waves): the row leaves packed (packed_rows.hpp) -- one word per member, id << cb | code, into set_ids, and
+// the keys that do not fit the code into the head of the row's set_slot, their number into nesc.  Only the final store differs.
+template <bool IDX64, int RNG, int MH, int SPL, int NT, int REC = 0, bool K32 = false, bool KR = false, int EPLP = 0, bool PK = false>
 // (waves per SIMD asked of the register allocator: the table form with 32-bit counts holds 12 bytes of LDS per slot + the fold table,
 //  ~15 KB per workgroup of two waves = 5 waves per SIMD whatever the registers; 64-bit counts on 128 lanes, 10.5 KB: 7; the rest 8)
 //  key rows with 32-bit counts: 6 asked for -- since round 6 the kernel needs 51 VGPRs (five members per lane in the sort, their state in
@@ -179,6 +181,7 @@ template <bool IDX64, int RNG, int MH, int SPL, int NT, int REC = 0, bool K32 = 
 //  then holds is the launch's choice, through the LDS it asks for: SG_ROWS_KR_LDS_MIN)
 __global__ __launch_bounds__(NT, K32 ? (KR ? 6 : 5) : (KR ? 5 : (NT == 128 ? 7 : 8))) __attribute__((amdgpu_num_sgpr(SG_ROWS_SGPR))) void walk_rows_kernel(const WalkArgs a) {
     constexpr bool KR64 = KR && !K32;      // rows of 64-bit LP keys
+    static_assert(!PK || (KR && K32 && NT == 2 * kWave), "packed rows: 32-bit key rows, two waves");
     extern __shared__ __align__(16) unsigned char lds_raw[];
     using CntT = typename std::conditional<K32, uint32_t, unsigned long long>::type;
     static_assert(SPL % 4 == 0, "slot ownership: 4-slot chunks");
@@ -222,6 +225,7 @@ __global__ __launch_bounds__(NT, K32 ? (KR ? 6 : 5) : (KR ? 5 : (NT == 128 ? 7 :
     const int32_t root = a.query[i];
     if (root == SUBGACC_NO_ROOT) {     // a repeated endpoint of the batch: its first occurrence carries the set (uniq.hip: step dedup)
         if (tid == 0 && !a.tags_only) a.nsize[i] = 0;
+        if (PK && tid == 0) a.nesc[i] = 0;
         return;
     }
     // while the root's two dependent loads (query -> row pointer) are in flight: clear what does not depend on them
@@ -247,6 +251,7 @@ __global__ __launch_bounds__(NT, K32 ? (KR ? 6 : 5) : (KR ? 5 : (NT == 128 ? 7 :
         if (tid == 0) {
             atomicOr(&a.flags[3], 16);
             if (!a.tags_only) a.nsize[i] = 0;
+            if (PK) a.nesc[i] = 0;
         }
         return;
     }
@@ -276,6 +281,12 @@ __global__ __launch_bounds__(NT, K32 ? (KR ? 6 : 5) : (KR ? 5 : (NT == 128 ? 7 :
             for (int s = 0; s < MH; ++s) k |= (unsigned long long)M << (s * a.shift);
             if (!KR && a.tags_only) {
                 uniq_global_insert(a.table, k, tag0, a.flags);
+            } else if (PK) {
+                const uint32_t code = pack_code<MH>((uint32_t)k, a.shift, a.pk_fmt & 255, a.pk_fmt >> 8);
+                const bool esc = code == (1u << (a.pk_fmt & 255)) - 1u;
+                a.set_ids[obase] = (int32_t)(((uint32_t)root << (a.pk_fmt & 255)) | code);
+                if (esc) a.set_slot[obase] = (int32_t)k;
+                a.nsize[i] = 1, a.nesc[i] = esc ? 1 : 0;
             } else {
                 a.set_ids[obase] = root;
                 if (KR64) a.set_keys[obase] = k;
@@ -932,6 +943,63 @@ __global__ __launch_bounds__(NT, K32 ? (KR ? 6 : 5) : (KR ? 5 : (NT == 128 ? 7 :
             if (e * NT + tid < ns) A[st[e]] = el[e];
         }
         __syncthreads();
+        if constexpr (PK) {
+            // The packed row: a lane takes PER consecutive sorted members (four where rows begin on 16-byte boundaries), forms their
+            // words, and gives every escape its rank among the row's escapes in sorted order -- a wave prefix over the lanes' escape
+            // counts, the other wave's total through two of the reduction words (all sixteen were read long ago), a running base over
+            // the trips.  One 16-byte store of words per lane; an escape's key goes to set_slot[obase + rank].
+            // (Measured instead and not kept: no barrier in the loop, every wave counting the other wave's escapes of the trip itself
+            //  from the sorted row in LDS -- the cit2 walk 0.629 ms against 0.624, the walk of the graph with id locality 0.62 against
+            //  0.60: profiles/packed_rows_bench.log.)
+            typedef int v4i __attribute__((ext_vector_type(4)));
+            const int cb = a.pk_fmt & 255, fb = a.pk_fmt >> 8, shift = a.shift;
+            const uint32_t ones = (1u << cb) - 1u;
+            const int wv = tid / kWave;
+            auto store = [&](auto perc) {
+                constexpr int PER = decltype(perc)::value;
+                int ebase = 0;
+                for (int x0 = 0, trip = 0; x0 < ns; x0 += PER * NT, ++trip) {
+                    const int x = x0 + PER * tid;
+                    uint32_t wd[PER], key[PER];
+                    int ne = 0;
+#pragma unroll
+                    for (int j = 0; j < PER; ++j) {
+                        wd[j] = 0u, key[j] = 0u;
+                        if (x + j < ns) {
+                            const unsigned long long v = A[x + j];
+                            key[j] = (uint32_t)v;
+                            const uint32_t code = pack_code<MH>(key[j], shift, cb, fb);
+                            wd[j] = ((uint32_t)(v >> 32) << cb) | code;
+                            ne += code == ones ? 1 : 0;
+                        }
+                    }
+                    const int incl = wave_scan_add_i32_incl(ne);
+                    int32_t *tot = red + (trip & 1) * 2;      // (the trip after next writes here again: a barrier lies between)
+                    if ((tid & (kWave - 1)) == kWave - 1) tot[wv] = incl;
+                    __syncthreads();
+                    const int t0 = tot[0], t1 = tot[1];
+                    int rank = ebase + (wv ? t0 : 0) + incl - ne;
+                    ebase += t0 + t1;
+                    if (PER == 4 && x + 3 < ns) {
+                        const v4i w4 = {(int32_t)wd[0], (int32_t)wd[PER > 1 ? 1 : 0], (int32_t)wd[PER > 2 ? 2 : 0], (int32_t)wd[PER > 3 ? 3 : 0]};
+                        SG_ROW_STORE((v4i *)&a.set_ids[obase + x], w4);
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < PER; ++j)
+                            if (x + j < ns) SG_ROW_STORE(&a.set_ids[obase + x + j], (int32_t)wd[j]);
+                    }
+                    if (ne) {
+#pragma unroll
+                        for (int j = 0; j < PER; ++j)
+                            if (x + j < ns && (wd[j] & ones) == ones) SG_ROW_STORE(&a.set_slot[obase + rank++], (int32_t)key[j]);
+                    }
+                }
+                if (tid == 0) a.nesc[i] = ebase;
+            };
+            if (a.wide_rows) store(std::integral_constant<int, 4>());
+            else store(std::integral_constant<int, 1>());
+            return;
+        }
         int xs = tid;
         if (!KR64 && a.wide_rows) {      // rows begin on 16-byte boundaries (a pitch of whole lines): four members per lane and store
             typedef int v4i __attribute__((ext_vector_type(4)));
@@ -1194,11 +1262,17 @@ struct RowsLaunch {
 };
 
 // one launch: with hop records (16 bytes with int64 row offsets, 8 with int32) or over plain CSR
-template <bool I64, int RNG, int MH, int SPL, int NT, bool K32, bool KR, int EPLP>
+template <bool I64, int RNG, int MH, int SPL, int NT, bool K32, bool KR, int EPLP, bool PK = false>
 static int rows_launch(const RowsLaunch &l, size_t lds) {
-    if (l.rec) hipLaunchKernelGGL((walk_rows_kernel<I64, RNG, MH, SPL, NT, I64 ? 16 : 8, K32, KR, EPLP>), dim3((unsigned)l.grid), dim3(NT), lds, l.s, l.a);
-    else hipLaunchKernelGGL((walk_rows_kernel<I64, RNG, MH, SPL, NT, 0, K32, KR, EPLP>), dim3((unsigned)l.grid), dim3(NT), lds, l.s, l.a);
+    if (l.rec) hipLaunchKernelGGL((walk_rows_kernel<I64, RNG, MH, SPL, NT, I64 ? 16 : 8, K32, KR, EPLP, PK>), dim3((unsigned)l.grid), dim3(NT), lds, l.s, l.a);
+    else hipLaunchKernelGGL((walk_rows_kernel<I64, RNG, MH, SPL, NT, 0, K32, KR, EPLP, PK>), dim3((unsigned)l.grid), dim3(NT), lds, l.s, l.a);
     return 1;
+}
+// a two-wave form of the 32-bit key rows, with its two planes or -- a.pk_fmt -- packed
+template <bool I64, int RNG, int MH, int SPL, int EPLP>
+static int rows_launch_kr2(const RowsLaunch &l, size_t lds) {
+    if (l.a.pk_fmt) return rows_launch<I64, RNG, MH, SPL, 128, true, true, EPLP, true>(l, lds);
+    return rows_launch<I64, RNG, MH, SPL, 128, true, true, EPLP>(l, lds);
 }
 
 // The forms, each with its admission test and its LDS size.  Every `if constexpr` stands for a form that no shape with these
@@ -1216,6 +1290,7 @@ template <bool I64, int RNG, int MH>
 static int rows_form(const RowsLaunch &l) {
     const WalkArgs &a = l.a;
     const int bits = a.m * a.shift + 1;
+    if (a.pk_fmt && !(a.keyrows && bits <= 31)) return 0;      // packed rows: 32-bit key rows or nothing
     if (a.keyrows && bits > 31) {
         // 64-bit key rows (round 4): the 4-hop shapes whose keys need 33+ bits (M = 128 .. 204: 4 x 8 + 1) -- 64-bit counts in the
         // walk tables, the keys leave through set_keys.  1,024-slot table, 128 lanes x 2 walks x 8 slots, ~15 KB of LDS per root.
@@ -1239,12 +1314,12 @@ static int rows_form(const RowsLaunch &l) {
         if (!(one_wave && a.T == 512) && ldsk < (size_t)SG_ROWS_KR_LDS_MIN) ldsk = SG_ROWS_KR_LDS_MIN;
         if (a.T == 1024) {
             // five members per lane in the sort up to 640 members; only the 3-hop strides go further (2 hops: 513, 4 hops: 509)
-            if (a.stride <= 5 * 128) return rows_launch<I64, RNG, MH, 8, 128, true, true, 5>(l, ldsk);
-            if constexpr (MH == 3) return rows_launch<I64, RNG, 3, 8, 128, true, true, 0>(l, ldsk);
+            if (a.stride <= 5 * 128) return rows_launch_kr2<I64, RNG, MH, 8, 5>(l, ldsk);
+            if constexpr (MH == 3) return rows_launch_kr2<I64, RNG, 3, 8, 0>(l, ldsk);
             return 0;
         }
-        if constexpr (one_wave) return rows_launch<I64, RNG, 2, 8, 64, true, true, 0>(l, ldsk);
-        else return rows_launch<I64, RNG, MH, 4, 128, true, true, 0>(l, ldsk);
+        if constexpr (one_wave) return a.pk_fmt ? 0 : rows_launch<I64, RNG, 2, 8, 64, true, true, 0>(l, ldsk);      // (one wave: never packed)
+        else return rows_launch_kr2<I64, RNG, MH, 4, 0>(l, ldsk);
     }
     if (a.T == 1024) {
         // counts that fit 32 bits: 128 lanes x 8 slots, 12 bytes of LDS per slot -> 11 roots per CU.  int32 row offsets +

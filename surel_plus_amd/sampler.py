@@ -93,6 +93,20 @@ def small_rows_form(num_walks, num_steps):
     return num_walks >= 1 and 1 <= num_steps <= 4 and _table_slots(num_walks, num_steps) <= 256
 
 
+def packed_rows_form(num_nodes, num_walks, num_steps, indptr64=False):
+    """(cb, fb) of the packed key rows of this graph and shape, or None where there are none -- subgacc_packed_rows_format
+    (csrc/walk.hip), restated: the 32-bit key rows of a TWO-wave form of the fused-row kernel, 2 to 4 hops, and a word with room for
+    three bits a count beside the id: id_bits = bits of num_nodes - 1 (at least 1), cb = 32 - id_bits, fb = (cb - 1) // m >= 3."""
+    num_nodes, num_walks, num_steps = int(num_nodes), int(num_walks), int(num_steps)
+    if num_nodes < 0 or num_walks < 1 or key_rows_form(num_walks, num_steps) != 32:
+        return None
+    if _table_slots(num_walks, num_steps) == 512 and num_steps == 2 and not indptr64:      # one wave per root: its two planes stay
+        return None
+    cb = 32 - max((num_nodes - 1).bit_length(), 1)
+    fb = (cb - 1) // num_steps if cb > 0 else 0
+    return (cb, fb) if fb >= 3 else None
+
+
 def key_rows_ok(num_walks, num_steps):
     """32-bit key rows for this shape? (what the batched registration of a kept store, csrc/keyrows.hip, works on)"""
     return key_rows_form(num_walks, num_steps) == 32
@@ -500,6 +514,32 @@ class SampledSets:
         return out
 
 
+class PackedStepSets(SampledSets):
+    """The SampledSets of a step whose rows stand PACKED in its StepBuffers (include/subgacc_packed.h): `ids` and `slot` are the
+    buffers' unpacked planes -- today's rows, made by subgacc_unpack_packed_rows when somebody first looks at them, never by the
+    step.  Everything that reads a step's rows (StridedSpG(sets), to_csr(), number()) goes through these two; nothing may assign
+    them (a packed step is strided, and no strided path does): AttributeError, so that a value is never dropped unseen."""
+    _bufs = None
+
+    @property
+    def ids(self):
+        return self._bufs.ids
+
+    @ids.setter
+    def ids(self, value):      # (the dataclass's __init__ assigns None: the rows are the buffers')
+        if value is not None:
+            raise AttributeError("PackedStepSets.ids: the rows of a packed step are its StepBuffers' (unpacked on demand) and cannot be assigned")
+
+    @property
+    def slot(self):
+        return self._bufs.slot
+
+    @slot.setter
+    def slot(self, value):
+        if value is not None:
+            raise AttributeError("PackedStepSets.slot: the rows of a packed step are its StepBuffers' (unpacked on demand) and cannot be assigned")
+
+
 @dataclass
 class LocalityOrder:
     """An order of the nodes that puts the members of a graph community next to each other (locality_order()): rank[v] = position
@@ -627,10 +667,11 @@ def _rng_positions(L, cfg, csr, q, n, rng_streams, calls_before, st):
 
 
 def _walk(cfg, csr, roots, n, flags, st, form, ids=None, payload=None, nsize=None, walks=None, rng=(None, None), table=None,
-          capacity=0, work=None, select=False, root_base=0, work_cap=0):
+          capacity=0, work=None, select=False, root_base=0, work_cap=0, nesc=None):
     """The subgacc_walk_* call of every walk (csrc/walk.hip).  form: "sets" (ids + LP keys in first-visit order, the raw walks with
     cfg.emit_walks), "fused" (ids sorted + table slots, without a table 32-bit LP keys), "keys64" (ids sorted + 64-bit LP keys),
-    "keys_small" (ids sorted + 32-bit LP keys of a small shape, small_rows_form: csrc/walk_small.hip) or
+    "keys_small" (ids sorted + 32-bit LP keys of a small shape, small_rows_form: csrc/walk_small.hip), "keys_packed" (the 32-bit key
+    rows packed: ids = one word per member, payload = the escape lists, nesc their lengths; work with or without select) or
     "tags" (no rows: the listed roots' LP keys go into `table` with their first-visit tags).  rng = (rng_pos, rng_seed) under rand_r;
     work = (list, its length on the device): the rows to sample with select=True, "keys64", "keys_small" and "tags", else an order over all rows."""
     L, g = lib(), (cfg, ptr(csr.indptr), ptr(csr.indices), csr.num_nodes, ptr(roots), n)
@@ -645,6 +686,8 @@ def _walk(cfg, csr, roots, n, flags, st, form, ids=None, payload=None, nsize=Non
         return check(L.subgacc_walk_keyrows64(*g, rp, rs, wl, nwl, *rows))
     if form == "keys_small":
         return check(L.subgacc_walk_keyrows_small(*g, rp, rs, wl, nwl, *rows))
+    if form == "keys_packed":     # ids = the word plane, payload = the escape lists (include/subgacc_packed.h)
+        return check(L.subgacc_walk_keyrows_packed(*g, rp, rs, wl, nwl, 1 if select else 0, *rows[:3], ptr(nesc), *rows[3:]))
     if work is None:
         return check(L.subgacc_walk_spg(*g, root_base, rp, rs, *tab, *rows))
     if select:

@@ -578,12 +578,19 @@ class StepBuffers:
     dtype=torch.float16 / torch.bfloat16: `out` -- the largest buffer of the set -- is allocated in that type, half the bytes, and the
     step's join writes it through subgacc_sjoin_fill_half (sjoin(dtype=)); sample_and_gather(buffers=) must ask for the same dtype.
     The row form over 32-bit key rows with segment pointers: ValueError for ptr=False, triplets=True, a stage, key_rows=False, a shape
-    with 64-bit keys or none, and batch=."""
+    with 64-bit keys or none, and batch=.
+    packed_rows=None|True|False: the hand-over of the step's rows from the walk to the join as ONE word per member and a short escape
+    list per row (include/subgacc_packed.h) instead of two planes -- `self.packed`.  None: the library's choice, which
+    is packed wherever the form exists: the row form (stage=None) with f32 rows, segment pointers, pairs and one batch per step, over
+    32-bit key rows of a two-wave form on a graph whose ids leave three bits a count (sampler.packed_rows_form).  True: the same, and
+    ValueError where it does not exist.  False: the two planes.  `ids` and `slot` show today's rows either way: of a packed step
+    they are unpacked when first looked at (subgacc_unpack_packed_rows, into planes allocated then), never in the step."""
 
     def __init__(self, csr, pairs, num_walks=200, num_steps=3, uniq_capacity=1 << 17, out=None, dedup_roots=False, rng="philox",
                  key_rows=True, sort_roots=True, batch=None, align_rows=True, order=None, ptr=True, triplets=False, stage=None,
-                 table_rows=2048, dtype=None):
-        from .sampler import FUSED_MAX_Q, as_rank, key_rows_form, small_rows_form
+                 table_rows=2048, dtype=None, packed_rows=None):
+        from .sampler import FUSED_MAX_Q, as_rank, key_rows_form, packed_rows_form, small_rows_form
+        self.packed, self._unpacked, self._unpacked_step = False, None, -1
         self.half = _half_code(dtype, "StepBuffers", lambda: {
             "ptr=False (segment ids)": not ptr, "triplets=True": triplets, f"stage={stage!r}": stage is not None,
             "key_rows=False (strided rows of table slots)": not key_rows,
@@ -657,6 +664,18 @@ class StepBuffers:
             raise ValueError("StepBuffers(rng='rand_r'): this graph has dead ends (a walk reached a node without out-edges), its "
                              "rand_r stream has to be replayed per batch -- sample_and_gather(..., rng='rand_r') without buffers= "
                              "does that; the buffered step cannot")
+        # packed rows: `_ids` takes the words, `_slot` the escape lists, `nesc` their lengths; nothing else of the buffers changes
+        self.num_nodes = int(csr.num_nodes)
+        fmt = packed_rows_form(self.num_nodes, self.M, self.m, csr.indptr.dtype == torch.int64)
+        why = {"key_rows=False": not key_rows, f"stage={stage!r}": stage is not None, "a 16-bit dtype": bool(self.half),
+               "ptr=False": not self.ptr, "triplets=True": self.triplets, "batch= (many batches per step)": self.batch != self.B,
+               f"no packed form for {self.num_nodes} nodes, num_walks = {self.M}, num_steps = {self.m} (sampler.packed_rows_form)": fmt is None}
+        if packed_rows and any(why.values()):
+            raise ValueError("StepBuffers(packed_rows=True): " + "; ".join(k for k, v in why.items() if v))
+        self.packed = packed_rows is not False and not any(why.values())
+        if self.packed:
+            self.nesc = torch.empty(n, dtype=torch.int32, device=dev)
+            self._unpack_flags = torch.zeros(4, dtype=torch.int32, device=dev)
         if rng == "rand_r":      # the rows' places in the reference's sequential stream (subgacc_rng_positions), per step
             self.rng_pos = torch.empty(n, dtype=torch.int32, device=dev)
             self.rng_seed = torch.empty(n, dtype=torch.int32, device=dev)
@@ -696,6 +715,41 @@ class StepBuffers:
     def _counts_buffer(self, S, T, dev):
         """stage="counts": the step's C [S, table_rows]"""
         return torch.empty((S, T), dtype=torch.float32, device=dev)
+
+    # the rows of the step: the buffers themselves, or -- packed -- the planes they are unpacked into when somebody looks
+    @property
+    def ids(self):
+        return self._rows()[0] if self.packed else self._ids
+
+    @ids.setter
+    def ids(self, t):
+        self._ids = t
+
+    @property
+    def slot(self):
+        return self._rows()[1] if self.packed else self._slot
+
+    @slot.setter
+    def slot(self, t):
+        self._slot = t
+
+    def _rows(self):
+        """(ids, keys) of a packed step as subgacc_walk_spg(uniq_table=NULL) writes them: unpacked once per step, on the current stream"""
+        if self._unpacked is None:
+            self._unpacked = (torch.empty_like(self._ids), torch.empty_like(self._slot))
+        sid = getattr(self, "step_id", 0)
+        if sid and self._unpacked_step != sid:
+            ids, keys = self._unpacked
+            check(lib().subgacc_unpack_packed_rows(ptr(self._ids), ptr(self._slot), ptr(self.nsize), ptr(self.nesc), self.n, self.stride,
+                                                   self.num_nodes, self.M, self.m, ptr(ids), ptr(keys), ptr(self._unpack_flags),
+                                                   stream_ptr()))
+            self._unpacked_step = sid
+            # an escape without a key in its row's list (flags[3] & 2) cannot come from the packed walk, which writes list and length
+            # together: like the join's guards that sound rows cannot reach (_checked above), the unpack's word is read under
+            # SUBGACC_DEBUG=1 only (one host sync) and never in a capture
+            if _DEBUG_FLAGS and not torch.cuda.is_current_stream_capturing() and int(self._unpack_flags[3].item()) & 2:
+                raise _lib.SubgAccError("packed rows: an escape at or beyond its row's nesc (the escape list does not match the row)")
+        return self._unpacked
 
 
 class _FitStepBuffers(StepBuffers):
@@ -737,10 +791,15 @@ def _dedup_tick(bufs):
 
 def _step_sets(csr, bufs, cfg, rr, step_id):
     """the SampledSets of a buffered step: views of the step's buffers, lazily resolved"""
-    from .sampler import SampledSets
+    from .sampler import PackedStepSets, SampledSets
     kr = bufs.keyrows
-    sets = SampledSets(bufs.nsize, None, bufs.ids, None, None, None, bufs.M, bufs.m, bufs.stride, None)
-    sets.slot, sets.table, sets.capacity, sets.strided = bufs.slot, bufs.table, (0 if kr else bufs.capacity), True
+    if bufs.packed:     # the rows are unpacked when somebody looks at them (sets.ids / sets.slot), not here
+        sets = PackedStepSets(bufs.nsize, None, None, None, None, None, bufs.M, bufs.m, bufs.stride, None)
+        sets._bufs = bufs
+    else:
+        sets = SampledSets(bufs.nsize, None, bufs.ids, None, None, None, bufs.M, bufs.m, bufs.stride, None)
+        sets.slot = bufs.slot
+    sets.table, sets.capacity, sets.strided = bufs.table, (0 if kr else bufs.capacity), True
     if kr:
         sets.keyrows, sets.key64, sets.small_rows = True, bufs.key64, bool(getattr(bufs, "small", False))
         # number() registers the keys of the rows as they stand in the buffers (root dedup: the rows of repeated endpoints are
@@ -874,9 +933,10 @@ def _buffered_step(csr, e, bufs, seed, out, fit=False):
         check(L.subgacc_rng_positions(cfg, ptr(csr.indptr), csr.num_nodes, ptr(bufs.roots), n, 1, 0, ptr(bufs.rng_pos),
                                       ptr(bufs.rng_seed), ptr(bufs.rng_ws), bufs.rng_ws.numel(), st))
     with _timed("walk_sets"):         # (root dedup: the list selects the first occurrences, the other rows are passed over)
-        _walk(cfg, csr, bufs.roots, n, flags, st, "keys_small" if small else "keys64" if bufs.key64 else "fused", ids=bufs.ids, payload=bufs.slot,
+        _walk(cfg, csr, bufs.roots, n, flags, st,
+              "keys_packed" if bufs.packed else "keys_small" if small else "keys64" if bufs.key64 else "fused", ids=bufs._ids, payload=bufs._slot,
               nsize=bufs.nsize, rng=(bufs.rng_pos, bufs.rng_seed) if rr else (None, None), table=bufs.table,
-              capacity=0 if kr else bufs.capacity, work=work, select=bufs.dedup)
+              capacity=0 if kr else bufs.capacity, work=work, select=bufs.dedup, nesc=bufs.nesc if bufs.packed else None)
     if bufs.dedup:
         own, partner = bufs.own, bufs.partner
     elif bufs.triplets:
@@ -902,9 +962,13 @@ def _buffered_step(csr, e, bufs, seed, out, fit=False):
         check(L.subgacc_unpack_lp(ptr(keys), bufs.capacity, None, M, m, None, None, ptr(bufs.feat), 1, st))
         kind, payload = JOIN_SFPTR, dict(table=bufs.feat, table_rows=bufs.capacity + 1, k=k)
     xz = _out_view(out if out is not None else bufs.out, dev, k, worst=S * bufs.Q, dtype=bufs.dtype)
-    rows = dict(row_len=bufs.nsize, n_rows=n, row_stride=bufs.stride, ids=bufs.ids, payload=bufs.slot, own=own, partner=partner, S=S,
+    rows = dict(row_len=bufs.nsize, n_rows=n, row_stride=bufs.stride, ids=bufs._ids, payload=bufs._slot, own=own, partner=partner, S=S,
                 seg=bufs.seg, pair_block=PB, flags=flags)
-    if bufs.half:       # 16-bit rows (StepBuffers(dtype=): 32-bit key rows, segment pointers)
+    if bufs.packed:     # one word per member and the escape lists: the same rows of xz
+        with _timed("sjoin_fill"):
+            check(L.subgacc_sjoin_fill_packed(ctypes.byref(_lib.join_desc(JOIN_ROWS, kind, out_xz=xz, **rows, **payload)), ptr(bufs.nesc),
+                                              bufs.num_nodes, st))
+    elif bufs.half:       # 16-bit rows (StepBuffers(dtype=): 32-bit key rows, segment pointers)
         with _timed("sjoin_fill_half"):
             check(L.subgacc_sjoin_fill_half(ctypes.byref(_lib.join_desc(JOIN_ROWS, kind, **rows, **payload)), bufs.half, ptr(xz), st))
     else:

@@ -25,7 +25,7 @@ for f in glob.glob(os.path.join(out, "*", "*", "*counter_collection.csv")):
             acc[k.split("(")[0].replace("void subgacc::", "").replace("subgacc::", "")][r["Counter_Name"]].append(float(r["Counter_Value"]))
 table = ["kernel,launches,FETCH_SIZE,WRITE_SIZE,TCC_REQ_sum,TCC_HIT_sum,TCC_MISS_sum,hbm_bytes_per_launch=(2*FETCH_SIZE+WRITE_SIZE)*1024"]
 rows = []
-JOIN_KERNELS = ("sjoin_pair_kernel", "sjoin_keypair_kernel", "sjoin_f64pair_kernel")      # the fill kernel of a step, whichever form
+JOIN_KERNELS = ("sjoin_pair_kernel", "sjoin_keypair_kernel", "sjoin_f64pair_kernel", "sjoin_packpair_kernel")      # the fill kernel of a step, whichever form
 for k, c in acc.items():
     m = {n: sum(v) / len(v) for n, v in c.items()}
     if "FETCH_SIZE" in m and "WRITE_SIZE" in m:
