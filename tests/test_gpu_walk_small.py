@@ -71,14 +71,14 @@ def _rows_of(exp, rows):
     return dict(nsize=exp["nsize"][rows], off=np.concatenate([[0], np.cumsum(lens)]), ids=exp["ids"][src], keys=exp["keys"][src])
 
 
-def _launch(csr, q, M, m, rng, pitch=0, work=None, n_work=None):
+def _launch(csr, q, M, m, rng, pitch=0, work=None, n_work=None, cap_root=True):
     """one call of subgacc_walk_keyrows_small into poisoned, guarded outputs -> what test_gpu_walk_rows_edges._check reads"""
     from surel_plus_amd import _lib as L, sampler
     lib, ptr, st = L.lib(), L.ptr, L.stream_ptr()
     n, Q = len(q), M * m + 1
     P = pitch if pitch > 0 else Q
     d_q = R._dev(np.asarray(q, dtype=np.int32))
-    cfg = sampler.make_cfg(csr, M, m, -1, SEED, rng, records=False, row_pitch=pitch)
+    cfg = sampler.make_cfg(csr, M, m, -1, SEED, rng, cap_root_degree=cap_root, records=False, row_pitch=pitch)
     rp, rs = sampler._rng_positions(lib, cfg, csr, d_q, n, 1, 0, st)
     w_ids, ids = R._guarded(n * P, torch.int32)
     w_pay, pay = R._guarded(n * P, torch.int32)
