@@ -14,6 +14,8 @@
 #ifndef SG_DEV_HOOKS
 #define SG_HOOK_KERNEL_ENTRY()
 #define SG_HOOK_STAMP(k)
+#define SG_HOOK_CLOCK_PARAM     // a kernel's phase function that stamps: the stamps' clock as its last parameter / argument
+#define SG_HOOK_CLOCK_ARG
 #define SG_HOOK_RSTAMP(k)
 #define SG_HOOK_BEFORE_HOP(cur, w, s)
 #define SG_HOOK_LOAD_ROW(I64, indptr, cur, b, d) load_row<I64>(indptr, cur, b, d)

@@ -243,7 +243,7 @@ __device__ __forceinline__ void finish_row(int32_t *__restrict__ row_ids, const 
         if (r >= ns) continue;
         uint32_t f = (uint32_t)(mix64(key[u]) >> 40) & (kFinFold - 1);
         bool done = false;
-        for (int p = 0; p < 16; ++p) {
+        for (int p = 0; p < 16; ++p) {   // (fold_insert of uniq_table.hpp, written out: called here, every finish_rows_kernel came out as different instructions)
             unsigned long long cur = wk[f];
             if (cur == kEmptyKey) cur = atomicCAS(&wk[f], kEmptyKey, key[u]);
             if (cur == kEmptyKey || cur == key[u]) {

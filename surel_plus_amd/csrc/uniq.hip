@@ -210,7 +210,7 @@ __global__ __launch_bounds__(256) void uniq_insert_kernel(UniqTable t, const uin
         const unsigned long long tag = (unsigned long long)(tag_base + e);
         uint32_t h = (uint32_t)(mix64(key) >> 40) & (kInsLds - 1);
         bool done = false;
-        for (int p = 0; p < 16; ++p) {
+        for (int p = 0; p < 16; ++p) {   // (fold_insert of uniq_table.hpp, written out: called here, the kernel came out as different instructions)
             unsigned long long cur = lk[h];
             if (cur == kEmptyKey) cur = atomicCAS(&lk[h], kEmptyKey, key);
             if (cur == kEmptyKey || cur == key) {

@@ -1,5 +1,6 @@
 // uniq_table.hpp -- the HBM open-addressing table of distinct LP rows (key -> min element position, id).
-// Shared by uniq.hip (insert / number / translate) and walk.hip (insert fused into the set compaction).
+// Shared by uniq.hip (insert / number / translate), compact.hip (insert fused into the set compaction) and the walk kernels
+// (insert fused into the walk's epilogue: walk.hip, walk_pipe.hip, walk_rows.hip).
 #pragma once
 #include "common.hpp"
 #include "blockscan.hpp"
@@ -40,6 +41,26 @@ __device__ __forceinline__ uint64_t mix64(uint64_t x) {
 template <int BITS>
 __device__ __forceinline__ uint32_t fold_hash(unsigned long long key) {
     return (((uint32_t)key * 0x9E3779B1u) ^ ((uint32_t)(key >> 32) * 0x85EBCA77u)) >> (32 - BITS);
+}
+
+// One insert into such an LDS fold table of mask + 1 slots (keys[] = kEmptyKey, tags[] = all ones when empty), from slot `home` on:
+// claim-or-find the key within 16 probes, lower its tag, return the slot -- or -1: the neighbourhood is crowded and the caller
+// takes the key to the HBM table itself.
+template <class TagT>
+__device__ __forceinline__ int32_t fold_insert(unsigned long long *keys, TagT *tags, uint32_t mask, uint32_t home, unsigned long long key,
+                                               TagT tag) {
+    uint32_t f = home;
+#pragma unroll 1   // (a loop, as where it was written out: with the `return` inside the compiler otherwise unrolls all 16 probes)
+    for (int p = 0; p < 16; ++p) {
+        unsigned long long cur = keys[f];
+        if (cur == kEmptyKey) cur = atomicCAS(&keys[f], kEmptyKey, key);
+        if (cur == kEmptyKey || cur == key) {
+            if (tags[f] > tag) atomicMin(&tags[f], tag);
+            return (int32_t)f;
+        }
+        f = (f + 1) & mask;
+    }
+    return -1;
 }
 
 constexpr int kInsItems = 8;

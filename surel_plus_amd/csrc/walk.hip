@@ -19,50 +19,215 @@
 // RNG: SUBGACC_RNG_RAND_R reproduces glibc rand_r's single sequential stream (the reference at
 // nthread=1): the LCG x -> a*x+c is affine, so a lane jumps straight to the stream position of its
 // (root, walk) in O(log k).  SUBGACC_RNG_PHILOX is Philox4x32-10 keyed by (seed; root id, walk, step).
+//
+// In this file: the general kernel walk_sets_kernel<IDX64, RNG, SPG> -- walk and first-visit ranking in its body, the fused-row
+// epilogue of SPG mode as walk_sets_spg_epilogue -- and the launcher of EVERY walk: WalkLaunch / launch_walk, which hands a launch to
+// walk_pipe.hip or walk_rows.hip where they take it, behind the subgacc_walk_* entry points.  What a launch is handed ready-made
+// (key shift, rand_r stream positions, hop records): walk_prep.hip; the compaction of the staged sets and rows: compact.hip.
 #include "common.hpp"
 #include "blockscan.hpp"
 #include "uniq_table.hpp"
 #include "walk_common.hpp"
+#include "waveops.hpp"
+#include "row_sort.hpp"
 #include "../../include/subgacc_packed.h"
 #include <stdlib.h>
 
 namespace subgacc {
 
-template <bool IDX64>
-__global__ void rng_calls_kernel(const void *__restrict__ indptr, const int32_t *__restrict__ query, int64_t n,
-                                 int64_t num_nodes, int M, int m, int wo, int cap, int32_t *__restrict__ calls) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    int64_t beg, deg = 0;
-    if ((uint64_t)(int64_t)query[i] < (uint64_t)num_nodes) load_row<IDX64>(indptr, query[i], beg, deg);   // else: the walk kernel flags it
-    if (cap && deg > kNeighCap) deg = kNeighCap;
-    int32_t c = 0;
-    if (deg > 0) c = wo ? ((deg > M ? M : 0) + M * (m - 1)) : M * m;
-    calls[i] = c;
-}
-
-// libgomp static schedule: the first n%T threads own ceil(n/T) iterations
-__global__ void rng_positions_kernel(const int64_t *__restrict__ calls_excl, int64_t n, int32_t streams,
-                                     uint64_t calls_before, uint32_t seed, uint32_t *__restrict__ pos,
-                                     uint32_t *__restrict__ sd) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int64_t q = n / streams, r = n % streams;
-    int64_t t, lo;
-    if (i < r * (q + 1)) {
-        t = i / (q + 1);
-        lo = t * (q + 1);
-    } else {
-        t = r + (q > 0 ? (i - r * (q + 1)) / q : 0);
-        lo = r * (q + 1) + (t - r) * q;
+// ------------------------------------------------------------------------------ the fused epilogue
+// SPG mode: the set leaves as a finished SpG row.
+// (1) fold the set's LP keys (a few dozen distinct rows) and register them in the HBM table of distinct rows
+//     with tag = (global root index)*stride + first-visit order, which orders first occurrences exactly like the
+//     reference's sequential pass (subg_acc.c:957-978); (2) bucket-sort the members by node id in the LDS the
+//     walk tables occupied (random_walks.py:79-80; the sort's pieces: row_sort.hpp) and write them to their sorted position.
+// The tail of walk_sets_kernel<SPG = true>, which hands over its LDS arrays (the walk tables pk / keys / minq, the ranking's inv, the
+// fold table fk / ft / fs, the 16 reduction words) and what it knows of the root; vmin / vmax = the id range this lane visited.
+// A `return` in here (the dev builds' stamps) ends the kernel.
+__device__ __forceinline__ void walk_sets_spg_epilogue(unsigned long long *pk, int32_t *keys, uint32_t *minq, const uint16_t *inv,
+                                                       unsigned long long *fk, uint32_t *ft, int32_t *fs, int32_t *red, const WalkArgs a,
+                                                       const int64_t i, const int32_t root, const int64_t obase, const unsigned long long lead,
+                                                       const bool need_rank, int32_t ns, int32_t total, int32_t vmin, int32_t vmax,
+                                                       const int tid SG_HOOK_CLOCK_PARAM) {
+    [[maybe_unused]] constexpr bool SPG = true;   // (read by the dev builds' stamps, like a, i and root)
+    const int T = a.T;
+    vmin = wave_red_min_i32(vmin);
+    vmax = wave_red_max_i32(vmax);
+    if ((tid & (kWave - 1)) == 0) {   // read behind the barrier in front of stamp 3
+        red[tid / kWave] = vmin;
+        red[4 + tid / kWave] = vmax;
     }
-    uint64_t c = (uint64_t)(calls_excl[i] - calls_excl[lo]);
-    if (streams == 1) c += calls_before;
-    // three LCG steps per rand_r call; the LCG has period 2^32.  The pair leaves NORMALISED: (state of the stream at the root's
-    // first draw, 0 further steps) names the same point of the stream as (seed + t, 3c) and spares every workgroup of the walk
-    // kernels the 32-round jump from the seed (they compute lcg_jump(seed, pos + ...): 0 rounds for pos = 0)
-    pos[i] = 0u;
-    sd[i] = lcg_jump(seed + (uint32_t)t, (uint32_t)(3ull * c));
+    const unsigned long long tag0 = (unsigned long long)((a.root_base + i) * (int64_t)a.pitch);
+    int32_t idv[kSpgPerLane], slv[kSpgPerLane];
+    bool ok[kSpgPerLane];
+    int mycount = 0;
+    // The lane's members are handled stage by stage, two at a time, not one after the other: a stage issues its LDS
+    // reads for both before either is consumed, so their latencies overlap (a workgroup's lifetime is a chain of such
+    // round trips; 8 workgroups per CU is all the latency hiding there is).
+    constexpr int kIlp = 2;   // members in flight per stage (4 would need more than the 64 VGPRs that keep 8 workgroups per CU)
+#pragma unroll
+    for (int u0 = 0; u0 < kSpgPerLane; u0 += kIlp) {
+        unsigned long long mkey[kIlp], fcur[kIlp];
+        uint32_t mtag[kIlp], mf[kIlp], ftag[kIlp];
+#pragma unroll
+        for (int v = 0; v < kIlp; ++v) {   // stage 1: the member (by rank in bucket mode, else straight from its slot)
+            const int u = u0 + v;
+            const int x = tid + u * kWalkThreads;
+            int h = x;
+            if (need_rank) {
+                ok[u] = x < ns;
+                h = ok[u] ? (int)inv[x] : 0;
+                mtag[v] = (uint32_t)x;
+                idv[u] = keys[h];
+            } else {
+                ok[u] = x < T;
+                h = ok[u] ? x : 0;
+                idv[u] = keys[h];
+                mtag[v] = minq[h];
+                ok[u] = ok[u] && idv[u] != -1;
+            }
+            mkey[v] = pk[h];
+        }
+#pragma unroll
+        for (int v = 0; v < kIlp; ++v) {   // stage 2: key, fold slot, first probe
+            const int u = u0 + v;
+            mkey[v] |= (mtag[v] == 0 ? lead : 0ull);               // the root is rank 0 / visit 0
+            mf[v] = fold_hash<kSpgFoldBits>(mkey[v]);
+            slv[u] = -1;
+            if (!ok[u]) idv[u] = 0;
+            mycount += ok[u] ? 1 : 0;
+        }
+#pragma unroll
+        for (int v = 0; v < kIlp; ++v) {
+            fcur[v] = fk[mf[v]];
+            ftag[v] = ft[mf[v]];
+        }
+#pragma unroll
+        for (int v = 0; v < kIlp; ++v) {   // stage 3: a set holds a few dozen distinct keys -> mostly a hit right away
+            const int u = u0 + v;
+            if (!ok[u]) continue;
+            const unsigned long long key = mkey[v];
+            const uint32_t tagoff = mtag[v];
+            if (fcur[v] == key) {
+                // most lanes meet a tag that is already smaller: the plain read (stale only towards larger values)
+                // spares the same-address atomic storm
+                if (ftag[v] > tagoff) atomicMin(&ft[mf[v]], tagoff);
+                slv[u] = -2 - (int32_t)mf[v];       // resolved to the HBM slot after the fold table is flushed
+                continue;
+            }
+            const int32_t f = fold_insert(fk, ft, kSpgFold - 1, mf[v], key, tagoff);
+            slv[u] = f >= 0 ? -2 - f : uniq_global_insert(a.table, key, tag0 + (unsigned long long)tagoff, a.flags);
+        }
+    }
+    if (!need_rank) {
+        mycount = wave_red_add_i32(mycount);
+        if ((tid & (kWave - 1)) == 0) atomicAdd(&red[8], mycount);
+    }
+    __syncthreads();   // every lane holds its members in registers: the walk tables are free to be re-used
+    SG_HOOK_STAMP(3);
+    if (!need_rank) total = ns = red[8];
+    if (tid == 0) {
+        a.nsize[i] = ns;
+        if (total > a.stride) atomicAdd(&a.flags[1], 1);
+    }
+    const int32_t mn = min(min(red[0], red[1]), min(red[2], red[3]));
+    const int32_t mx = max(max(red[4], red[5]), max(red[6], red[7]));
+    unsigned long long *A = pk;                 // [ns] (id << 32 | slot) grouped by bucket
+    int32_t *start = keys;                      // [B+1]
+    int32_t *cursor = keys + (T / 4) + 1;       // [B]      B <= min(T/4, 256)
+    int B, bshift;
+    rows_bucket_geometry(T, kWalkThreads, ns, mn, mx, B, bshift);
+    if (tid < B) start[tid] = 0;
+    for (int s2 = tid; s2 < kSpgFold; s2 += kWalkThreads)    // flush the fold table to HBM (latency overlaps the sort)
+        if (fk[s2] != kEmptyKey) fs[s2] = SG_HOOK_FLUSH_SLOT(s2, uniq_global_insert(a.table, fk[s2], tag0 + ft[s2], a.flags));
+    __syncthreads();
+    SG_HOOK_STAMP(4);
+    uint32_t bk[kSpgPerLane];
+#pragma unroll
+    for (int u = 0; u < kSpgPerLane; ++u) {
+        bk[u] = (uint32_t)(idv[u] - mn) >> bshift;        // (id - mn) < 2^Ls and Ls >= logb unless the row is a single id
+        if (ok[u]) atomicAdd(&start[bk[u]], 1);
+        if (slv[u] <= -2) slv[u] = fs[-2 - slv[u]];
+    }
+    __syncthreads();
+    SG_HOOK_STAMP(5);
+    // counts -> offsets of the B <= 256 buckets (red[4..7] take the waves' largest counts: the id range is in registers); a lane's own
+    // offset is also the bucket's cursor of the short path below
+    const int32_t maxc = rows_level1_scan<kWalkThreads>(start, red, B, tid);
+    if (tid < B) cursor[tid] = start[tid];
+    __syncthreads();
+    SG_HOOK_STAMP(6);
+    // A crowded bucket -- a set whose ids sit in one community of a graph with id locality -- made the ranking by counting below
+    // quadratic (walk_rows.hip met the same, DESIGN.md section 4.10).  The same second level here: bucket b gets as many sub-buckets
+    // as it has members (sub = offset inside b's id window scaled by b's count), so that start[b] + sub is a monotone map of the ids
+    // onto [0, ns) that follows the set's own distribution, and the counting runs over ~1 member.  Evenly spread ids keep the
+    // short path.  The level-2 counters (16 bits each) live behind the level-1 offsets and cursors, in the dead id table.
+    constexpr int kFineAbove = 12, CW = 2;
+    const int W2 = (ns + 2) / 2 + 1;
+    uint32_t *cnt2 = (uint32_t *)(keys + T / 2 + 2);                     // [W2] <= T/2 - 2 words (W2 <= 0.4 T + 2)
+    int blo[kSpgPerLane], bhi[kSpgPerLane];
+    if (!(maxc > kFineAbove && W2 <= CW * kWalkThreads && W2 <= T / 2 - 2)) {
+#pragma unroll
+        for (int u = 0; u < kSpgPerLane; ++u)
+            if (ok[u]) A[atomicAdd(&cursor[bk[u]], 1)] = ((unsigned long long)(uint32_t)idv[u] << 32) | (uint32_t)slv[u];
+#pragma unroll
+        for (int u = 0; u < kSpgPerLane; ++u) {   // bucket bounds of all the lane's members (overlapping reads)
+            blo[u] = ok[u] ? start[bk[u]] : 0;
+            bhi[u] = ok[u] ? start[bk[u] + 1] : 0;
+        }
+    } else {
+        for (int x = tid; x < W2; x += kWalkThreads) cnt2[x] = 0u;
+        __syncthreads();
+        int32_t arr[kSpgPerLane];
+#pragma unroll
+        for (int u = 0; u < kSpgPerLane; ++u) {      // (bk[u] becomes the member's sub-bucket)
+            arr[u] = 0;
+            if (!ok[u]) continue;
+            const RowsPart p = rows_part(start, (uint32_t)(idv[u] - mn), bk[u], bshift, 1u);
+            bk[u] = p.lo1 + p.sub;
+            arr[u] = (int32_t)rows_count16(cnt2, bk[u]);
+        }
+        __syncthreads();
+        rows_level2_scan<kWalkThreads, CW>(cnt2, W2, red, tid);   // the ns + 1 level-2 counters -> offsets <= ns < 2^16, in place
+        __syncthreads();
+        const uint16_t *off2 = (const uint16_t *)cnt2;
+#pragma unroll
+        for (int u = 0; u < kSpgPerLane; ++u) {
+            blo[u] = ok[u] ? off2[bk[u]] : 0;
+            bhi[u] = ok[u] ? off2[bk[u] + 1] : 0;
+            if (ok[u]) A[blo[u] + arr[u]] = ((unsigned long long)(uint32_t)idv[u] << 32) | (uint32_t)slv[u];
+        }
+    }
+    __syncthreads();
+    SG_HOOK_STAMP(7);
+    // order inside a bucket = number of smaller ids in it -> final position in the row.  The sorted row is assembled
+    // in LDS (ids over the dead minq table, slots behind A) and leaves with consecutive lanes on consecutive words.
+    int32_t *fin_id = (int32_t *)minq;                 // [ns] <= T
+    int32_t *fin_sl = (int32_t *)(pk + a.stride + 1);   // [ns]: A occupies pk[0..ns), ns <= stride; (T - stride - 1) * 8 >= 4 * stride
+    const bool staged = (int64_t)(T - a.stride - 1) * 8 >= (int64_t)4 * a.stride;
+    const uint32_t *Ahi = (const uint32_t *)A;
+#pragma unroll
+    for (int u = 0; u < kSpgPerLane; ++u)
+        if (ok[u]) {
+            const int lo = blo[u], hi = bhi[u];
+            int rank = 0;       // ids are distinct within a set: the high word of A decides
+            for (int t2 = lo; t2 < hi; ++t2) rank += (Ahi[2 * t2 + 1] < (uint32_t)idv[u]) ? 1 : 0;
+            if (staged) {
+                fin_id[lo + rank] = idv[u];
+                fin_sl[lo + rank] = slv[u];
+            } else {
+                a.set_ids[obase + lo + rank] = idv[u];
+                a.set_slot[obase + lo + rank] = slv[u];
+            }
+        }
+    if (staged) {
+        __syncthreads();
+        for (int x = tid; x < ns; x += kWalkThreads) {
+            a.set_ids[obase + x] = fin_id[x];
+            a.set_slot[obase + x] = fin_sl[x];
+        }
+    }
+    SG_HOOK_STAMP(8);
 }
 
 // ------------------------------------------------------------------------------ the walk kernel
@@ -249,17 +414,6 @@ __global__ __launch_bounds__(kWalkThreads, SG_WALK_MINW) __attribute__((amdgpu_n
             atomicAdd(&pk[h], 1ull << ((m - 1 - s) * a.shift));
         }
     }
-    if (SPG) {
-#pragma unroll
-        for (int d = kWave / 2; d > 0; d >>= 1) {
-            vmin = min(vmin, __shfl_xor(vmin, d, kWave));
-            vmax = max(vmax, __shfl_xor(vmax, d, kWave));
-        }
-        if ((tid & (kWave - 1)) == 0) {
-            red[tid / kWave] = vmin;
-            red[4 + tid / kWave] = vmax;
-        }
-    }
     __syncthreads();
     SG_HOOK_STAMP(2);
 
@@ -306,458 +460,13 @@ __global__ __launch_bounds__(kWalkThreads, SG_WALK_MINW) __attribute__((amdgpu_n
         }
         return;
     }
-
-    // ================= SPG mode: the set leaves as a finished SpG row =================
-    // (1) fold the set's LP keys (a few dozen distinct rows) and register them in the HBM table of distinct rows
-    //     with tag = (global root index)*stride + first-visit order, which orders first occurrences exactly like the
-    //     reference's sequential pass (subg_acc.c:957-978); (2) bucket-sort the members by node id in the LDS the
-    //     walk tables occupied (random_walks.py:79-80) and write them to their sorted position.
-    const unsigned long long tag0 = (unsigned long long)((a.root_base + i) * (int64_t)a.pitch);
-    int32_t idv[kSpgPerLane], slv[kSpgPerLane];
-    bool ok[kSpgPerLane];
-    int mycount = 0;
-    // The lane's members are handled stage by stage, two at a time, not one after the other: a stage issues its LDS
-    // reads for both before either is consumed, so their latencies overlap (a workgroup's lifetime is a chain of such
-    // round trips; 8 workgroups per CU is all the latency hiding there is).
-    constexpr int kIlp = 2;   // members in flight per stage (4 would need more than the 64 VGPRs that keep 8 workgroups per CU)
-#pragma unroll
-    for (int u0 = 0; u0 < kSpgPerLane; u0 += kIlp) {
-        unsigned long long mkey[kIlp], fcur[kIlp];
-        uint32_t mtag[kIlp], mf[kIlp], ftag[kIlp];
-#pragma unroll
-        for (int v = 0; v < kIlp; ++v) {   // stage 1: the member (by rank in bucket mode, else straight from its slot)
-            const int u = u0 + v;
-            const int x = tid + u * kWalkThreads;
-            int h = x;
-            if (need_rank) {
-                ok[u] = x < ns;
-                h = ok[u] ? (int)inv[x] : 0;
-                mtag[v] = (uint32_t)x;
-                idv[u] = keys[h];
-            } else {
-                ok[u] = x < T;
-                h = ok[u] ? x : 0;
-                idv[u] = keys[h];
-                mtag[v] = minq[h];
-                ok[u] = ok[u] && idv[u] != -1;
-            }
-            mkey[v] = pk[h];
-        }
-#pragma unroll
-        for (int v = 0; v < kIlp; ++v) {   // stage 2: key, fold slot, first probe
-            const int u = u0 + v;
-            mkey[v] |= (mtag[v] == 0 ? lead : 0ull);               // the root is rank 0 / visit 0
-            mf[v] = fold_hash<kSpgFoldBits>(mkey[v]);
-            slv[u] = -1;
-            if (!ok[u]) idv[u] = 0;
-            mycount += ok[u] ? 1 : 0;
-        }
-#pragma unroll
-        for (int v = 0; v < kIlp; ++v) {
-            fcur[v] = fk[mf[v]];
-            ftag[v] = ft[mf[v]];
-        }
-#pragma unroll
-        for (int v = 0; v < kIlp; ++v) {   // stage 3: a set holds a few dozen distinct keys -> mostly a hit right away
-            const int u = u0 + v;
-            if (!ok[u]) continue;
-            const unsigned long long key = mkey[v];
-            const uint32_t tagoff = mtag[v];
-            if (fcur[v] == key) {
-                // most lanes meet a tag that is already smaller: the plain read (stale only towards larger values)
-                // spares the same-address atomic storm
-                if (ftag[v] > tagoff) atomicMin(&ft[mf[v]], tagoff);
-                slv[u] = -2 - (int32_t)mf[v];       // resolved to the HBM slot after the fold table is flushed
-                continue;
-            }
-            uint32_t f = mf[v];
-            bool done = false;
-            for (int p = 0; p < 16; ++p) {
-                unsigned long long cur = fk[f];
-                if (cur == kEmptyKey) cur = atomicCAS(&fk[f], kEmptyKey, key);
-                if (cur == kEmptyKey || cur == key) {
-                    if (ft[f] > tagoff) atomicMin(&ft[f], tagoff);
-                    slv[u] = -2 - (int32_t)f;
-                    done = true;
-                    break;
-                }
-                f = (f + 1) & (kSpgFold - 1);
-            }
-            if (!done) slv[u] = uniq_global_insert(a.table, key, tag0 + (unsigned long long)tagoff, a.flags);
-        }
-    }
-    if (!need_rank) {
-#pragma unroll
-        for (int d = kWave / 2; d > 0; d >>= 1) mycount += __shfl_xor(mycount, d, kWave);
-        if ((tid & (kWave - 1)) == 0) atomicAdd(&red[8], mycount);
-    }
-    __syncthreads();   // every lane holds its members in registers: the walk tables are free to be re-used
-    SG_HOOK_STAMP(3);
-    if (!need_rank) total = ns = red[8];
-    if (tid == 0) {
-        a.nsize[i] = ns;
-        if (total > a.stride) atomicAdd(&a.flags[1], 1);
-    }
-    const int32_t mn = min(min(red[0], red[1]), min(red[2], red[3]));
-    const int32_t mx = max(max(red[4], red[5]), max(red[6], red[7]));
-    unsigned long long *A = pk;                 // [ns] (id << 32 | slot) grouped by bucket
-    int32_t *start = keys;                      // [B+1]
-    int32_t *cursor = keys + (T / 4) + 1;       // [B]      B <= min(T/4, 256)
-    int logb = 0;
-    while ((1 << logb) < ns && (2 << logb) <= T / 4 && (2 << logb) <= kWalkThreads) ++logb;
-    const int B = 1 << logb;
-    const uint32_t range = (uint32_t)(mx - mn) + 1u;
-    const int Ls = (range <= 1u) ? 0 : (32 - __builtin_clz(range - 1u));
-    const int bshift = Ls > logb ? Ls - logb : 0;
-    if (tid < B) cursor[tid] = 0;
-    for (int s2 = tid; s2 < kSpgFold; s2 += kWalkThreads)    // flush the fold table to HBM (latency overlaps the sort)
-        if (fk[s2] != kEmptyKey) fs[s2] = SG_HOOK_FLUSH_SLOT(s2, uniq_global_insert(a.table, fk[s2], tag0 + ft[s2], a.flags));
-    __syncthreads();
-    SG_HOOK_STAMP(4);
-    uint32_t bk[kSpgPerLane];
-#pragma unroll
-    for (int u = 0; u < kSpgPerLane; ++u) {
-        bk[u] = (uint32_t)(idv[u] - mn) >> bshift;        // (id - mn) < 2^Ls and Ls >= logb unless the row is a single id
-        if (ok[u]) atomicAdd(&cursor[bk[u]], 1);
-        if (slv[u] <= -2) slv[u] = fs[-2 - slv[u]];
-    }
-    __syncthreads();
-    SG_HOOK_STAMP(5);
-    int32_t maxc;
-    {   // exclusive scan over the B <= 256 buckets, one bucket per lane: wave scan, then the wave totals through LDS
-        const int32_t c = tid < B ? cursor[tid] : 0;
-        int32_t inc = c, mc = c;
-#pragma unroll
-        for (int dd = 1; dd < kWave; dd <<= 1) {
-            const int32_t t2 = __shfl_up(inc, dd, kWave);
-            if ((tid & (kWave - 1)) >= dd) inc += t2;
-            mc = max(mc, __shfl_xor(mc, dd, kWave));
-        }
-        if ((tid & (kWave - 1)) == kWave - 1) red[12 + tid / kWave] = inc, red[4 + tid / kWave] = mc;   // (the id range is in registers)
-        __syncthreads();
-        int32_t base = 0;
-#pragma unroll
-        for (int w2 = 0; w2 < kWalkThreads / kWave - 1; ++w2) base += w2 < tid / kWave ? red[12 + w2] : 0;      // (spelled out: as a loop over tid / 64 the compiler vectorises it)
-        maxc = max(max(red[4], red[5]), max(red[6], red[7]));
-        const int32_t excl = base + inc - c;
-        if (tid < B) {
-            start[tid] = excl;
-            cursor[tid] = excl;
-        }
-        if (tid == B - 1) start[B] = excl + c;
-    }
-    __syncthreads();
-    SG_HOOK_STAMP(6);
-    // A crowded bucket -- a set whose ids sit in one community of a graph with id locality -- made the ranking by counting below
-    // quadratic (walk_rows.hip met the same, DESIGN.md section 4.10).  The same second level here: bucket b gets as many sub-buckets
-    // as it has members (sub = offset inside b's id window scaled by b's count), so that start[b] + sub is a monotone map of the ids
-    // onto [0, ns) that follows the set's own distribution, and the counting runs over ~1 member.  Evenly spread ids keep the
-    // short path.  The level-2 counters (16 bits each) live behind the level-1 offsets and cursors, in the dead id table.
-    constexpr int kFineAbove = 12, CW = 2;
-    const int W2 = (ns + 2) / 2 + 1;
-    uint32_t *cnt2 = (uint32_t *)(keys + T / 2 + 2);                     // [W2] <= T/2 - 2 words (W2 <= 0.4 T + 2)
-    int blo[kSpgPerLane], bhi[kSpgPerLane];
-    if (!(maxc > kFineAbove && W2 <= CW * kWalkThreads && W2 <= T / 2 - 2)) {
-#pragma unroll
-        for (int u = 0; u < kSpgPerLane; ++u)
-            if (ok[u]) A[atomicAdd(&cursor[bk[u]], 1)] = ((unsigned long long)(uint32_t)idv[u] << 32) | (uint32_t)slv[u];
-#pragma unroll
-        for (int u = 0; u < kSpgPerLane; ++u) {   // bucket bounds of all the lane's members (overlapping reads)
-            blo[u] = ok[u] ? start[bk[u]] : 0;
-            bhi[u] = ok[u] ? start[bk[u] + 1] : 0;
-        }
-    } else {
-        for (int x = tid; x < W2; x += kWalkThreads) cnt2[x] = 0u;
-        __syncthreads();
-        int32_t arr[kSpgPerLane];
-#pragma unroll
-        for (int u = 0; u < kSpgPerLane; ++u) {      // (bk[u] becomes the member's sub-bucket)
-            arr[u] = 0;
-            if (!ok[u]) continue;
-            const uint32_t lo1 = (uint32_t)start[bk[u]], kb = (uint32_t)start[bk[u] + 1] - lo1;
-            const uint32_t off = (uint32_t)(idv[u] - mn) - (bk[u] << bshift);                      // < 2^bshift
-            const uint32_t sub = bshift ? __umulhi(off << (32 - bshift), kb) : 0u;                 // floor(off * kb / 2^bshift) < kb
-            bk[u] = lo1 + sub;
-            const uint32_t sh = (bk[u] & 1u) * 16u;
-            arr[u] = (int32_t)((atomicAdd(&cnt2[bk[u] >> 1], 1u << sh) >> sh) & 0xFFFFu);
-        }
-        __syncthreads();
-        {   // exclusive scan of the ns + 1 level-2 counters, in place (offsets <= ns < 2^16): CW consecutive words per lane
-            uint32_t w[CW];
-            int32_t s2 = 0;
-#pragma unroll
-            for (int c = 0; c < CW; ++c) {
-                const int x = tid * CW + c;
-                w[c] = x < W2 ? cnt2[x] : 0u;
-                s2 += (int32_t)((w[c] & 0xFFFFu) + (w[c] >> 16));
-            }
-            int32_t inc = s2;
-#pragma unroll
-            for (int dd = 1; dd < kWave; dd <<= 1) {
-                const int32_t t2 = __shfl_up(inc, dd, kWave);
-                if ((tid & (kWave - 1)) >= dd) inc += t2;
-            }
-            if ((tid & (kWave - 1)) == kWave - 1) red[12 + tid / kWave] = inc;
-            __syncthreads();
-            int32_t run = inc - s2;
-#pragma unroll
-            for (int w2 = 0; w2 < kWalkThreads / kWave - 1; ++w2) run += w2 < tid / kWave ? red[12 + w2] : 0;
-#pragma unroll
-            for (int c = 0; c < CW; ++c) {
-                const int x = tid * CW + c;
-                const uint32_t lo16 = (uint32_t)run;
-                run += (int32_t)(w[c] & 0xFFFFu);
-                const uint32_t hi16 = (uint32_t)run;
-                run += (int32_t)(w[c] >> 16);
-                if (x < W2) cnt2[x] = lo16 | (hi16 << 16);
-            }
-        }
-        __syncthreads();
-        const uint16_t *off2 = (const uint16_t *)cnt2;
-#pragma unroll
-        for (int u = 0; u < kSpgPerLane; ++u) {
-            blo[u] = ok[u] ? off2[bk[u]] : 0;
-            bhi[u] = ok[u] ? off2[bk[u] + 1] : 0;
-            if (ok[u]) A[blo[u] + arr[u]] = ((unsigned long long)(uint32_t)idv[u] << 32) | (uint32_t)slv[u];
-        }
-    }
-    __syncthreads();
-    SG_HOOK_STAMP(7);
-    // order inside a bucket = number of smaller ids in it -> final position in the row.  The sorted row is assembled
-    // in LDS (ids over the dead minq table, slots behind A) and leaves with consecutive lanes on consecutive words.
-    int32_t *fin_id = (int32_t *)minq;                 // [ns] <= T
-    int32_t *fin_sl = (int32_t *)(pk + a.stride + 1);   // [ns]: A occupies pk[0..ns), ns <= stride; (T - stride - 1) * 8 >= 4 * stride
-    const bool staged = (int64_t)(T - a.stride - 1) * 8 >= (int64_t)4 * a.stride;
-    const uint32_t *Ahi = (const uint32_t *)A;
-#pragma unroll
-    for (int u = 0; u < kSpgPerLane; ++u)
-        if (ok[u]) {
-            const int lo = blo[u], hi = bhi[u];
-            int rank = 0;       // ids are distinct within a set: the high word of A decides
-            for (int t2 = lo; t2 < hi; ++t2) rank += (Ahi[2 * t2 + 1] < (uint32_t)idv[u]) ? 1 : 0;
-            if (staged) {
-                fin_id[lo + rank] = idv[u];
-                fin_sl[lo + rank] = slv[u];
-            } else {
-                a.set_ids[obase + lo + rank] = idv[u];
-                a.set_slot[obase + lo + rank] = slv[u];
-            }
-        }
-    if (staged) {
-        __syncthreads();
-        for (int x = tid; x < ns; x += kWalkThreads) {
-            a.set_ids[obase + x] = fin_id[x];
-            a.set_slot[obase + x] = fin_sl[x];
-        }
-    }
-    SG_HOOK_STAMP(8);
+    walk_sets_spg_epilogue(pk, keys, minq, inv, fk, ft, fs, red, a, i, root, obase, lead, need_rank, ns, total, vmin, vmax, tid SG_HOOK_CLOCK_ARG);
 }
 
-// ------------------------------------------------------------------------------- compaction
-// One wave per root: copy its members from the strided staging area to the packed arrays (subg_acc.c:870-871).
-// INSERT: the same pass also registers every member's LP key in the HBM table of distinct rows
-// (subg_acc.c:957-978) -- the keys of one set are folded in a wave-private LDS table first (a set of ~400
-// members carries a few dozen distinct rows), only those go to HBM, and out_slot[] receives the table slot of
-// every member, so no later pass touches the 8-byte keys again.
-constexpr int kCompactThreads = 256;
-constexpr int kCompactWaves = kCompactThreads / kWave;
-constexpr int kFoldSlots = 256;   // per-wave LDS table
-
-template <bool INSERT>
-__global__ __launch_bounds__(kCompactThreads) void compact_sets_kernel(
-    const int32_t *__restrict__ set_ids, const uint64_t *__restrict__ set_keys, const int32_t *__restrict__ nsize,
-    const int64_t *__restrict__ row_off, int64_t n, int32_t stride, int32_t *__restrict__ out_ids,
-    uint64_t *__restrict__ out_keys, UniqTable t, int64_t tag_base, int32_t *__restrict__ out_slot, int32_t *flags) {
-    __shared__ unsigned long long lk[INSERT ? kCompactWaves * kFoldSlots : 1];
-    __shared__ unsigned long long lt[INSERT ? kCompactWaves * kFoldSlots : 1];
-    __shared__ int32_t ls[INSERT ? kCompactWaves * kFoldSlots : 1];
-    const int wave = threadIdx.x / kWave, lane = threadIdx.x & (kWave - 1);
-    const int64_t i = (int64_t)blockIdx.x * kCompactWaves + wave;
-    const int ns = i < n ? nsize[i] : 0;
-    const int64_t src = i * (int64_t)stride, dst = i < n ? row_off[i] : 0;
-    if (!INSERT) {
-        for (int r = lane; r < ns; r += kWave) {
-            out_ids[dst + r] = set_ids[src + r];
-            out_keys[dst + r] = set_keys[src + r];
-        }
-        return;
-    }
-    unsigned long long *wk = lk + wave * kFoldSlots, *wt = lt + wave * kFoldSlots;
-    int32_t *ws = ls + wave * kFoldSlots;
-    for (int s = lane; s < kFoldSlots; s += kWave) {
-        wk[s] = kEmptyKey;
-        wt[s] = ~0ull;
-    }
-    __syncthreads();
-    for (int r = lane; r < ns; r += kWave) {   // fold the set's keys: key -> min position
-        const unsigned long long key = set_keys[src + r];
-        const unsigned long long tag = (unsigned long long)(tag_base + dst + r);
-        uint32_t h = (uint32_t)(mix64(key) >> 40) & (kFoldSlots - 1);
-        bool done = false;
-        for (int p = 0; p < 16; ++p) {
-            unsigned long long cur = wk[h];
-            if (cur == kEmptyKey) cur = atomicCAS(&wk[h], kEmptyKey, key);
-            if (cur == kEmptyKey || cur == key) {
-                if (wt[h] > tag) atomicMin(&wt[h], tag);
-                done = true;
-                break;
-            }
-            h = (h + 1) & (kFoldSlots - 1);
-        }
-        if (!done) uniq_global_insert(t, key, tag, flags);   // crowded: straight to HBM, found again below
-    }
-    __syncthreads();
-    for (int s = lane; s < kFoldSlots; s += kWave)
-        if (wk[s] != kEmptyKey) ws[s] = uniq_global_insert(t, wk[s], wt[s], flags);
-    __syncthreads();
-    for (int r = lane; r < ns; r += kWave) {
-        const unsigned long long key = set_keys[src + r];   // second read: L2 hit
-        out_ids[dst + r] = set_ids[src + r];
-        if (out_keys) out_keys[dst + r] = key;
-        uint32_t h = (uint32_t)(mix64(key) >> 40) & (kFoldSlots - 1);
-        int32_t slot = -1;
-        for (int p = 0; p < 16; ++p) {
-            if (wk[h] == key) {
-                slot = ws[h];
-                break;
-            }
-            h = (h + 1) & (kFoldSlots - 1);
-        }
-        if (slot < 0) {   // the key went straight to HBM (or the table is over-full: flags[2] is set, caller retries)
-            uint64_t g = mix64(key) & t.mask;
-            for (uint64_t probes = 0; probes < kMaxProbes && t.keys[g] != key; ++probes) g = (g + 1) & t.mask;
-            slot = (int32_t)g;
-        }
-        out_slot[dst + r] = slot;
-    }
-}
 
 }  // namespace subgacc
 
 using namespace subgacc;
-
-extern "C" int subgacc_key_shift(int32_t num_walks, int32_t num_steps) {
-    SG_REQUIRE(num_walks > 0 && num_steps > 0, SUBGACC_ERR_BADARG, "num_walks and num_steps must be positive");
-    const int shift = 32 - __builtin_clz((unsigned)num_walks);
-    SG_REQUIRE((int64_t)num_steps * shift + 1 <= 64, SUBGACC_ERR_KEYWIDTH,
-               "Longer width of type for hasing key needed > INT64.");
-    // an all-ones key would collide with the empty marker of the unique table
-    SG_REQUIRE(!((int64_t)num_steps * shift + 1 == 64 && num_walks == (1 << shift) - 1), SUBGACC_ERR_KEYWIDTH,
-               "key space exhausted: num_steps*SHIFT+1 == 64 with num_walks == 2^SHIFT-1");
-    return shift;
-}
-
-extern "C" size_t subgacc_rng_positions_workspace_bytes(int64_t n) {
-    if (n < 0) n = 0;
-    return align_up((size_t)n * 4, 256) + align_up((size_t)(n + 1) * 8, 256) + scan_workspace_bytes(n);
-}
-
-extern "C" int subgacc_rng_positions(const subgacc_walk_cfg *cfg, const void *indptr, int64_t num_nodes,
-                                     const int32_t *query, int64_t n, int32_t rng_streams, uint64_t calls_before, uint32_t *rng_pos,
-                                     uint32_t *rng_seed, void *workspace, size_t workspace_bytes, void *stream) {
-    SG_REQUIRE(cfg && indptr && rng_pos && rng_seed && n >= 0 && num_nodes >= 0, SUBGACC_ERR_BADARG,
-               "rng_positions: null argument");
-    SG_REQUIRE(rng_streams >= 1, SUBGACC_ERR_BADARG, "rng_positions: rng_streams must be >= 1");
-    SG_REQUIRE(rng_streams == 1 || calls_before == 0, SUBGACC_ERR_BADARG,
-               "rng_positions: calls_before only makes sense for a single stream");
-    if (n == 0) return SUBGACC_OK;
-    SG_REQUIRE(query, SUBGACC_ERR_BADARG, "rng_positions: null query");
-    SG_REQUIRE(workspace && workspace_bytes >= subgacc_rng_positions_workspace_bytes(n), SUBGACC_ERR_WORKSPACE,
-               "rng_positions: workspace too small");
-    hipStream_t s = (hipStream_t)stream;
-    char *ws = (char *)workspace;
-    int32_t *calls = (int32_t *)ws;
-    ws += align_up((size_t)n * 4, 256);
-    int64_t *excl = (int64_t *)ws;
-    ws += align_up((size_t)(n + 1) * 8, 256);
-    const unsigned grid = (unsigned)ceil_div(n, 256);
-    if (cfg->indptr64)
-        hipLaunchKernelGGL(rng_calls_kernel<true>, dim3(grid), dim3(256), 0, s, indptr, query, n, num_nodes, cfg->num_walks,
-                           cfg->num_steps, cfg->first_hop_wo, cfg->cap_root_degree, calls);
-    else
-        hipLaunchKernelGGL(rng_calls_kernel<false>, dim3(grid), dim3(256), 0, s, indptr, query, n, num_nodes, cfg->num_walks,
-                           cfg->num_steps, cfg->first_hop_wo, cfg->cap_root_degree, calls);
-    SG_LAUNCH_CHECK();
-    int rc = exclusive_scan_i32(calls, n, excl, ws, workspace_bytes - (size_t)(ws - (char *)workspace), s);
-    if (rc != SUBGACC_OK) return rc;
-    hipLaunchKernelGGL(rng_positions_kernel, dim3(grid), dim3(256), 0, s, (const int64_t *)excl, n, rng_streams,
-                       calls_before, cfg->seed, rng_pos, rng_seed);
-    SG_LAUNCH_CHECK();
-    return SUBGACC_OK;
-}
-
-template <bool IDX64>
-__global__ void hop_records_kernel(const void *__restrict__ indptr, const int32_t *__restrict__ indices, int64_t num_nodes,
-                                   int64_t nnz, RecFmt f, unsigned long long *__restrict__ recs) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= nnz) return;
-    const int32_t v = indices[e];
-    int64_t beg = 0, deg = 0;
-    if ((uint64_t)(int64_t)v < (uint64_t)num_nodes) load_row<IDX64>(indptr, v, beg, deg);
-    const int deg_bits = 64 - f.id_bits - f.beg_bits;
-    const unsigned long long dmask = (1ull << deg_bits) - 1ull;
-    const unsigned long long dv = (unsigned long long)deg >= dmask ? dmask : (unsigned long long)deg;   // all ones = escape
-    recs[e] = ((unsigned long long)(uint32_t)v << (64 - f.id_bits)) | ((unsigned long long)beg << deg_bits) | dv;
-}
-
-// 16-byte form for graphs with int64 row offsets: {neighbour id : 32 | its degree : 32 (saturated), its row begin : 64}
-template <bool IDX64>
-__global__ void hop_records16_kernel(const void *__restrict__ indptr, const int32_t *__restrict__ indices, int64_t num_nodes,
-                                     int64_t nnz, ulonglong2 *__restrict__ recs) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= nnz) return;
-    const int32_t v = indices[e];
-    int64_t beg = 0, deg = 0;
-    if ((uint64_t)(int64_t)v < (uint64_t)num_nodes) load_row<IDX64>(indptr, v, beg, deg);
-    recs[e] = make_ulonglong2(((unsigned long long)(deg > 0xFFFFFFFFll ? 0xFFFFFFFFull : (unsigned long long)deg) << 32) | (uint32_t)v,
-                              (unsigned long long)beg);
-}
-
-extern "C" int subgacc_hop_records_format(int64_t num_nodes, int64_t nnz, int32_t *id_bits, int32_t *beg_bits) {
-    SG_REQUIRE(num_nodes >= 0 && nnz >= 0 && id_bits && beg_bits, SUBGACC_ERR_BADARG, "hop_records_format: bad arguments");
-    int ib = 1, bb = 1;
-    while (ib < 32 && ((int64_t)1 << ib) < num_nodes) ++ib;
-    while (bb < 40 && ((int64_t)1 << bb) <= nnz) ++bb;
-    *id_bits = ib, *beg_bits = bb;
-    const int deg_bits = 64 - ib - bb;
-    SG_REQUIRE(deg_bits >= 8, SUBGACC_ERR_BADARG, "hop_records_format: only %d bits left for the degree", deg_bits);
-    return deg_bits;
-}
-
-extern "C" int subgacc_hop_records_build(const void *indptr, int32_t indptr64, const int32_t *indices, int64_t num_nodes,
-                                         int64_t nnz, int32_t id_bits, int32_t beg_bits, uint64_t *recs, void *stream) {
-    SG_REQUIRE(indptr && num_nodes >= 0 && nnz >= 0, SUBGACC_ERR_BADARG, "hop_records_build: bad arguments");
-    if (id_bits == 0 && beg_bits == 0) {     // the 16-byte form (2 uint64 per entry)
-        if (nnz == 0) return SUBGACC_OK;
-        SG_REQUIRE(indices && recs, SUBGACC_ERR_BADARG, "hop_records_build: null argument");
-        const int64_t blocks16 = ceil_div(nnz, 256);
-        SG_REQUIRE(blocks16 < (1ll << 31), SUBGACC_ERR_BADARG, "hop_records_build: graph too large for one launch");
-        if (indptr64)
-            hipLaunchKernelGGL(hop_records16_kernel<true>, dim3((unsigned)blocks16), dim3(256), 0, (hipStream_t)stream, indptr,
-                               indices, num_nodes, nnz, (ulonglong2 *)recs);
-        else
-            hipLaunchKernelGGL(hop_records16_kernel<false>, dim3((unsigned)blocks16), dim3(256), 0, (hipStream_t)stream, indptr,
-                               indices, num_nodes, nnz, (ulonglong2 *)recs);
-        SG_LAUNCH_CHECK();
-        return SUBGACC_OK;
-    }
-    SG_REQUIRE(id_bits >= 1 && beg_bits >= 1 && id_bits + beg_bits <= 56, SUBGACC_ERR_BADARG, "hop_records_build: bad field widths");
-    SG_REQUIRE(num_nodes <= ((int64_t)1 << id_bits) && nnz < ((int64_t)1 << beg_bits), SUBGACC_ERR_BADARG,
-               "hop_records_build: the graph does not fit id_bits = %d / beg_bits = %d", id_bits, beg_bits);
-    if (nnz == 0) return SUBGACC_OK;
-    SG_REQUIRE(indices && recs, SUBGACC_ERR_BADARG, "hop_records_build: null argument");
-    const RecFmt f{id_bits, beg_bits};
-    const int64_t blocks = ceil_div(nnz, 256);
-    SG_REQUIRE(blocks < (1ll << 31), SUBGACC_ERR_BADARG, "hop_records_build: graph too large for one launch");
-    if (indptr64)
-        hipLaunchKernelGGL(hop_records_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, indptr, indices,
-                           num_nodes, nnz, f, (unsigned long long *)recs);
-    else
-        hipLaunchKernelGGL(hop_records_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, indptr, indices,
-                           num_nodes, nnz, f, (unsigned long long *)recs);
-    SG_LAUNCH_CHECK();
-    return SUBGACC_OK;
-}
 
 // One walk as launch_walk reads it: each subgacc_walk_* entry point checks its own arguments and fills one.  Rows (form): general
 // sets, ids + 64-bit LP keys in first-visit order (+ raw walks); fused rows, ids sorted + the slot of the LP key in the table of
@@ -789,6 +498,21 @@ struct WalkLaunch {
     int32_t *nesc = nullptr;      // kRowsKeys32 as packed rows (subgacc_walk_keyrows_packed): ids = the words, slot = the escape lists
     int32_t pk_cb = 0, pk_fb = 0;
 };
+
+// the general kernel's launch: one instantiation, then the dispatch over RNG and row form (the row-offset width: launch_walk)
+template <bool I64, int RNG, bool SPG>
+static int sets_launch(const WalkArgs &a, int64_t grid, size_t lds, hipStream_t s) {
+    if (lds > 64 * 1024)
+        SG_CHECK_HIP(hipFuncSetAttribute((const void *)walk_sets_kernel<I64, RNG, SPG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((walk_sets_kernel<I64, RNG, SPG>), dim3((unsigned)grid), dim3(kWalkThreads), lds, s, a);
+    return SUBGACC_OK;
+}
+template <bool I64>
+static int sets_rng(const WalkArgs &a, int rng_mode, bool spg, int64_t grid, size_t lds, hipStream_t s) {
+    if (rng_mode == SUBGACC_RNG_RAND_R)
+        return spg ? sets_launch<I64, SUBGACC_RNG_RAND_R, true>(a, grid, lds, s) : sets_launch<I64, SUBGACC_RNG_RAND_R, false>(a, grid, lds, s);
+    return spg ? sets_launch<I64, SUBGACC_RNG_PHILOX, true>(a, grid, lds, s) : sets_launch<I64, SUBGACC_RNG_PHILOX, false>(a, grid, lds, s);
+}
 
 static int launch_walk(const WalkLaunch &w) {
     const subgacc_walk_cfg *cfg = w.cfg;
@@ -894,28 +618,8 @@ static int launch_walk(const WalkLaunch &w) {
                "1,024-slot table and num_steps*SHIFT+1 <= 31 (subgacc_walk_keyrows64: 4 hops, <= 63 bits); M = %d, m = %d", M, m);
     const int64_t grid = xcd_grid(n);
     SG_REQUIRE(grid < (1ll << 31), SUBGACC_ERR_BADARG, "walk: chunk of %lld roots too large, split it", (long long)n);
-#define SG_WALK_LAUNCH(I64, RNGM, SPGM)                                                                           \
-    do {                                                                                                          \
-        if (lds > 64 * 1024)                                                                                      \
-            SG_CHECK_HIP(hipFuncSetAttribute((const void *)walk_sets_kernel<I64, RNGM, SPGM>,                     \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));              \
-        hipLaunchKernelGGL((walk_sets_kernel<I64, RNGM, SPGM>), dim3((unsigned)grid), dim3(kWalkThreads), lds, s, \
-                           a);                                                                                    \
-    } while (0)
-#define SG_WALK_RNG(I64, SPGM)                                                                                    \
-    do {                                                                                                          \
-        if (cfg->rng_mode == SUBGACC_RNG_RAND_R) SG_WALK_LAUNCH(I64, SUBGACC_RNG_RAND_R, SPGM);                   \
-        else SG_WALK_LAUNCH(I64, SUBGACC_RNG_PHILOX, SPGM);                                                       \
-    } while (0)
-    if (cfg->indptr64) {
-        if (spg) SG_WALK_RNG(true, true);
-        else SG_WALK_RNG(true, false);
-    } else {
-        if (spg) SG_WALK_RNG(false, true);
-        else SG_WALK_RNG(false, false);
-    }
-#undef SG_WALK_RNG
-#undef SG_WALK_LAUNCH
+    const int rc = cfg->indptr64 ? sets_rng<true>(a, cfg->rng_mode, spg, grid, lds, s) : sets_rng<false>(a, cfg->rng_mode, spg, grid, lds, s);
+    if (rc != SUBGACC_OK) return rc;
     SG_LAUNCH_CHECK();
     return SUBGACC_OK;
 }
@@ -1043,67 +747,4 @@ extern "C" int subgacc_walk_tags(const subgacc_walk_cfg *cfg, const void *indptr
     w.uniq_table = uniq_table, w.uniq_capacity = uniq_capacity, w.root_base = root_base;
     w.list = kListSelect, w.worklist = worklist, w.n_work = n_work, w.work_cap = work_cap;
     return launch_walk(w);
-}
-
-extern "C" int subgacc_compact_sets(const int32_t *set_ids, const uint64_t *set_keys, const int32_t *nsize,
-                                    const int64_t *row_off, int64_t n, int32_t stride, int32_t *out_ids,
-                                    uint64_t *out_keys, void *uniq_table, int64_t uniq_capacity, int64_t tag_base,
-                                    int32_t *out_slot, int32_t *flags, void *stream) {
-    SG_REQUIRE(n >= 0 && stride > 0, SUBGACC_ERR_BADARG, "compact_sets: bad sizes");
-    if (n == 0) return SUBGACC_OK;
-    SG_REQUIRE(set_ids && set_keys && nsize && row_off && out_ids, SUBGACC_ERR_BADARG, "compact_sets: null argument");
-    const bool insert = uniq_table != nullptr;
-    SG_REQUIRE(insert || out_keys, SUBGACC_ERR_BADARG, "compact_sets: nothing to produce (no out_keys, no table)");
-    SG_REQUIRE(!insert || (out_slot && flags && tag_base >= 0 && uniq_capacity > 0 &&
-                           (uniq_capacity & (uniq_capacity - 1)) == 0 && uniq_capacity < (1ll << 31)),
-               SUBGACC_ERR_BADARG, "compact_sets: the fused insert needs out_slot, flags and a power-of-two table");
-    const int64_t blocks = ceil_div(n, kCompactWaves);
-    SG_REQUIRE(blocks < (1ll << 31), SUBGACC_ERR_BADARG, "compact_sets: too many roots in one call");
-    if (insert)
-        hipLaunchKernelGGL(compact_sets_kernel<true>, dim3((unsigned)blocks), dim3(kCompactThreads), 0,
-                           (hipStream_t)stream, set_ids, set_keys, nsize, row_off, n, stride, out_ids, out_keys,
-                           uniq_view(uniq_table, uniq_capacity), tag_base, out_slot, flags);
-    else
-        hipLaunchKernelGGL(compact_sets_kernel<false>, dim3((unsigned)blocks), dim3(kCompactThreads), 0,
-                           (hipStream_t)stream, set_ids, set_keys, nsize, row_off, n, stride, out_ids, out_keys,
-                           UniqTable{nullptr, nullptr, nullptr, 0}, (int64_t)0, (int32_t *)nullptr, (int32_t *)nullptr);
-    SG_LAUNCH_CHECK();
-    return SUBGACC_OK;
-}
-
-// SPG mode: rows are already final (sorted ids + table slot); this is a plain strided -> packed copy
-__global__ __launch_bounds__(kCompactThreads) void compact_rows_kernel(const int32_t *__restrict__ row_ids,
-                                                                        const int32_t *__restrict__ row_slot,
-                                                                        const int32_t *__restrict__ nsize,
-                                                                        const int64_t *__restrict__ row_off, int64_t n,
-                                                                        int32_t stride, int32_t *__restrict__ out_indices,
-                                                                        int32_t *__restrict__ out_data,
-                                                                        const int32_t *__restrict__ slot_id) {
-    const int wave = threadIdx.x / kWave, lane = threadIdx.x & (kWave - 1);
-    const int64_t i = (int64_t)blockIdx.x * kCompactWaves + wave;
-    if (i >= n) return;
-    const int ns = nsize[i];
-    const int64_t src = i * (int64_t)stride, dst = row_off[i];
-    for (int r = lane; r < ns; r += kWave) {
-        out_indices[dst + r] = row_ids[src + r];
-        const int32_t sl = row_slot[src + r];
-        out_data[dst + r] = slot_id ? slot_id[sl] + 1 : sl;   // numbered table given: SFptr+1 at once, no translate pass
-    }
-}
-
-extern "C" int subgacc_compact_rows(const int32_t *row_ids, const int32_t *row_slot, const int32_t *nsize,
-                                    const int64_t *row_off, int64_t n, int32_t stride, int32_t *out_indices,
-                                    int32_t *out_data, const void *uniq_table, int64_t uniq_capacity, void *stream) {
-    const int32_t *slot_id = uniq_table ? (const int32_t *)((const char *)uniq_table + (size_t)uniq_capacity * 16) : nullptr;
-    SG_REQUIRE(!uniq_table || uniq_capacity > 0, SUBGACC_ERR_BADARG, "compact_rows: table without capacity");
-    SG_REQUIRE(n >= 0 && stride > 0, SUBGACC_ERR_BADARG, "compact_rows: bad sizes");
-    if (n == 0) return SUBGACC_OK;
-    SG_REQUIRE(row_ids && row_slot && nsize && row_off && out_indices && out_data, SUBGACC_ERR_BADARG,
-               "compact_rows: null argument");
-    const int64_t blocks = ceil_div(n, kCompactWaves);
-    SG_REQUIRE(blocks < (1ll << 31), SUBGACC_ERR_BADARG, "compact_rows: too many rows in one call");
-    hipLaunchKernelGGL(compact_rows_kernel, dim3((unsigned)blocks), dim3(kCompactThreads), 0, (hipStream_t)stream,
-                       row_ids, row_slot, nsize, row_off, n, stride, out_indices, out_data, slot_id);
-    SG_LAUNCH_CHECK();
-    return SUBGACC_OK;
 }

@@ -1,5 +1,6 @@
 // walk_common.hpp -- pieces shared by the walk kernels (walk.hip: one root per workgroup; walk_pipe.hip: persistent,
-// software-pipelined): RNGs, CSR row access, kernel arguments, LDS sizing.
+// software-pipelined; walk_rows.hip, walk_small.hip: fused rows) and by walk_prep.hip (rand_r stream positions, hop records): RNGs, CSR row
+// access, kernel arguments, LDS sizing.
 #pragma once
 #include "common.hpp"
 #include "blockscan.hpp"

@@ -27,6 +27,7 @@
 
 #include "walk_common.hpp"
 #include "waveops.hpp"
+#include "row_sort.hpp"
 
 namespace subgacc {
 
@@ -102,61 +103,7 @@ __device__ __forceinline__ void rows_fetch_slots(const int32_t *keys, const uint
     }
 }
 
-// level 1's geometry: B <= min(T/4, NT) buckets of 2^bshift ids over the set's ns ids in [mn, mx]
-template <int T, int NT>
-__device__ __forceinline__ void rows_bucket_geometry(int32_t ns, int32_t mn, int32_t mx, int &B, int &bshift) {
-    int logb = 0;
-    while ((1 << logb) < ns && (2 << logb) <= T / 4 && (2 << logb) <= NT) ++logb;
-    B = 1 << logb;
-    const uint32_t range = (uint32_t)(mx - mn) + 1u;
-    const int Ls = (range <= 1u) ? 0 : (32 - __builtin_clz(range - 1u));
-    bshift = Ls > logb ? Ls - logb : 0;      // (id - mn) < 2^Ls, and ns <= range => logb <= Ls
-}
-
-// level 1 of the key rows' sort: exclusive scan over the B <= NT buckets, one bucket per lane: wave scan, then (two waves) the
-// wave totals through LDS -> the largest count
-// (a wave's base = the totals of the waves in front of it: at most NT / 64 - 1 of them, spelled out -- as a loop over
-//  tid / 64 the compiler vectorised it into 16-byte reads with a scalar tail, ~60 instructions for one addition)
-template <int NT>
-__device__ __forceinline__ int32_t rows_level1_scan(int32_t *start, int32_t *red, int B, int tid) {
-    const int32_t c = tid < B ? start[tid] : 0;
-    const int32_t inc = wave_scan_add_i32_incl(c);     // inclusive scan over the wave
-    const int32_t mc = wave_red_max_i32(c);
-    int32_t base = 0, maxc = mc;
-    if (NT > kWave) {
-        if ((tid & (kWave - 1)) == kWave - 1) red[12 + tid / kWave] = inc, red[4 + tid / kWave] = mc;
-        __syncthreads();
-#pragma unroll
-        for (int w2 = 0; w2 < NT / kWave - 1; ++w2) base += w2 < tid / kWave ? red[12 + w2] : 0;
-        maxc = red[4];
-#pragma unroll
-        for (int w2 = 1; w2 < NT / kWave; ++w2) maxc = max(maxc, red[4 + w2]);
-    }
-    const int32_t excl = base + inc - c;
-    if (tid < B) start[tid] = excl;
-    if (tid == B - 1) start[B] = excl + c;
-    return maxc;
-}
-
-// Where a member goes at level 2: its level-1 bucket b1 (from lo1 on, kb / fine members) is cut into kb parts of equal id width;
-// ido = id - min, off = the member's offset in the bucket's id window, sub = its part
-struct RowsPart {
-    uint32_t lo1, kb, off, sub;
-};
-__device__ __forceinline__ RowsPart rows_part(const int32_t *start, uint32_t ido, uint32_t b1, int bshift, uint32_t fine) {
-    RowsPart p;
-    p.lo1 = (uint32_t)start[b1];
-    p.kb = ((uint32_t)start[b1 + 1] - p.lo1) * fine;
-    p.off = ido - (b1 << bshift);                                                  // < 2^bshift
-    p.sub = bshift ? __umulhi(p.off << (32 - bshift), p.kb) : 0u;                 // floor(off * kb / 2^bshift) < kb
-    return p;
-}
-
-// one more member in the 16-bit counter idx (two per word) -> its arrival order
-__device__ __forceinline__ uint32_t rows_count16(uint32_t *cnt2, uint32_t idx) {
-    const uint32_t sh = (idx & 1u) * 16u;
-    return (atomicAdd(&cnt2[idx >> 1], 1u << sh) >> sh) & 0xFFFFu;
-}
+// (level 1's geometry and scan, a member's level-2 part, the 16-bit counters and their scan: row_sort.hpp, shared with walk.hip)
 
 // NT lanes per workgroup (256, or 128 with two walks per lane: twice the roots per CU where the 512-slot table leaves the
 // LDS for them), SPL table slots per lane, T = NT * SPL.
@@ -1124,7 +1071,7 @@ __global__ __launch_bounds__(NT, K32 ? (KR ? 6 : 5) : (KR ? 5 : (NT == 128 ? 7 :
     SG_HOOK_RSTAMP(5);
     int32_t maxc;
     {   // exclusive scan over the B <= 256 buckets, one bucket per lane: wave scan, then the wave totals through LDS
-        // (rows_level1_scan, written out: called here, the table form's kernels came out as different instructions)
+        // (rows_level1_scan of row_sort.hpp, written out: called here, the table form's kernels came out as different instructions)
         const int32_t c = tid < B ? start[tid] : 0;
         const int32_t inc = wave_scan_add_i32_incl(c);     // inclusive scan over the wave
         const int32_t mc = wave_red_max_i32(c);
@@ -1169,6 +1116,7 @@ __global__ __launch_bounds__(NT, K32 ? (KR ? 6 : 5) : (KR ? 5 : (NT == 128 ? 7 :
         }
         __syncthreads();
         {   // exclusive scan of the ns + 1 level-2 counters, in place (offsets <= ns < 2^16): CW consecutive words per lane
+            // (rows_level2_scan<NT, CW> of row_sort.hpp, written out: called here, the table form's kernels came out as different instructions)
             uint32_t w[CW];
             int32_t s2 = 0;
 #pragma unroll

@@ -59,7 +59,7 @@ def rand_r_calls(indptr, roots, num_walks, num_steps, first_hop_wo=True, cap_roo
     """Number of rand_r draws the reference's sequential loop makes for `roots` (subg_acc.c:763-776: M shuffle draws when
     deg > M; :790-808: one draw per later step of every walk; nothing for an isolated root) -- the stream position
     at which the NEXT root starts.  This is what a rank needs to know about the roots in front of its range
-    (`calls_before` of subgacc_rng_positions); same arithmetic as rng_calls_kernel (csrc/walk.hip).  Works on
+    (`calls_before` of subgacc_rng_positions); same arithmetic as rng_calls_kernel (csrc/walk_prep.hip).  Works on
     host or device tensors (a gather of the roots' degrees and a sum)."""
     M, m = int(num_walks), int(num_steps)
     r = torch.as_tensor(roots).long().reshape(-1)

@@ -109,7 +109,7 @@ def test_constants_match_the_header(L):
 
 
 def test_hop_records_format_through_void_pointers(L):
-    """Host-only code (csrc/walk.hip: two loops over the bit widths, no device call): byref(c_int32) outputs through the derived
+    """Host-only code (csrc/walk_prep.hip: two loops over the bit widths, no device call): byref(c_int32) outputs through the derived
     c_void_p parameters give what a handle typed POINTER(c_int32), as the binding used to be, gives -- and what the loops say."""
     typed = C.CDLL(_lib.LIB_PATH).subgacc_hop_records_format
     typed.restype, typed.argtypes = C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]

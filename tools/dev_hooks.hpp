@@ -23,6 +23,8 @@
 // ---- walk.hip / walk_rows.hip
 #if SG_EXPERIMENT == 7
 #define SG_HOOK_KERNEL_ENTRY() unsigned long long t_prev__ = __builtin_readcyclecounter()
+#define SG_HOOK_CLOCK_PARAM , unsigned long long &t_prev__
+#define SG_HOOK_CLOCK_ARG , t_prev__
 #define SG_HOOK_STAMP(k)                                                                        \
     do {                                                                                        \
         if (threadIdx.x == 0 && (blockIdx.x & 63) == 0) {   /* 1 workgroup in 64: the atomics stay uncontended */ \
@@ -33,6 +35,8 @@
     } while (0)
 #elif defined(SG_STOP_AFTER)
 #define SG_HOOK_KERNEL_ENTRY()
+#define SG_HOOK_CLOCK_PARAM
+#define SG_HOOK_CLOCK_ARG
 #define SG_HOOK_STAMP(k)                 \
     do {                                 \
         if (SG_STOP_AFTER == (k)) {      \
@@ -47,6 +51,8 @@
     } while (0)
 #else
 #define SG_HOOK_KERNEL_ENTRY()
+#define SG_HOOK_CLOCK_PARAM
+#define SG_HOOK_CLOCK_ARG
 #define SG_HOOK_STAMP(k)
 #endif
 
