@@ -584,13 +584,23 @@ class StepBuffers:
     is packed wherever the form exists: the row form (stage=None) with f32 rows, segment pointers, pairs and one batch per step, over
     32-bit key rows of a two-wave form on a graph whose ids leave three bits a count (sampler.packed_rows_form).  True: the same, and
     ValueError where it does not exist.  False: the two planes.  `ids` and `slot` show today's rows either way: of a packed step
-    they are unpacked when first looked at (subgacc_unpack_packed_rows, into planes allocated then), never in the step."""
+    they are unpacked when first looked at (subgacc_unpack_packed_rows, into planes allocated then), never in the step.
+    wide_keys=True: a stage ("counts", "counts_attn", "index") over the 64-bit key rows of a 4-hop shape with M = 128 .. 204
+    (sampler.key_rows_form == 64: the paper's citation2 setting M = 200, m = 4), which the stages refuse otherwise -- `self.wide`.
+    The columns pass is subgacc_keyrows_columns64 (include/subgacc_wide.h: one launch more than the 32-bit step), which also writes
+    every member's column as a 32-bit surrogate key into `cols` int32 [rows * stride]; the joins read `cols` and the identity list
+    `ukeys` = 1 .. c instead of `slot`, and answer exactly what they answer at a 32-bit shape.  The buffers hold `ukeys64` int64
+    [table_rows - 1] (the sorted distinct keys), `cols` -- 4 bytes per member slot beside the 8 of `slot` -- and a larger `col_ws`;
+    `slot` keeps the 64-bit keys.  table_rows <= 8,192 at such a shape (ValueError before any device work); at a shape with 32-bit or
+    small key rows the keyword changes nothing."""
 
     def __init__(self, csr, pairs, num_walks=200, num_steps=3, uniq_capacity=1 << 17, out=None, dedup_roots=False, rng="philox",
                  key_rows=True, sort_roots=True, batch=None, align_rows=True, order=None, ptr=True, triplets=False, stage=None,
-                 table_rows=2048, dtype=None, packed_rows=None):
+                 table_rows=2048, dtype=None, packed_rows=None, wide_keys=False):
         from .sampler import FUSED_MAX_Q, as_rank, key_rows_form, packed_rows_form, small_rows_form
         self.packed, self._unpacked, self._unpacked_step = False, None, -1
+        # a stage over 64-bit key rows (wide_keys=True at such a shape, nothing anywhere else): the columns pass of csrc/keycols64.hip
+        self.wide = bool(wide_keys) and stage in _KEY_STAGES and bool(key_rows) and key_rows_form(int(num_walks), int(num_steps)) == 64
         self.half = _half_code(dtype, "StepBuffers", lambda: {
             "ptr=False (segment ids)": not ptr, "triplets=True": triplets, f"stage={stage!r}": stage is not None,
             "key_rows=False (strided rows of table slots)": not key_rows,
@@ -604,7 +614,7 @@ class StepBuffers:
             who = f"StepBuffers(stage='{stage}')"
             if stage == "index" and triplets:
                 raise ValueError(f"{who} joins pairs: triplets=True has no index form (HONet has no LSTM aggregation)")
-            _counts_stage_shape(who, num_walks, num_steps, key_rows, self.T)
+            _counts_stage_shape(who, num_walks, num_steps, key_rows, self.T, wide_keys)
             if batch is not None and int(batch) != int(pairs):
                 raise ValueError(f"{who}: the columns are those of one batch (batch=None)")
             if out is not None or not ptr:
@@ -699,7 +709,12 @@ class StepBuffers:
             self.sizes = torch.empty(S, dtype=torch.int32, device=dev)
             self.ukeys = torch.empty(T - 1, dtype=torch.int32, device=dev)
             self.feat = torch.empty((T, self.k), dtype=torch.float32, device=dev)
-            self.col_ws = torch.zeros(L.subgacc_keyrows_columns_workspace_bytes(T), dtype=torch.uint8, device=dev)   # zeroed once
+            if self.wide:   # the sorted 64-bit keys, the rows as surrogate keys (what the joins read instead of `slot`), the wider set
+                self.ukeys64 = torch.empty(T - 1, dtype=torch.int64, device=dev)
+                self.cols = torch.empty(n * self.stride, dtype=torch.int32, device=dev)
+                self.col_ws = torch.zeros(L.subgacc_keyrows_columns64_workspace_bytes(T), dtype=torch.uint8, device=dev)   # zeroed once
+            else:
+                self.col_ws = torch.zeros(L.subgacc_keyrows_columns_workspace_bytes(T), dtype=torch.uint8, device=dev)   # zeroed once
             self.ws = self.out = self.segid = None
             if stage == "index":    # the index pairs of the worst case, and the size pass in front of them
                 self.pairs = torch.empty((S * self.Q, 2), dtype=torch.int32, device=dev)
@@ -762,17 +777,24 @@ class _FitStepBuffers(StepBuffers):
 
 
 COUNTS_MAX_TABLE_ROWS = 16384      # subgacc_keyrows_columns sorts the distinct keys of a step in LDS
+COUNTS_MAX_TABLE_ROWS_WIDE = 8192  # ... subgacc_keyrows_columns64 sorts 64-bit keys in the same 128 KiB
 _COUNT_STAGES = ("counts", "counts_attn")       # the stages of a step that run over the columns of its LP keys: the count forms
 _KEY_STAGES = _COUNT_STAGES + ("index",)        # ... and the index form
 
 
-def _counts_stage_shape(who, num_walks, num_steps, key_rows, table_rows):
+def _counts_stage_shape(who, num_walks, num_steps, key_rows, table_rows, wide_keys=False):
     """what the count stage of a step refuses before any device work: a shape without 32-bit key rows, key_rows=False, a table_rows
-    the columns pass does not hold"""
+    the columns pass does not hold.  wide_keys: a shape with 64-bit key rows is served too (subgacc_keyrows_columns64), with at most
+    COUNTS_MAX_TABLE_ROWS_WIDE columns; nothing changes at any other shape"""
     from .sampler import key_rows_form, small_rows_form
     if not key_rows:
         raise ValueError(f"{who} runs over the key rows of the step: key_rows=False has none")
     form = key_rows_form(int(num_walks), int(num_steps))
+    if form == 64 and wide_keys:
+        if not 2 <= int(table_rows) <= COUNTS_MAX_TABLE_ROWS_WIDE:
+            raise ValueError(f"{who}: table_rows = {table_rows} (2 .. {COUNTS_MAX_TABLE_ROWS_WIDE} with 64-bit LP keys, wide_keys=True: "
+                             "column 0 and one column per distinct LP row)")
+        return
     if form != 32 and not small_rows_form(int(num_walks), int(num_steps)):
         raise ValueError(f"{who} needs 32-bit LP keys: num_walks = {num_walks}, num_steps = {num_steps} " +
                          ("has 64-bit keys (key_rows_form == 64)" if form == 64 else "has no key-rows form"))
@@ -825,9 +847,15 @@ def _step_columns(bufs, flags, st, fit):
     number of distinct LP rows c is read back once and T = c + 1"""
     n, T = bufs.n, bufs.T
     count = bufs.status[2:3]        # the status word `distinct rows`: resolve() reads it with the flags
-    with _timed("keyrows_columns"):
-        check(lib().subgacc_keyrows_columns(ptr(bufs.slot), ptr(bufs.nsize), n, bufs.stride, bufs.M, bufs.m, T, ptr(bufs.ukeys),
-                                            ptr(count), ptr(bufs.feat), ptr(flags), ptr(bufs.col_ws), bufs.col_ws.numel(), st))
+    if bufs.wide:   # 64-bit key rows: three launches, and the rows as surrogate keys in bufs.cols (_step_key_desc hands them to the joins)
+        with _timed("keyrows_columns64"):
+            check(lib().subgacc_keyrows_columns64(ptr(bufs.slot), ptr(bufs.nsize), n, bufs.stride, bufs.M, bufs.m, T, ptr(bufs.ukeys64),
+                                                  ptr(bufs.ukeys), ptr(count), ptr(bufs.feat), ptr(bufs.cols), ptr(flags),
+                                                  ptr(bufs.col_ws), bufs.col_ws.numel(), st))
+    else:
+        with _timed("keyrows_columns"):
+            check(lib().subgacc_keyrows_columns(ptr(bufs.slot), ptr(bufs.nsize), n, bufs.stride, bufs.M, bufs.m, T, ptr(bufs.ukeys),
+                                                ptr(count), ptr(bufs.feat), ptr(flags), ptr(bufs.col_ws), bufs.col_ws.numel(), st))
     if fit:
         words = bufs.status.tolist()
         if (words[1] & 0xFFFFFFFF) & 1:
@@ -839,8 +867,10 @@ def _step_columns(bufs, flags, st, fit):
 
 def _step_key_desc(bufs, form, own, partner, T, flags):
     """the descriptor of a join over the key rows of a step of `bufs`: its strided rows of 32-bit LP keys, the mirrored list
-    (own, partner) and T columns"""
-    return _lib.join_desc(form, JOIN_KEY32, row_len=bufs.nsize, n_rows=bufs.n, row_stride=bufs.stride, ids=bufs.ids, payload=bufs.slot,
+    (own, partner) and T columns.  A wide step (64-bit keys): the same descriptor over bufs.cols, the rows as 32-bit surrogate keys
+    whose list bufs.ukeys is 1 .. c (subgacc_keyrows_columns64)"""
+    return _lib.join_desc(form, JOIN_KEY32, row_len=bufs.nsize, n_rows=bufs.n, row_stride=bufs.stride, ids=bufs.ids,
+                          payload=bufs.cols if bufs.wide else bufs.slot,
                           own=own, partner=partner, S=bufs.S, pair_block=bufs.batch, table_rows=T, num_walks=bufs.M, num_steps=bufs.m,
                           flags=flags)
 
@@ -1105,33 +1135,36 @@ def sample_and_hgather(csr, hedge, num_walks=200, num_steps=3, seed=111413, rng=
     return xz, ids, sets
 
 
-def _step_counts(who, csr, e, triplets, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers, stage="counts"):
+def _step_counts(who, csr, e, triplets, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers, stage="counts",
+                 wide_keys=False):
     """sample_and_counts / sample_and_hcounts: the step with stage="counts" through the caller's StepBuffers, or through a set made for
     this one call (stage="counts_attn": sample_and_attn_counts, which checks the step itself once its kernel has run)"""
-    from .sampler import as_rank
+    from .sampler import as_rank, key_rows_form
     order = as_rank(csr, order)
+    wide = bool(wide_keys) and key_rows_form(int(num_walks), int(num_steps)) == 64     # (the keyword means nothing at any other shape)
     if buffers is not None:
         if buffers.stage != stage or buffers.triplets != triplets:
             raise ValueError(f"{who}: buffers= must be StepBuffers(..., stage='{stage}'" + (", triplets=True)" if triplets else ")"))
         if (dedup_roots and not buffers.dedup) or (num_walks, num_steps) != (buffers.M, buffers.m) or \
-                (table_rows is not None and int(table_rows) != buffers.T):
+                (table_rows is not None and int(table_rows) != buffers.T) or wide != bool(getattr(buffers, "wide", False)):
             raise ValueError(f"{who}: buffers= serves the step its StepBuffers were made for (num_walks, num_steps, table_rows; root "
                              "dedup if they were made with dedup_roots=True)")
         if order is not None and (buffers.order is None or order.rank is not buffers.order.rank):
             raise ValueError("buffers= walks in the order its StepBuffers were made with: pass order= to StepBuffers(...)")
         return _buffered_step(csr, e, buffers, seed, None)
     fit = table_rows is None
-    T = COUNTS_MAX_TABLE_ROWS if fit else int(table_rows)
-    _counts_stage_shape(who, num_walks, num_steps, True, T)
+    T = (COUNTS_MAX_TABLE_ROWS_WIDE if wide else COUNTS_MAX_TABLE_ROWS) if fit else int(table_rows)
+    _counts_stage_shape(who, num_walks, num_steps, True, T, wide_keys)
     bufs = (_FitStepBuffers if fit else StepBuffers)(csr, e.shape[1], num_walks=num_walks, num_steps=num_steps, dedup_roots=dedup_roots,
-                                                     order=order, triplets=triplets, stage=stage, table_rows=T)
+                                                     order=order, triplets=triplets, stage=stage, table_rows=T, wide_keys=wide_keys)
     C, sizes, table, sets = _buffered_step(csr, e, bufs, seed, None, fit=fit)
     if stage != "counts_attn":
         sets.resolve()
     return C, sizes, table, sets
 
 
-def sample_and_counts(csr, edge, num_walks=200, num_steps=3, seed=111413, dedup_roots=False, order=None, table_rows=None, buffers=None):
+def sample_and_counts(csr, edge, num_walks=200, num_steps=3, seed=111413, dedup_roots=False, order=None, table_rows=None, buffers=None,
+                      wide_keys=False):
     """The count form of the on-demand step: sample the endpoints of `edge` [2, B] and join their key rows as COUNTS ->
     (C float32 [2B, T], sizes int32 [2B], table float32 [T, m+1], sets).  C[j, p] = how often row p of `table` occurs in either feature
     slot of segment j (gather()'s segments: left blocks, then right blocks), p = 0 the zero row of a member without a partner; sizes =
@@ -1146,20 +1179,28 @@ def sample_and_counts(csr, edge, num_walks=200, num_steps=3, seed=111413, dedup_
     and table are views of the buffers, and sets.resolve() raises SubgAccError naming table_rows when the step had more distinct LP
     rows than columns (C is then not to be used).  Shapes: 32-bit key rows -- 2 to 4 hops with num_steps*SHIFT+1 <= 31 over a 512- or
     1,024-slot table (sampler.key_rows_form == 32), and the small shapes, 1 to 4 hops with M*m+1 <= 204 (sampler.small_rows_form:
-    csrc/walk_small.hip writes their rows); rng Philox."""
+    csrc/walk_small.hip writes their rows); rng Philox.
+    wide_keys=True (here and on the seven other stage calls -- sample_and_hcounts, sample_and_mean_stage, sample_and_hmean_stage,
+    sample_and_attn_counts, sample_and_attn_stage, sample_and_index, sample_and_lstm_stage -- and on StepBuffers): the shapes with 64-bit
+    keys too (sampler.key_rows_form == 64: 4 hops, M = 128 .. 204, the paper's citation2 setting M = 200), with the same results under
+    the same rules; the columns pass is subgacc_keyrows_columns64 and table_rows is at most 8,192 there (ValueError before any device
+    work; without table_rows a batch of more than 8,191 distinct LP rows raises SubgAccError).  It changes nothing at a shape with 32-bit
+    or small key rows.  With buffers= the buffers' own setting holds: they must have been made with the same wide_keys."""
     e = _as_rows(edge, csr.device)
     if e.dim() != 2 or e.shape[0] != 2:
         raise ValueError(f"sample_and_counts: edge must be [2, B], not {list(e.shape)}")
-    return _step_counts("sample_and_counts", csr, e, False, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers)
+    return _step_counts("sample_and_counts", csr, e, False, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers,
+                        wide_keys=wide_keys)
 
 
 def sample_and_hcounts(csr, hedge, num_walks=200, num_steps=3, seed=111413, dedup_roots=False, order=None, table_rows=None,
-                       buffers=None):
+                       buffers=None, wide_keys=False):
     """sample_and_counts for the triplets `hedge` [3, B] (u, v, w) of the higher-order model: 3B roots walked once each, hgather's 4B
     segments [U|w ; W|u ; V|w ; W|v] -> (C float32 [4B, T], sizes int32 [4B], table, sets); the rows hgather_counts(hedge, z, ...)
     counts.  buffers=StepBuffers(csr, B, ..., triplets=True, stage="counts", table_rows=T)."""
     h = _as_triplets(hedge, csr.device, "sample_and_hcounts")
-    return _step_counts("sample_and_hcounts", csr, h, True, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers)
+    return _step_counts("sample_and_hcounts", csr, h, True, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers,
+                        wide_keys=wide_keys)
 
 
 def _step_mean(C, sizes, table, sets, embed, blocks):
@@ -1169,7 +1210,7 @@ def _step_mean(C, sizes, table, sets, embed, blocks):
 
 
 def sample_and_mean_stage(csr, edge, embed, num_walks=200, num_steps=3, seed=111413, dedup_roots=False, order=None, table_rows=None,
-                          buffers=None):
+                          buffers=None, wide_keys=False):
     """The reference's first model stage for mean aggregation (model.py:78-83: x = pe_embedding(xz).sum(dim=-2); xl, xr =
     MeanAggregation(x, ptr).view(2, -1, H)) on the on-demand step: (C @ embed(table)) / sizes with (C, sizes, table) =
     sample_and_counts(csr, edge, ...) -- mean_stage's algebra without a resident store, and without xz [R,2,k] or the [R,2,H]
@@ -1178,15 +1219,17 @@ def sample_and_mean_stage(csr, edge, embed, num_walks=200, num_steps=3, seed=111
     is checked before the result is returned.  With buffers= nothing is read back, as for every buffered step: the step's SampledSets
     are `buffers.sets`, and `buffers.sets.resolve()` (after `.prefetch()`, if the loop queues ahead) raises SubgAccError when the step
     had more distinct LP rows than table_rows - 1 -- its result is then not to be used."""
-    return _step_mean(*sample_and_counts(csr, edge, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers), embed, 2)
+    return _step_mean(*sample_and_counts(csr, edge, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers, wide_keys),
+                      embed, 2)
 
 
 def sample_and_hmean_stage(csr, hedge, embed, num_walks=200, num_steps=3, seed=111413, dedup_roots=False, order=None, table_rows=None,
-                           buffers=None):
+                           buffers=None, wide_keys=False):
     """HONet's first stage (model_horder.py:56-57: scatter_mean(pe_embedding(xz).sum(-2), ind).view(4, -1, H)) on the on-demand triplet
     step: hmean_stage's algebra over sample_and_hcounts.  Returns float32 [4, B, H] in the order (xu, xwu, xv, xwv); with buffers= the
     step is checked through `buffers.sets.resolve()`, as for sample_and_mean_stage."""
-    return _step_mean(*sample_and_hcounts(csr, hedge, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers), embed, 4)
+    return _step_mean(*sample_and_hcounts(csr, hedge, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers, wide_keys),
+                      embed, 4)
 
 
 class _StepAttnJoin:
@@ -1241,7 +1284,7 @@ class _StepAttnJoin:
         return Dg
 
 
-def _step_attn(who, csr, edge, gate, bias, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers):
+def _step_attn(who, csr, edge, gate, bias, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers, wide_keys=False):
     """sample_and_attn_counts with gate(table, count) -- count: the number of distinct LP rows c, int64 [1] on the device -- and the
     gate's bias (None: none) as an input of the autograd function -> (W, sizes, table, sets, count)"""
     e = _as_rows(edge, csr.device)
@@ -1249,14 +1292,14 @@ def _step_attn(who, csr, edge, gate, bias, num_walks, num_steps, seed, dedup_roo
         raise ValueError(f"{who}: edge must be [2, B], not {list(e.shape)}")
     if e.shape[1] == 0 and buffers is None:     # an empty batch: no step, the zero row alone
         T = 2 if table_rows is None else int(table_rows)
-        _counts_stage_shape(who, num_walks, num_steps, True, T)
+        _counts_stage_shape(who, num_walks, num_steps, True, T, wide_keys)
         dev = csr.device
         join = _StepAttnJoin(None, None, None, T, 0, None, dev)
         sizes, table = torch.empty(0, dtype=torch.int32, device=dev), torch.zeros((T, int(num_steps) + 1), dtype=torch.float32, device=dev)
         sets, count = None, torch.zeros(1, dtype=torch.int64, device=dev)
     else:
         join, sizes, table, sets = _step_counts(who, csr, e, False, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers,
-                                                stage="counts_attn")
+                                                stage="counts_attn", wide_keys=wide_keys)
         count = join.bufs.status[2:3]
     g = gate(table, count)
     if not (torch.is_tensor(g) and g.shape == (join.T,) and g.dtype == torch.float32 and g.device == table.device):
@@ -1271,7 +1314,7 @@ def _step_attn(who, csr, edge, gate, bias, num_walks, num_steps, seed, dedup_roo
 
 
 def sample_and_attn_counts(csr, edge, gate, num_walks=200, num_steps=3, seed=111413, dedup_roots=False, order=None, table_rows=None,
-                           buffers=None):
+                           buffers=None, wide_keys=False):
     """The attentional count form of the on-demand step: sample the endpoints of `edge` [2, B], number the batch's distinct LP rows as
     sample_and_counts does, and join the key rows as SOFTMAX-WEIGHTED counts -> (W float32 [2B, T], sizes int32 [2B], table float32
     [T, m+1], sets).  gate: a callable table -> g float32 [T], the gate's logit of every row of `table` (row 0 = partner absent; the rows
@@ -1287,11 +1330,11 @@ def sample_and_attn_counts(csr, edge, gate, num_walks=200, num_steps=3, seed=111
     read back (capturable); W, sizes and table are views of the buffers, and the backward, which joins the step's rows again, must run
     before the buffers take their next step: later it raises RuntimeError naming the step, it never answers from another batch."""
     return _step_attn("sample_and_attn_counts", csr, edge, lambda table, count: gate(table), None, num_walks, num_steps, seed, dedup_roots, order, table_rows,
-                      buffers)[:4]
+                      buffers, wide_keys)[:4]
 
 
 def sample_and_attn_stage(csr, edge, embed, gate_nn, value_nn=None, num_walks=200, num_steps=3, seed=111413, dedup_roots=False,
-                          order=None, table_rows=None, buffers=None):
+                          order=None, table_rows=None, buffers=None, wide_keys=False):
     """The reference's first model stage of the LP encoder for --aggr attn (model.py:59-62,78-81: x = pe_embedding(xz).sum(dim=-2);
     xl, xr = AttentionalAggregation(gate_nn, nn)(x, ptr=ptr).view(2, -1, H'')) on the on-demand step -- counts_attn_stage's algebra
     without a resident store, and without xz [R,2,k], the [R,2,H] activations or the pair rows:
@@ -1325,7 +1368,7 @@ def sample_and_attn_stage(csr, edge, embed, gate_nn, value_nn=None, num_walks=20
         return (E - centre) @ gate.weight.view(-1)
 
     W, sizes, table, sets, _ = _step_attn(name, csr, edge, logits, gate.bias, num_walks, num_steps, seed, dedup_roots, order, table_rows,
-                                          buffers)
+                                          buffers, wide_keys)
     h = W @ box["E"]
     if val is not None:
         h = torch.nn.functional.linear(h, val.weight, val.bias)
@@ -2177,7 +2220,8 @@ def index_lstm_stage(edge, x, encode, embed, lstm):
     return out
 
 
-def sample_and_index(csr, edge, num_walks=200, num_steps=3, seed=111413, dedup_roots=False, order=None, table_rows=None, buffers=None):
+def sample_and_index(csr, edge, num_walks=200, num_steps=3, seed=111413, dedup_roots=False, order=None, table_rows=None, buffers=None,
+                     wide_keys=False):
     """The index form of the on-demand step: sample the endpoints of `edge` [2, B], number the batch's distinct LP rows as
     sample_and_counts does, and join the key rows as INDEX PAIRS -> (pairs int32 [R, 2], indptr int64 [2B+1], table float32 [T, m+1],
     sets).  Row indptr[j] + t of `pairs` is (p_t, q_t) for member t of segment j (gather()'s segments and row order: members in ascending
@@ -2200,12 +2244,12 @@ def sample_and_index(csr, edge, num_walks=200, num_steps=3, seed=111413, dedup_r
         raise ValueError(f"{who}: edge must be [2, B], not {list(e.shape)}")
     if e.shape[1] == 0 and buffers is None:      # an empty batch: no step, the zero row alone
         T = 2 if table_rows is None else int(table_rows)
-        _counts_stage_shape(who, num_walks, num_steps, True, T)
+        _counts_stage_shape(who, num_walks, num_steps, True, T, wide_keys)
         dev = csr.device
         return (torch.zeros((0, 2), dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int64, device=dev),
                 torch.zeros((T, int(num_steps) + 1), dtype=torch.float32, device=dev), None)
     pairs, indptr, table, sets = _step_counts(who, csr, e, False, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers,
-                                              stage="index")
+                                              stage="index", wide_keys=wide_keys)
     if buffers is None:
         pairs = pairs[: int(indptr[-1].item())]
     return pairs, indptr, table, sets
@@ -2236,7 +2280,7 @@ class _StepLstmJoin(_LstmJoin):
 
 
 def sample_and_lstm_stage(csr, edge, embed, lstm, num_walks=200, num_steps=3, seed=111413, dedup_roots=False, order=None,
-                          table_rows=None, buffers=None):
+                          table_rows=None, buffers=None, wide_keys=False):
     """The reference's first model stage of the LP encoder for --aggr lstm (model.py:63-65,78-83: x = pe_embedding(xz).sum(dim=-2);
     xl, xr = LSTMAggregation(H, H')(x, index=ptr).view(2, -1, H'); main.py:217) on the on-demand step -- index_lstm_stage's algebra
     without a resident store, and without xz [R,2,k], the packed copy of the step's rows or their registration:
@@ -2261,7 +2305,7 @@ def sample_and_lstm_stage(csr, edge, embed, lstm, num_walks=200, num_steps=3, se
     for prm in embed.parameters():
         if prm.device != dev or prm.dtype != torch.float32:
             raise ValueError(f"{name}: embed must hold float32 parameters on the graph's device ({dev})")
-    pairs, indptr, table, _ = sample_and_index(csr, edge, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers)
+    pairs, indptr, table, _ = sample_and_index(csr, edge, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers, wide_keys)
     S, T = indptr.numel() - 1, int(table.shape[0])
     E = embed(table)
     if E.ndim != 2 or E.shape[0] != T or E.shape[1] != lstm.input_size:
