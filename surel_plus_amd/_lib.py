@@ -1,6 +1,7 @@
 """ctypes binding of libsubgacc_hip.so, derived from the declarations of include/subgacc.h (the C ABI), of include/subgacc_half.h
 (the join's rows in a 16-bit type), of include/subgacc_small.h (key rows for the small walk shapes), of include/subgacc_packed.h
-(the step's key rows as one word per member) and of include/subgacc_wide.h (the columns of 64-bit key rows) when this module is imported: an entry point is declared there and defined under csrc/, and
+(the step's key rows as one word per member), of include/subgacc_wide.h (the columns of 64-bit key rows) and of include/subgacc_half64.h
+(the 16-bit rows over 64-bit key rows) when this module is imported: an entry point is declared there and defined under csrc/, and
 nothing here names it.
 
 There is no CPU fallback: if the library is missing, or no gfx950 device is visible when a compute entry
@@ -134,6 +135,11 @@ WIDE_HEADER = os.path.join(os.path.dirname(HEADER), "subgacc_wide.h")
 WIDE_DECLS = parse_header(_header_text(WIDE_HEADER))
 _TYPES.update(bind_types(WIDE_DECLS))
 WIDE_SYMBOLS = tuple(WIDE_DECLS)
+# the sixth header: the join's rows in a 16-bit type over 64-bit key rows (csrc/sjoin_half64.hip), the same library, the same descriptor
+HALF64_HEADER = os.path.join(os.path.dirname(HEADER), "subgacc_half64.h")
+HALF64_DECLS = parse_header(_header_text(HALF64_HEADER))
+_TYPES.update(bind_types(HALF64_DECLS))
+HALF64_SYMBOLS = tuple(HALF64_DECLS)
 HALF_F16, HALF_BF16 = (int(re.search(rf"^#define\s+SUBGACC_HALF_{n}\s+(\d+)", _HALF_TEXT, re.M).group(1)) for n in ("F16", "BF16"))
 
 
@@ -145,7 +151,7 @@ VERBOSE = os.environ.get("SUBGACC_QUIET", "0") != "1"
 def build(force=False):
     """hipcc-compile csrc/*.hip for gfx950 into surel_plus_amd/libsubgacc_hip.so (in-tree)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))]
-    srcs += [HEADER, HALF_HEADER, SMALL_HEADER, PACKED_HEADER, WIDE_HEADER]
+    srcs += [HEADER, HALF_HEADER, SMALL_HEADER, PACKED_HEADER, WIDE_HEADER, HALF64_HEADER]
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
         subprocess.check_call(["make", "-s", "-C", CSRC, "-j4", "all"])

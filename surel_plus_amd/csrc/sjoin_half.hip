@@ -16,21 +16,13 @@
 // non-temporal, like every output of the join.
 // A workgroup has 128 lanes, or 256 for batches too small to fill the chip with 128 (half_threads); SPrefetch (sjoin.hpp) is written
 // for 256, so the prefetch of S is restated here for either size.
-#include <hip/hip_bf16.h>
-#include <hip/hip_fp16.h>
-
 #include "../../include/subgacc_half.h"
-#include "sjoin.hpp"
+#include "sjoin_half.hpp"
 
 namespace subgacc {
 
-// f32 -> the 16 bits of the output type, round to nearest even
-template <typename T>
-__device__ __forceinline__ uint32_t half_bits(float f);
-template <>
-__device__ __forceinline__ uint32_t half_bits<__half>(float f) { return __half_as_ushort(__float2half_rn(f)); }
-template <>
-__device__ __forceinline__ uint32_t half_bits<__hip_bfloat16>(float f) { return __bfloat16_as_ushort(__float2bfloat16(f)); }
+// (half_bits -- the rounding to the 16 bits of the output type -- and store_half_row live in sjoin_half.hpp: sjoin_half64.hip rounds
+//  and stores its rows through the same functions)
 
 // count / num_walks as sjoin.hip's lp_quotient computes it: q0 = c * (1/M), r = fma(-M, q0, c), q = fma(r, 1/M, q0) is the correctly
 // rounded quotient for every count a key of num_walks < 4,096 can hold (tests/test_host_logic_cpu.py); larger num_walks divide
@@ -74,27 +66,12 @@ __device__ __forceinline__ void half_row(const JoinArgs &a, const HalfQuot &q, u
     for (int c = 0; c < K; ++c) w[c] = half_bits<T>(f[2 * c]) | (half_bits<T>(f[2 * c + 1]) << 16);
 }
 
-typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-typedef uint32_t v2u __attribute__((ext_vector_type(2)));
-
 // One output row, made from (va, vb) and stored by its lane
 template <int K, bool TAB, typename T>
 __device__ __forceinline__ void emit_half_row(const JoinArgs &a, const HalfQuot &q, uint32_t *out, int64_t row, uint32_t va, uint32_t vb) {
     uint32_t w[K];
     half_row<K, TAB, T>(a, q, va, vb, w);
-    uint32_t *dst = out + row * K;
-    if constexpr (K == 4) {
-        v4u v;
-        v.x = w[0], v.y = w[1], v.z = w[2], v.w = w[3];
-        __builtin_nontemporal_store(v, reinterpret_cast<v4u *>(dst));
-    } else if constexpr (K == 2) {
-        v2u v;
-        v.x = w[0], v.y = w[1];
-        __builtin_nontemporal_store(v, reinterpret_cast<v2u *>(dst));
-    } else {
-#pragma unroll
-        for (int c = 0; c < K; ++c) __builtin_nontemporal_store(w[c], dst + c);
-    }
+    store_half_row<K>(out + row * K, w);
 }
 
 // LDS of sjoin_half_kernel: ids, payload and partner payload of the staged row

@@ -117,17 +117,32 @@ def _half_code(dtype, who, refused):
     return code
 
 
-def _half_store_refusals(x):
+def _half_store_refusals(x, wide_keys=False):
     """what _half_code refuses about the store `x` (anything that is not one of the library's stores is uploaded as a packed SFptr
-    or float store: its payload type says which)"""
+    or float store: its payload type says which).  wide_keys: the strided 64-bit key rows of a step are served
+    (subgacc_sjoin_fill_half64, include/subgacc_half64.h)."""
     data = None if getattr(x, "payload_is_slot", False) else getattr(x, "data", None)
     return {"a HeadedSpG (headed rows)": isinstance(x, HeadedSpG),
             "a float64 store (the PPR payload)": data is not None and str(data.dtype).endswith("float64"),
-            "64-bit keys": bool(getattr(x, "key64", False)),
+            "64-bit keys": bool(getattr(x, "key64", False)) and not (wide_keys and bool(getattr(x, "payload_is_slot", False))),
             "key_rows=False (strided rows of table slots)": bool(getattr(x, "payload_is_slot", False)) and not getattr(x, "keyrows", False)}
 
 
-def sjoin(spg, own, partner, encode=None, ptr_mode=True, return_index=False, pair_block=0, out=None, lazy=False, star=False, dtype=None):
+def _half_shape_refused(num_walks, num_steps, wide_keys):
+    """a step's 16-bit rows exist over its key rows: the 32-bit ones (subgacc_sjoin_fill_half) and -- wide_keys=True -- the 64-bit ones of
+    sampler.key_rows_form == 64 (subgacc_sjoin_fill_half64); not at a shape without key rows"""
+    from .sampler import key_rows_form
+    form = key_rows_form(int(num_walks), int(num_steps))
+    return form != 32 and not (wide_keys and form == 64)
+
+
+def _fill_half(L, kind):
+    """the library's 16-bit row fill for a payload kind: 64-bit keys have an entry point of their own"""
+    return L.subgacc_sjoin_fill_half64 if kind == JOIN_KEY64 else L.subgacc_sjoin_fill_half
+
+
+def sjoin(spg, own, partner, encode=None, ptr_mode=True, return_index=False, pair_block=0, out=None, lazy=False, star=False, dtype=None,
+          wide_keys=False):
     """Generic segment join (include/subgacc.h: the layout's size pass + subgacc_sjoin_fill_v2) over any store: its rows are described
     by spg.join_rows(), its payload by join_payload().
 
@@ -147,12 +162,15 @@ def sjoin(spg, own, partner, encode=None, ptr_mode=True, return_index=False, pai
     callers that train under autocast.  Mirrored lists (pair_block > 0) with segment pointers over a keyed store, the key rows of a
     step or a packed SFptr store with its table, k = 2 .. 5; ValueError for ptr_mode=False, return_index, lazy, star, a HeadedSpG, a
     float64 store, 64-bit keys and rows of table slots.  out=: a buffer of that dtype.  None / torch.float32: the rows as ever.
+    wide_keys=True (with a 16-bit dtype): the strided 64-bit key rows of a step (sampler.key_rows_form == 64: 4 hops, M = 128 .. 204)
+    are joined too, by subgacc_sjoin_fill_half64 (include/subgacc_half64.h) -- the same bits as xz.to(dtype) of their float32 rows;
+    every other refusal stands, and over any other store the keyword changes nothing.
     Returns (xz, ind, flags): xz float32 [R,2,k] (or int32 [R,2] index pairs when return_index), ind = int64 [S+1]
     segment pointers (ptr_mode) or int64 [R] segment ids, flags the join's int32[4] status words.
     """
     half = _half_code(dtype, "sjoin", lambda: {"ptr=False (segment ids)": not ptr_mode, "return_index": return_index, "lazy=True": lazy,
                                                "star=True": star, "a list that is not mirrored (pair_block <= 0)": pair_block <= 0,
-                                               **_half_store_refusals(spg)})
+                                               **_half_store_refusals(spg, wide_keys)})
     L, dev = lib(), spg.device
     S = 2 * partner.numel() if star else own.numel()
     own = own.contiguous()
@@ -199,11 +217,11 @@ def sjoin(spg, own, partner, encode=None, ptr_mode=True, return_index=False, pai
             check(getattr(L, fn)(ptr(lens), spg.n_rows, ptr(own), ptr(partner), S, ptr(seg), ptr(flags), ptr(ws), ws.numel(), st))
         if not lazy:
             R = _size_and_row_check(seg, S, flags, spg.n_rows)     # the one host round trip
-    if half:        # the rows in 16 bits: the same descriptor, no out_* field, the library's second entry point
+    if half:        # the rows in 16 bits: the same descriptor, no out_* field, the library's 16-bit fill for the payload kind
         res = _out_view(out, dev, k, R, dtype=dtype)
         with _timed("sjoin_fill_half"):
             if R:
-                check(L.subgacc_sjoin_fill_half(ctypes.byref(_lib.join_desc(JOIN_ROWS, kind, **desc)), half, ptr(res), st))
+                check(_fill_half(L, kind)(ctypes.byref(_lib.join_desc(JOIN_ROWS, kind, **desc)), half, ptr(res), st))
         return res, seg, flags
     if return_index and kind == JOIN_SFPTR:          # (a float store answers with its xz, as bgather() wants it)
         res = desc["out_idx"] = torch.empty((R, 2), dtype=torch.int32, device=dev)
@@ -284,16 +302,18 @@ def _checked(out, ind, flags, lazy=False):
     return out, ind
 
 
-def gather(edge, x, device=None, ptr=True, encode=None, out=None, lazy=False, dtype=None):
+def gather(edge, x, device=None, ptr=True, encode=None, out=None, lazy=False, dtype=None, wide_keys=False):
     """train.py:13-45.  Left blocks (S_u with S_v looked up) then right blocks, per pair in batch order.
     out= / lazy=: see sjoin (a serving loop's forms: caller-owned output buffer, no host round trip).
-    dtype=torch.float16 / torch.bfloat16: xz in that type (sjoin: what autocast would make of the float32 rows, bit for bit)."""
-    _half_code(dtype, "gather", lambda: {"ptr=False (segment ids)": not ptr, "lazy=True": lazy, **_half_store_refusals(x)})
+    dtype=torch.float16 / torch.bfloat16: xz in that type (sjoin: what autocast would make of the float32 rows, bit for bit);
+    wide_keys=True: also over the 64-bit key rows of a step (sjoin(wide_keys=))."""
+    _half_code(dtype, "gather", lambda: {"ptr=False (segment ids)": not ptr, "lazy=True": lazy, **_half_store_refusals(x, wide_keys)})
     spg = _as_spg(x)
     e = _as_rows(edge, spg.device)
     # own = [u.. | v..] is the contiguous [2, B] tensor itself; the mirrored partner list [v.. | u..] is derived by the kernels
     own = e.contiguous().view(-1)
-    return _checked(*sjoin(spg, own, None, encode, ptr_mode=ptr, pair_block=e.shape[1], out=out, lazy=lazy, dtype=dtype), lazy=lazy)
+    return _checked(*sjoin(spg, own, None, encode, ptr_mode=ptr, pair_block=e.shape[1], out=out, lazy=lazy, dtype=dtype, wide_keys=wide_keys),
+                    lazy=lazy)
 
 
 def _star_rows(source, targets):
@@ -592,7 +612,13 @@ class StepBuffers:
     `ukeys` = 1 .. c instead of `slot`, and answer exactly what they answer at a 32-bit shape.  The buffers hold `ukeys64` int64
     [table_rows - 1] (the sorted distinct keys), `cols` -- 4 bytes per member slot beside the 8 of `slot` -- and a larger `col_ws`;
     `slot` keeps the 64-bit keys.  table_rows <= 8,192 at such a shape (ValueError before any device work); at a shape with 32-bit or
-    small key rows the keyword changes nothing."""
+    small key rows the keyword changes nothing.
+    wide_keys=True with dtype=torch.float16 / torch.bfloat16 and stage=None at such a shape: the row form in 16 bits over the 64-bit key
+    rows -- `self.half64`; `out` is allocated in that type, `slot` stays int64, and the step runs its usual launches and ends in
+    subgacc_sjoin_fill_half64 (include/subgacc_half64.h) instead of the f32 fill: nothing more is allocated or read back, root dedup,
+    order=, rng="rand_r" and out= work as in the f32 step, and `self.wide` stays False (no stage, no columns pass).  Without the keyword
+    the shape is refused as ever, and so are ptr=False, triplets=True, a stage, key_rows=False, batch= and a shape without key rows
+    with it."""
 
     def __init__(self, csr, pairs, num_walks=200, num_steps=3, uniq_capacity=1 << 17, out=None, dedup_roots=False, rng="philox",
                  key_rows=True, sort_roots=True, batch=None, align_rows=True, order=None, ptr=True, triplets=False, stage=None,
@@ -604,9 +630,11 @@ class StepBuffers:
         self.half = _half_code(dtype, "StepBuffers", lambda: {
             "ptr=False (segment ids)": not ptr, "triplets=True": triplets, f"stage={stage!r}": stage is not None,
             "key_rows=False (strided rows of table slots)": not key_rows,
-            f"num_walks = {num_walks}, num_steps = {num_steps} (64-bit keys, or no key rows)": key_rows_form(int(num_walks), int(num_steps)) != 32,
+            f"num_walks = {num_walks}, num_steps = {num_steps} (64-bit keys, or no key rows)": _half_shape_refused(num_walks, num_steps, wide_keys),
             "batch= (many batches per step)": batch is not None})
         self.dtype = dtype if self.half else torch.float32
+        # 16-bit rows over 64-bit key rows (wide_keys=True with a 16-bit dtype at such a shape): the step ends in subgacc_sjoin_fill_half64
+        self.half64 = bool(self.half) and key_rows_form(int(num_walks), int(num_steps)) == 64
         self.stage, self.T = stage, int(table_rows)
         if stage not in (None,) + _KEY_STAGES:
             raise ValueError(f"StepBuffers: stage is None (the row form), 'counts', 'counts_attn' or 'index', not {stage!r}")
@@ -998,9 +1026,9 @@ def _buffered_step(csr, e, bufs, seed, out, fit=False):
         with _timed("sjoin_fill"):
             check(L.subgacc_sjoin_fill_packed(ctypes.byref(_lib.join_desc(JOIN_ROWS, kind, out_xz=xz, **rows, **payload)), ptr(bufs.nesc),
                                               bufs.num_nodes, st))
-    elif bufs.half:       # 16-bit rows (StepBuffers(dtype=): 32-bit key rows, segment pointers)
+    elif bufs.half:       # 16-bit rows (StepBuffers(dtype=): key rows of 32 bits, or -- wide_keys=True -- of 64; segment pointers)
         with _timed("sjoin_fill_half"):
-            check(L.subgacc_sjoin_fill_half(ctypes.byref(_lib.join_desc(JOIN_ROWS, kind, **rows, **payload)), bufs.half, ptr(xz), st))
+            check(_fill_half(L, kind)(ctypes.byref(_lib.join_desc(JOIN_ROWS, kind, **rows, **payload)), bufs.half, ptr(xz), st))
     else:
         with _timed("sjoin_fill"):
             join_fill(JOIN_ROWS, kind, st, out_xz=xz, out_segid=bufs.segid, **rows, **payload)
@@ -1010,7 +1038,7 @@ def _buffered_step(csr, e, bufs, seed, out, fit=False):
 
 
 def sample_and_gather(csr, edge, num_walks=200, num_steps=3, seed=111413, rng="philox", dedup_roots=False, out=None,
-                      lazy=False, strided=None, buffers=None, order=None, ptr=True, dtype=None, **kw):
+                      lazy=False, strided=None, buffers=None, order=None, ptr=True, dtype=None, wide_keys=False, **kw):
     """The on-demand form of the path in one call: sample the endpoints of `edge` [2, B] (node ids), build their SpG
     rows, join -> (xz, indptr, sets), the same (xz, indptr) as `gather(edge, subg_matrix(G, arange(N)))` would give for sets
     drawn with the same RNG (Philox keys every walk by (seed, root id, walk, step), so a root's set does not depend on
@@ -1029,15 +1057,21 @@ def sample_and_gather(csr, edge, num_walks=200, num_steps=3, seed=111413, rng="p
     the output buffer.
     dtype=torch.float16 / torch.bfloat16: xz in that type (sjoin(dtype=): bit for bit the float32 rows under .to(dtype), half the
     bytes written); the step's rows of 32-bit LP keys with segment pointers -- ValueError for ptr=False, lazy=True, key_rows=False,
-    strided=False and a shape with 64-bit keys or without key rows.  buffers= must have been made with the same dtype."""
+    strided=False and a shape with 64-bit keys or without key rows.  buffers= must have been made with the same dtype.
+    wide_keys=True (with a 16-bit dtype): a shape with 64-bit key rows (sampler.key_rows_form == 64: 4 hops, M = 128 .. 204 -- the
+    paper's citation2 setting M = 200) is served too, by subgacc_sjoin_fill_half64 (include/subgacc_half64.h), buffered
+    (StepBuffers(..., dtype=, wide_keys=True)) or not, with or without dedup_roots; the other refusals stand, and at a 32-bit shape
+    the keyword changes nothing."""
     from .sampler import as_rank, key_rows_form
     from .spg import sample_spg
     half = _half_code(dtype, "sample_and_gather", lambda: {
         "ptr=False (segment ids)": not ptr, "lazy=True": lazy, "key_rows=False (strided rows of table slots)": not kw.get("key_rows", True),
         "strided=False (a packed copy of the step's rows)": strided is False,
-        f"num_walks = {num_walks}, num_steps = {num_steps} (64-bit keys, or no key rows)": key_rows_form(int(num_walks), int(num_steps)) != 32})
-    if buffers is not None and half != getattr(buffers, "half", 0):
-        raise ValueError(f"sample_and_gather: dtype={dtype} but buffers= were made with dtype={getattr(buffers, 'dtype', None)}: "
+        f"num_walks = {num_walks}, num_steps = {num_steps} (64-bit keys, or no key rows)": _half_shape_refused(num_walks, num_steps, wide_keys)})
+    half64 = bool(half) and key_rows_form(int(num_walks), int(num_steps)) == 64
+    if buffers is not None and (half != getattr(buffers, "half", 0) or half64 != bool(getattr(buffers, "half64", False))):
+        raise ValueError(f"sample_and_gather: dtype={dtype}{', wide_keys=True' if half64 else ''} but buffers= were made with "
+                         f"dtype={getattr(buffers, 'dtype', None)}{', wide_keys=True' if getattr(buffers, 'half64', False) else ''}: "
                          "StepBuffers(..., dtype=) allocates `out` in the type the step writes")
     order = as_rank(csr, order)
     e = _as_rows(edge, csr.device)
@@ -1073,11 +1107,11 @@ def sample_and_gather(csr, edge, num_walks=200, num_steps=3, seed=111413, rng="p
                          strided=strided, order=order, **kw)
     table = z.slot_table() if sets.strided else sets.feature_table()
     if rows is not None:
-        xz, ind = gather(rows, z, e.device, ptr=bool(ptr), encode=table, out=out, lazy=lazy, dtype=dtype)
+        xz, ind = gather(rows, z, e.device, ptr=bool(ptr), encode=table, out=out, lazy=lazy, dtype=dtype, wide_keys=wide_keys)
     else:
         own, partner = _arange_segments(B, e.device)
-        xz, ind = _checked(*sjoin(_as_spg(z), own, partner, table, ptr_mode=bool(ptr), pair_block=B, out=out, lazy=lazy, dtype=dtype),
-                           lazy=lazy)
+        xz, ind = _checked(*sjoin(_as_spg(z), own, partner, table, ptr_mode=bool(ptr), pair_block=B, out=out, lazy=lazy, dtype=dtype,
+                                  wide_keys=wide_keys), lazy=lazy)
     if lazy:      # the join's status word travels with the sets' own: resolve() raises IndexError for a row outside the store
         sets._join_flags = getattr(ind, "join_flags", None)
     return xz, ind, sets
