@@ -6,18 +6,22 @@ resident in HBM:   2B endpoint roots -> walk + per-root dedup + LP counts (walk_
 global unique LP rows -> SpG (segmented sort) -> Z_SF table -> SpJoin producing xz float32 [R,2,k] + indptr.
 Nothing is cached between steps; every step gets fresh pairs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cit2|collab|ppa] [--pairs B] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cit2|collab|ppa] [--pairs B] [--dump-outputs DIR] [--full]
 
 N>1 is launched by the driver through torch.distributed.run (one rank per GPU); the graph is replicated, the
 pair batches are sharded (each rank its own: "weak"; --scaling strong splits one fixed batch), there is no data-path
 collective.  Rank 0 prints ONE JSON line, the last line of stdout, < 6 KB (compact_line(); the full record with every nested
 block goes to bench_detail.json).  `roofline` is measured live with HIP events around the walk kernel on its
-launch stream; `cpu_baseline` times the reference's own OpenMP sampler (oracle/_ref, compiled from the
-reference sources in the build container) plus the oracle's C merge join on a bounded sample of the workload.
-After the timed region (rank 0, 1 GPU): the random-line roof of this box (tools/line_roof_lib.hip), three more regions of 100
-steps, and BASELINE.json's other configurations as passes of 3 x 100 steps (their medians are scalars of `config`).  `--full` adds the
-side studies (the reference's offline-sample + resident-store-join flow, B = 1,024 loops, hgather, the mean stage, walk_sampler,
-two-stream and root-dedup loops): minutes, bench_detail.json only.
+launch stream, inside the timed region.
+
+A plain run does what the headline figure needs and nothing else: set-up (the graph, the batches, priming), W warm-up steps, the K
+timed steps, --dump-outputs, the line.  Everything else is behind `--full`, after the timed region (rank 0, 1 GPU): `cpu_baseline`
+(the reference's own OpenMP sampler -- oracle/_ref, compiled from the reference sources when the package is built -- plus the
+oracle's C merge join on a bounded sample of the workload), the random-line roof of the machine (tools/line_roof_lib.hip), three more
+regions of 100 steps, the host-fed, two-stream, root-dedup and packed-CSR loops, the reference's offline-sample + resident-store-join
+flow, BASELINE.json's other configurations as passes of 3 x 100 steps (their medians are scalars of `config`), and the side studies of
+tools/bench_studies.py (B = 1,024 loops, hgather, the mean stage, walk_sampler): minutes.  --no-cpu-baseline and --no-others take
+their parts out of a --full run.  The timed steps, `value` and `ms_per_step` are the same with and without --full.
 """
 import argparse
 import contextlib
@@ -402,8 +406,11 @@ def literal_dropin(csr, M, k, n_cpu=32768, nthread_cpu=-1):
 _PPR_STORE = {}
 
 
-def bench_ppr(args, sp, sampler_mod, dev, rank, world, dist, desc, B, K, W, extra_regions=0, layout="aligned", dump_last=False):
+def bench_ppr(args, sp, sampler_mod, dev, rank, world, dist, desc, B, K, W, extra_regions=0, layout="aligned", dump_last=False,
+              kernel_runs=True):
     """SpJoin over a resident float-payload SpG (the citation2 PPR configuration): one step = B pairs -> xz [R,2,1].
+    kernel_runs: after the timed region, launch the join call and its fill kernel alone between HIP events (the `roofline` block's
+    kernel times; a plain run leaves them out and reports the block's times as null).
     layout: "aligned" (round 6, the serving layout: SpG.aligned() -- rows on whole 128-byte lines at a fixed pitch, their lengths in
     their first slots, no row pointers) or "packed" (the CSR the offline stage leaves, as rounds 1-5 joined it).
     dump_last: keep the last timed step's (xz, indptr) for --dump-outputs (rank 0)."""
@@ -503,7 +510,7 @@ def bench_ppr(args, sp, sampler_mod, dev, rank, world, dist, desc, B, K, W, extr
         resolve(pending)
         torch.cuda.synchronize()
         region_values.append(B * K / (time.perf_counter() - t1))
-    if not eager:      # one call at a time, alone on the GPU, between HIP events: what a whole join call takes (size pass + fill)
+    if kernel_runs and not eager:      # one call at a time, alone on the GPU, between HIP events: what a whole join call takes (size pass + fill)
         timer.enabled = True
         for s in range(W, W + 10):
             with timer("join"):
@@ -525,53 +532,62 @@ def bench_ppr(args, sp, sampler_mod, dev, rank, world, dist, desc, B, K, W, extr
         elapsed = world * B * K / median(region_values)
     call_ms, launches = timer.mean_ms("join")       # HIP events around a whole join call alone on the GPU: the size pass and the fill
     ms, _ = timer.mean_ms("sjoin_fill")             # the fill kernel alone (eager mode only: events do not time inside a replayed graph)
-    from surel_plus_amd import _lib as lib_
-    xz_e, ind_e = sp.gather(edges[W], z, dev, ptr=True, encode=None, out=torch.empty(2 * B * z.max_len * 2, dtype=torch.float32, device=dev), lazy=True)
-    own_e = edges[W].contiguous().view(-1)
 
-    def fill_alone():       # the fill kernel of one batch, sizes known: one launch
-        lib_.join_fill(lib_.JOIN_ROWS, lib_.JOIN_F64, n_rows=z.n_rows, payload=z.data, own=own_e, S=own_e.numel(), seg=ind_e, pair_block=B,
-                       out_xz=xz_e, flags=ind_e.join_flags,
-                       **(dict(row_stride=z.pitch, ids=z.ids) if layout == "aligned" else dict(row_off=z.indptr, ids=z.indices, max_len=z.max_len)))
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    if ms is None and layout == "aligned":
-        # a lazy gather from a headed store is ONE library call (size pass + fill, what join_graph_ms times): the fill alone is
-        # launched here, on the segments of one of the timed batches, one launch per event pair
-        one = []
-        for _ in range(6):
+    def fill_kernel_runs(ms):
+        """the fill kernel alone after the region: -> (ms of a single launch, how it was taken, ms per launch of ten back to back)"""
+        from surel_plus_amd import _lib as lib_
+        xz_e, ind_e = sp.gather(edges[W], z, dev, ptr=True, encode=None, out=torch.empty(2 * B * z.max_len * 2, dtype=torch.float32, device=dev), lazy=True)
+        own_e = edges[W].contiguous().view(-1)
+
+        def fill_alone():       # the fill kernel of one batch, sizes known: one launch
+            lib_.join_fill(lib_.JOIN_ROWS, lib_.JOIN_F64, n_rows=z.n_rows, payload=z.data, own=own_e, S=own_e.numel(), seg=ind_e, pair_block=B,
+                           out_xz=xz_e, flags=ind_e.join_flags,
+                           **(dict(row_stride=z.pitch, ids=z.ids) if layout == "aligned" else dict(row_off=z.indptr, ids=z.indices, max_len=z.max_len)))
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        if ms is None and layout == "aligned":
+            # a lazy gather from a headed store is ONE library call (size pass + fill, what join_graph_ms times): the fill alone is
+            # launched here, on the segments of one of the timed batches, one launch per event pair
+            one = []
+            for _ in range(6):
+                ev0.record()
+                fill_alone()
+                ev1.record()
+                torch.cuda.synchronize()
+                one.append(ev0.elapsed_time(ev1))
+            fill_ms = sum(one[1:]) / len(one[1:])
+            ms, ms_source = fill_ms, "HIP events around single launches of the fill kernel on one batch of the timed region, sizes known (after the region)"
+        elif ms is None:                                # ... so a few eager joins after the timed region time it, for the record
+            ebuf = torch.empty(2 * B * z.max_len * 2, dtype=torch.float32, device=dev)
+            timer.pairs.pop("sjoin_fill", None)
+            sampler_mod.KERNEL_TIMER = timer
+            timer.enabled = True
+            for s in range(W, W + min(K, 5)):
+                sp.gather(edges[s], z, dev, ptr=True, encode=None, out=ebuf, lazy=True)
+            torch.cuda.synchronize()
+            timer.enabled = False
+            sampler_mod.KERNEL_TIMER = None
+            fill_ms, _ = timer.mean_ms("sjoin_fill")
+            ms, ms_source = fill_ms, ("HIP events around the fill kernel of gather(lazy=True) launches of the same joins right after the timed region "
+                                      "(the timed region's call holds the size pass and the fill: join_graph_ms is that whole call)")
+        else:
+            fill_ms, ms_source = ms, "HIP events around the fill kernel in the timed region"
+        # an event pair around ONE launch of a ~60 us kernel reads 4-6 us more than the kernel runs (rocprofv3's kernel trace of the
+        # same launches is the arbiter: profiles/rNN_cit2ppr_kernel_stats.csv): the same fill ten times back to back between one pair
+        b2b = []
+        for _ in range(3):
             ev0.record()
-            fill_alone()
+            for _ in range(10):
+                fill_alone()
             ev1.record()
             torch.cuda.synchronize()
-            one.append(ev0.elapsed_time(ev1))
-        fill_ms = sum(one[1:]) / len(one[1:])
-        ms, ms_source = fill_ms, "HIP events around single launches of the fill kernel on one batch of the timed region, sizes known (after the region)"
-    elif ms is None:                                # ... so a few eager joins after the timed region time it, for the record
-        ebuf = torch.empty(2 * B * z.max_len * 2, dtype=torch.float32, device=dev)
-        timer.pairs.pop("sjoin_fill", None)
-        sampler_mod.KERNEL_TIMER = timer
-        timer.enabled = True
-        for s in range(W, W + min(K, 5)):
-            sp.gather(edges[s], z, dev, ptr=True, encode=None, out=ebuf, lazy=True)
-        torch.cuda.synchronize()
-        timer.enabled = False
-        sampler_mod.KERNEL_TIMER = None
-        fill_ms, _ = timer.mean_ms("sjoin_fill")
-        ms, ms_source = fill_ms, ("HIP events around the fill kernel of gather(lazy=True) launches of the same joins right after the timed region "
-                                  "(the timed region's call holds the size pass and the fill: join_graph_ms is that whole call)")
-    else:
-        fill_ms, ms_source = ms, "HIP events around the fill kernel in the timed region"
-    # an event pair around ONE launch of a ~60 us kernel reads 4-6 us more than the kernel runs (rocprofv3's kernel trace of the
-    # same launches is the arbiter: profiles/rNN_cit2ppr_kernel_stats.csv): the same fill ten times back to back between one pair
-    b2b = []
-    for _ in range(3):
-        ev0.record()
-        for _ in range(10):
-            fill_alone()
-        ev1.record()
-        torch.cuda.synchronize()
-        b2b.append(ev0.elapsed_time(ev1) / 10)
-    b2b_ms = median(b2b)
+            b2b.append(ev0.elapsed_time(ev1) / 10)
+        b2b_ms = median(b2b)
+        return ms, ms_source, b2b_ms
+    ms_source = b2b_ms = None
+    if kernel_runs:
+        ms, ms_source, b2b_ms = fill_kernel_runs(ms)
+    elif ms is not None:
+        ms_source = "HIP events around the fill kernel in the timed region"
     steady_ms = world * B / median(region_values) * 1e3          # the loop's period per call (per rank)
     abytes = B * 64 + rows_out * (12 + 8)      # SURVEY 8(d): 64 + (|S_u|+|S_v|) * (12 read: id + f64 payload, 8 written: f32 [.,2,1])
     traffic = None
@@ -580,6 +596,12 @@ def bench_ppr(args, sp, sampler_mod, dev, rank, world, dist, desc, B, K, W, extr
         tj = json.load(open(tpath)).get(f"cit2ppr:{B}:join" + (":aligned" if layout == "aligned" else ""), {})
         if tj.get("kernel_source_sha") == kernel_source_sha():
             traffic = tj.get("join_hbm_bytes_per_launch")
+
+    def gbs(kernel_ms):       # the algorithmic bytes over a kernel time that a plain run may not have
+        return abytes / (kernel_ms * 1e-3) / 1e9 if kernel_ms else None
+
+    def frac(kernel_ms):
+        return gbs(kernel_ms) / HBM_PEAK_GBS if kernel_ms else None
     return {"metric": "query-pairs/sec (SpJoin, PPR payload)", "value": world * B * K / elapsed, "unit": "query-pairs/s",
             "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": elapsed / K * 1e3, "higher_is_better": True,
             "scaling": args.scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
@@ -604,13 +626,14 @@ def bench_ppr(args, sp, sampler_mod, dev, rank, world, dist, desc, B, K, W, extr
             # fill (profiles/r70_cit2ppr_kernel_stats.csv: 58.8 us without the first, cold launch) sides with the average of ten
             # (57.8 us in that call), not with the single-launch reading (64.8 us), which stays beside it as *_single_launch
             "roofline": {"bound": "hbm", "kernel": "sjoin_f64pair_kernel<64> (one wave per pair)",
-                         "achieved": abytes / (b2b_ms * 1e-3) / 1e9,
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": abytes / (b2b_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                         "achieved": gbs(b2b_ms),
+                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": frac(b2b_ms),
                          "traffic": traffic, "kernel_ms": b2b_ms,
-                         "kernel_ms_source": "ten launches of the fill kernel back to back between one pair of HIP events, / 10; median of 3",
+                         "kernel_ms_source": ("ten launches of the fill kernel back to back between one pair of HIP events, / 10; median of 3"
+                                              if kernel_runs else "not launched alone: --full does"),
                          "kernel_ms_single_launch": ms, "kernel_ms_single_launch_source": ms_source,
-                         "frac_single_launch": abytes / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "kernel_ms_x10_back_to_back": b2b_ms, "frac_x10_back_to_back": abytes / (b2b_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                         "frac_single_launch": frac(ms),
+                         "kernel_ms_x10_back_to_back": b2b_ms, "frac_x10_back_to_back": frac(b2b_ms),
                          "join_graph_ms": call_ms, "frac_whole_join": (abytes / (call_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if call_ms else None,
                          "launches_timed": launches, "algorithmic_bytes_per_launch": abytes}}
 
@@ -622,9 +645,10 @@ def median(v):
 
 def bench_lp(args, name, rng, B, K, W, sp, sampler_mod, dev, rank, world, dist, with_cpu_baseline, csr_variant=True,
              small_batches=False, two_stream_extra=True, dedup_extra=None, offline=False, extra_regions=(0, 0), value_is_median=False, captured=False,
-             cpu_kw={}, wake_s=0.0, host_fed=False, ref_flow=False, dump_last=False):
+             cpu_kw={}, wake_s=0.0, host_fed=False, ref_flow=False, dump_last=False, line_roof=True):
     """sample + SpJoin over one LP workload: W warm-up steps, K timed steps bracketed by barrier + synchronize, max over
     ranks.  Returns the JSON object (rank 0) or None.
+    line_roof: launch the random-line probe after the region (roofline.random_line_roof; a plain run leaves it out).
     dump_last: keep the last timed step's (xz, indptr) for --dump-outputs (rank 0; not with captured).
     extra_regions = (R, Kx): after the timed region, R more regions of Kx steps each in the same loop (rank 0, 1 GPU): their
     pairs/s as min / median / max -- the timed region of the driver's K steps is ~25 ms, one host hiccup away from any number;
@@ -856,7 +880,7 @@ def bench_lp(args, name, rng, B, K, W, sp, sampler_mod, dev, rank, world, dist, 
         if tj.get("kernel_source_sha") == kernel_source_sha():
             traffic, lines = tj.get("walk_sets_hbm_bytes_per_launch"), tj.get("walk_sets_l2_miss_lines_per_launch")
             join_traffic = tj.get("join_hbm_bytes_per_launch")
-    roof, roof_bytes, roof_table = measure_line_roof(csr) if rank == 0 else (None, None, None)
+    roof, roof_bytes, roof_table = measure_line_roof(csr) if (rank == 0 and line_roof) else (None, None, None)
     # SURVEY 8(d), SpJoin: per pair 16 (query ids) + 32 (4 row offsets) + 16 (two segment pointers) and per output row 8 read
     # (id + payload) + 8k written (float32 [.,2,k])
     join_abytes = (B * 64 + last_rows * (8 + 8 * k)) if last_rows is not None else None
@@ -920,7 +944,7 @@ def bench_lp(args, name, rng, B, K, W, sp, sampler_mod, dev, rank, world, dist, 
                      "random_line_roof": {"lines_per_s": roof, "line_bytes": LINE_BYTES, "table_bytes": roof_bytes,
                                           "source": (f"tools/line_roof_lib.hip in this run: independent random 4-byte reads over the {roof_table} "
                                                      f"({roof_bytes >> 20} MiB), 2048 x 256 lanes, best of 3 (study: profiles/r02_line_probe_pmc.csv)")
-                                          if roof else "tools/build/libsubgacc_probe.so not built",
+                                          if roof else ("tools/build/libsubgacc_probe.so not built" if line_roof else "not measured: --full does"),
                                           "l2_miss_lines_per_launch": lines,
                                           "achieved_lines_per_s": (lines / (walk_ms * 1e-3)) if (lines and walk_ms) else None,
                                           "frac": (lines / (walk_ms * 1e-3) / roof) if (lines and walk_ms and roof) else None}},
@@ -940,7 +964,7 @@ def bench_lp(args, name, rng, B, K, W, sp, sampler_mod, dev, rank, world, dist, 
         except Exception as ex:  # the baseline is a report, never a reason to lose the measurement
             out["cpu_baseline"] = {"value": None, "unit": "query-pairs/s", "cores": os.cpu_count(), "kind": "port",
                                    "sample": f"failed: {type(ex).__name__}: {ex}"}
-    if ref_flow and not offline:     # SURVEY 8(d)'s S / J / Q on the reference's own flow: part of the default run since round 6 (~1.5 s)
+    if ref_flow and not offline:     # SURVEY 8(d)'s S / J / Q on the reference's own flow (~1.5 s; the side studies' offline_flow holds them too)
         try:
             flow = reference_flow(sp, csr, M, k, B)[0]
             out["config"]["offline_flow"] = flow
@@ -1353,7 +1377,7 @@ def summary(o):
     return keep
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -1361,11 +1385,14 @@ def main():
     ap.add_argument("--workload", default="cit2", choices=sorted(WORKLOADS))
     ap.add_argument("--pairs", type=int, default=65536, help="query pairs per step per GPU")
     ap.add_argument("--rng", default="philox", choices=["philox", "rand_r"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-others", action="store_true", help="skip the short passes over BASELINE.json's other configs")
     ap.add_argument("--full", action="store_true",
-                    help="also run the side studies (two-stream and root-dedup loops, packed-CSR variant, B=1,024 sweeps, the reference's "
-                         "offline flow, hgather, mean stage, walk_sampler): minutes, all of it into bench_detail.json")
+                    help="after the timed region, also measure everything else: the CPU baseline, more regions of the same loop, the "
+                         "random-line roof, the host-fed / two-stream / root-dedup / packed-CSR loops, the reference's offline flow, "
+                         "BASELINE.json's other configurations, and the side studies (B=1,024 sweeps, hgather, mean stage, walk_sampler): "
+                         "minutes, all of it into bench_detail.json.  Without it a run sets up, warms up, times its steps and prints its line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baselines")
+    ap.add_argument("--no-others", action="store_true",
+                    help="with --full: leave out the passes over BASELINE.json's other configurations and the extra loops of the headline one")
     ap.add_argument("--scale", type=float, default=1.0, help="shrink the graph (debug only; invalidates the number)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: --pairs per step PER GPU (the driver's scaling runs); strong: --pairs per step in all, split over "
@@ -1373,7 +1400,31 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="write what the last timed step returned (rank 0) as DIR/<name>.npy: xz float32, indptr float64 and "
                          "xz_segments float64 (the segments whose rows xz holds: all of them, or a fixed seeded sample within 64 MB)")
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def headline_extras(args, rank, world):
+    """which measurements of bench_lp follow the headline workload's timed region (its keyword arguments): none in a plain run --
+    set-up, warm-up, the timed steps, the line -- and, with --full on one GPU, all of them but those --no-others / --no-cpu-baseline take out"""
+    one_gpu = args.full and world == 1
+    others = one_gpu and not args.no_others
+    whole_graph = rank == 0 and args.scale == 1.0        # (the offline flows sample every node of the full-size graph)
+    return dict(with_cpu_baseline=one_gpu and not args.no_cpu_baseline,
+                line_roof=args.full,
+                # three more regions of 100 steps in the same loop
+                extra_regions=(3, 100) if others else (0, 0),
+                # K more steps with two step buffers in turn on two streams (what a serving loop gains by it); not with --no-others:
+                # that is the command the profiles are taken with, and kernels that overlap on two streams would spoil its
+                # per-kernel averages
+                two_stream_extra=others, host_fed=others,
+                # SURVEY 8(d)'s S / J / Q on the reference's own flow (~1.5 s)
+                ref_flow=others and whole_graph and not args.workload.startswith("twitter"),
+                # the pass with every distinct endpoint sampled once, the packed-CSR (table rows) variant, the side studies
+                dedup_extra=args.full, csr_variant=args.full, small_batches=one_gpu, offline=one_gpu and whole_graph)
+
+
+def main():
+    args = parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -1423,23 +1474,10 @@ def main():
     t_start = time.perf_counter()
     if WORKLOADS[args.workload][0] is None:
         out = bench_ppr(args, sp, sampler_mod, dev, rank, world, dist, WORKLOADS[args.workload][3], B, K, W,
-                        layout=os.environ.get("SUBGACC_PPR_LAYOUT", "aligned"), dump_last=bool(args.dump_outputs))
+                        layout=os.environ.get("SUBGACC_PPR_LAYOUT", "aligned"), dump_last=bool(args.dump_outputs), kernel_runs=args.full)
     else:
         out = bench_lp(args, args.workload, args.rng, B, K, W, sp, sampler_mod, dev, rank, world, dist,
-                       with_cpu_baseline=(world == 1 and not args.no_cpu_baseline),
-                       small_batches=(world == 1 and args.full),
-                       # outside the clock, K more steps with two step buffers in turn on two streams (what a serving loop gains by it);
-                       # the pass with every distinct endpoint sampled once: --full only
-                       # (not with --no-others: that is the command the profiles are taken with, and kernels that overlap on two
-                       #  streams would spoil its per-kernel averages)
-                       two_stream_extra=not args.no_others, dedup_extra=args.full,
-                       csr_variant=args.full,                    # ... and no pass with the packed-CSR (table rows) variant
-                       offline=(rank == 0 and world == 1 and args.full and args.scale == 1.0),
-                       ref_flow=(rank == 0 and world == 1 and not args.no_others and args.scale == 1.0 and not args.workload.startswith("twitter")),
-                       host_fed=not args.no_others,
-                       # the driver's K steps are the headline region; three regions of 100 steps follow, outside its clock
-                       extra_regions=((3, 100) if (world == 1 and not args.no_others) else (0, 0)),
-                       dump_last=bool(args.dump_outputs))
+                       dump_last=bool(args.dump_outputs), **headline_extras(args, rank, world))
     if rank == 0 and out is not None:
         note(f"{args.workload}: {out['value'] / 1e6:.2f} M pairs/s in the driver's region of {K} steps")
     if rank == 0 and args.dump_outputs:
@@ -1448,7 +1486,7 @@ def main():
     # BASELINE.json's other single-GPU configurations (and the reference-bit-exact rand_r stream on the headline one),
     # as short passes after the timed region: same code path, >= 5 timed steps each, their own roofline blocks
     # (configs[0], the reference's CPU-runnable collab case, rides on the collab entry as its cpu_baseline).
-    if rank == 0 and world == 1 and not args.no_others and args.workload == "cit2" and args.rng == "philox" and args.scale == 1.0:
+    if args.full and rank == 0 and world == 1 and not args.no_others and args.workload == "cit2" and args.rng == "philox" and args.scale == 1.0:
         others = {}
         budget_s = float(os.environ.get("SUBGACC_OTHERS_BUDGET_S", "900"))
         for key, (wl, rng_o) in {"cit2 (rng=rand_r: the reference's own stream, bit-exact mode)": ("cit2", "rand_r"),
@@ -1475,9 +1513,7 @@ def main():
                 else:
                     o = bench_lp(args, wl, rng_o, B, Ko, Wo, sp, sampler_mod, dev, 0, 1, None,
                                  with_cpu_baseline=(wl == "collab" and not args.no_cpu_baseline), csr_variant=False,
-                                 two_stream_extra=args.full, extra_regions=(2, Ko), value_is_median=True, wake_s=0.25,
-                                 # configs[0] (the reference's CPU-runnable case): 16 threads and the probe's pick only, ~1.5 s each
-                                 cpu_kw=({} if args.full else {"target_s": 1.5, "teams": (-1, 16, 8), "with_t1": False}),
+                                 two_stream_extra=True, extra_regions=(2, Ko), value_is_median=True, wake_s=0.25,
                                  # a 2-hop step is ~0.4 ms of kernels: replayed as one HIP graph, or the host is what gets measured
                                  captured=(WORKLOADS[wl][2] <= 3))
                 others[key] = summary(o)
@@ -1491,12 +1527,11 @@ def main():
                         others[key]["literal_dropin"] = {"failed": f"{type(ex).__name__}: {ex}"}
             except Exception as ex:   # an extra must never cost the headline line
                 others[key] = {"failed": f"{type(ex).__name__}: {ex}"}
-        if args.full:
-            try:
-                torch.cuda.empty_cache()
-                others["walk_sampler (collab)"] = bench_studies().bench_walk_sampler(sp, sampler_mod, dev, 5)
-            except Exception as ex:
-                others["walk_sampler (collab)"] = {"failed": f"{type(ex).__name__}: {ex}"}
+        try:
+            torch.cuda.empty_cache()
+            others["walk_sampler (collab)"] = bench_studies().bench_walk_sampler(sp, sampler_mod, dev, 5)
+        except Exception as ex:
+            others["walk_sampler (collab)"] = {"failed": f"{type(ex).__name__}: {ex}"}
         out["config"]["other_workloads"] = others
     if rank == 0:
         emit(out)

@@ -161,3 +161,23 @@ def test_dump_outputs_keep_whole_segments_of_a_fixed_sample(tmp_path, monkeypatc
     again = bench.step_outputs(xz, indptr)
     for name, a in again.items():
         assert np.array_equal(np.load(tmp_path / "d" / f"{name}.npy"), a)
+
+
+def test_plain_run_measures_nothing_behind_its_steps():
+    """a plain `bench.py --gpus 1 --steps K --warmup W` asks bench_lp for no measurement after the timed region; --full asks for all of
+    them, less what --no-others / --no-cpu-baseline take out; neither flag adds anything to a plain run"""
+    import bench
+    plain = bench.headline_extras(bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"]), 0, 1)
+    assert plain.pop("extra_regions") == (0, 0)
+    assert plain and not any(plain.values()), plain
+    for flags in (["--no-others"], ["--no-cpu-baseline"], ["--no-others", "--no-cpu-baseline"]):
+        assert bench.headline_extras(bench.parse_args(flags), 0, 1) == dict(plain, extra_regions=(0, 0))
+    full = bench.headline_extras(bench.parse_args(["--full"]), 0, 1)
+    assert set(full) == set(plain) | {"extra_regions"}
+    assert full.pop("extra_regions") == (3, 100) and all(full.values()), full
+    lean = bench.headline_extras(bench.parse_args(["--full", "--no-others", "--no-cpu-baseline"]), 0, 1)
+    assert lean["extra_regions"] == (0, 0) and not lean["with_cpu_baseline"] and not lean["two_stream_extra"] and not lean["host_fed"]
+    assert lean["line_roof"] and lean["small_batches"] and lean["offline"]
+    # more than one rank: the per-rank loops alone (the extras are rank 0's on one GPU)
+    many = bench.headline_extras(bench.parse_args(["--full", "--gpus", "8"]), 0, 8)
+    assert not many["with_cpu_baseline"] and many["extra_regions"] == (0, 0) and not many["offline"] and not many["small_batches"]

@@ -116,7 +116,7 @@ def offline_flow(sp, csr, M, k, B, K, cpu):
     from surel_plus_amd.graphs import query_pairs
     from surel_plus_amd.spg import sample_spg
     dev, N = csr.device, csr.num_nodes
-    # S / J / Q themselves are part of the default run since round 6 (bench.reference_flow); what --full adds follows
+    # S / J / Q themselves: bench.reference_flow; what this study adds to them follows
     base, z, sets, enc, table, zk = bench.reference_flow(sp, csr, M, k, B)
     idx = torch.arange(N, dtype=torch.int32, device=dev)
     # the paper's own sampler figure (Fig. 6a: citation2, m = 4, M = 200 -- 143..302 s on 16..1 CPU threads "incl. encoding + SpG

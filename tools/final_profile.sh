@@ -35,6 +35,8 @@ cp profiles/traffic.json gpurun_out/${TAG}_traffic.json
 bash tools/pmc_sq.sh gpurun_out/${TAG}_sq_cit2_passes --workload cit2 > gpurun_out/${TAG}_sq_cit2.csv 2> gpurun_out/${TAG}_sq_cit2.err
 bash tools/pmc_sq.sh gpurun_out/${TAG}_sq_cit2loc_passes --workload cit2loc > gpurun_out/${TAG}_sq_cit2loc.csv 2> gpurun_out/${TAG}_sq_cit2loc.err
 bash tools/pmc_sq.sh gpurun_out/${TAG}_sq_collab_passes --workload collab > gpurun_out/${TAG}_sq_collab.csv 2> gpurun_out/${TAG}_sq_collab.err
-( time python bench.py --steps 20 --warmup 5 ) > gpurun_out/${TAG}_bench_cit2.json 2> gpurun_out/${TAG}_bench_cit2.err
-cp bench_detail.json gpurun_out/${TAG}_bench_cit2_detail.json
-tail -c 1500 gpurun_out/${TAG}_bench_cit2.json; tail -5 gpurun_out/${TAG}_bench_cit2.err
+# the whole line: every configuration, the CPU baseline, the roofs and the side studies (a plain run prints the headline workload alone)
+OUT=${FP_OUT:-/tmp}
+( time python bench.py --full --steps 20 --warmup 5 ) > $OUT/${TAG}_bench_cit2.json 2> $OUT/${TAG}_bench_cit2.err
+cp bench_detail.json $OUT/${TAG}_bench_cit2_detail.json
+tail -c 1500 $OUT/${TAG}_bench_cit2.json; tail -5 $OUT/${TAG}_bench_cit2.err
