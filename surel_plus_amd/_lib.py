@@ -1,7 +1,7 @@
 """ctypes binding of libsubgacc_hip.so, derived from the declarations of include/subgacc.h (the C ABI), of include/subgacc_half.h
 (the join's rows in a 16-bit type), of include/subgacc_small.h (key rows for the small walk shapes), of include/subgacc_packed.h
-(the step's key rows as one word per member), of include/subgacc_wide.h (the columns of 64-bit key rows) and of include/subgacc_half64.h
-(the 16-bit rows over 64-bit key rows) when this module is imported: an entry point is declared there and defined under csrc/, and
+(the step's key rows as one word per member), of include/subgacc_wide.h (the columns of 64-bit key rows), of include/subgacc_half64.h
+(the 16-bit rows over 64-bit key rows) and of include/subgacc_packed_half.h (the packed rows joined in 16 bits) when this module is imported: an entry point is declared there and defined under csrc/, and
 nothing here names it.
 
 There is no CPU fallback: if the library is missing, or no gfx950 device is visible when a compute entry
@@ -140,6 +140,11 @@ HALF64_HEADER = os.path.join(os.path.dirname(HEADER), "subgacc_half64.h")
 HALF64_DECLS = parse_header(_header_text(HALF64_HEADER))
 _TYPES.update(bind_types(HALF64_DECLS))
 HALF64_SYMBOLS = tuple(HALF64_DECLS)
+# the seventh header: the join over the step's packed rows written in a 16-bit type (csrc/sjoin_packed_half.hip), the same library
+PACKED_HALF_HEADER = os.path.join(os.path.dirname(HEADER), "subgacc_packed_half.h")
+PACKED_HALF_DECLS = parse_header(_header_text(PACKED_HALF_HEADER))
+_TYPES.update(bind_types(PACKED_HALF_DECLS))
+PACKED_HALF_SYMBOLS = tuple(PACKED_HALF_DECLS)
 HALF_F16, HALF_BF16 = (int(re.search(rf"^#define\s+SUBGACC_HALF_{n}\s+(\d+)", _HALF_TEXT, re.M).group(1)) for n in ("F16", "BF16"))
 
 
@@ -151,7 +156,7 @@ VERBOSE = os.environ.get("SUBGACC_QUIET", "0") != "1"
 def build(force=False):
     """hipcc-compile csrc/*.hip for gfx950 into surel_plus_amd/libsubgacc_hip.so (in-tree)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))]
-    srcs += [HEADER, HALF_HEADER, SMALL_HEADER, PACKED_HEADER, WIDE_HEADER, HALF64_HEADER]
+    srcs += [HEADER, HALF_HEADER, SMALL_HEADER, PACKED_HEADER, WIDE_HEADER, HALF64_HEADER, PACKED_HALF_HEADER]
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
         subprocess.check_call(["make", "-s", "-C", CSRC, "-j4", "all"])

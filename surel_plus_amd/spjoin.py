@@ -605,6 +605,12 @@ class StepBuffers:
     32-bit key rows of a two-wave form on a graph whose ids leave three bits a count (sampler.packed_rows_form).  True: the same, and
     ValueError where it does not exist.  False: the two planes.  `ids` and `slot` show today's rows either way: of a packed step
     they are unpacked when first looked at (subgacc_unpack_packed_rows, into planes allocated then), never in the step.
+    packed_half=True (with dtype=torch.float16 / torch.bfloat16): both at once -- the packed hand-over under the 16-bit rows,
+    `self.packed` and `self.half` -- where sampler.packed_rows_form has a form; the walk writes the packed rows as in the f32 step
+    and the step ends in subgacc_sjoin_fill_packed_half (include/subgacc_packed_half.h): six launches, nothing allocated or read
+    back, (xz, indptr) bit for bit those of StepBuffers(dtype=).  Opt-in: without it a 16-bit step keeps the two planes
+    (profiles/packed_half_bench.log has both).  ValueError naming the keyword without a 16-bit dtype, for packed_rows=False,
+    ptr=False, triplets=True, a stage, key_rows=False, batch= and a shape or graph without a packed form (64-bit keys included).
     wide_keys=True: a stage ("counts", "counts_attn", "index") over the 64-bit key rows of a 4-hop shape with M = 128 .. 204
     (sampler.key_rows_form == 64: the paper's citation2 setting M = 200, m = 4), which the stages refuse otherwise -- `self.wide`.
     The columns pass is subgacc_keyrows_columns64 (include/subgacc_wide.h: one launch more than the 32-bit step), which also writes
@@ -622,9 +628,19 @@ class StepBuffers:
 
     def __init__(self, csr, pairs, num_walks=200, num_steps=3, uniq_capacity=1 << 17, out=None, dedup_roots=False, rng="philox",
                  key_rows=True, sort_roots=True, batch=None, align_rows=True, order=None, ptr=True, triplets=False, stage=None,
-                 table_rows=2048, dtype=None, packed_rows=None, wide_keys=False):
+                 table_rows=2048, dtype=None, packed_rows=None, wide_keys=False, packed_half=False):
         from .sampler import FUSED_MAX_Q, as_rank, key_rows_form, packed_rows_form, small_rows_form
         self.packed, self._unpacked, self._unpacked_step = False, None, -1
+        if packed_half:     # opt-in: the packed hand-over under the 16-bit rows, refused before anything touches the device
+            why = {f"dtype={dtype} (the packed rows are joined in 16 bits with dtype=torch.float16 / torch.bfloat16; the f32 step is packed "
+                   "by itself)": dtype not in (torch.float16, torch.bfloat16),
+                   "packed_rows=False": packed_rows is False, "ptr=False": not ptr, "triplets=True": bool(triplets),
+                   f"stage={stage!r}": stage is not None, "key_rows=False": not key_rows, "batch= (many batches per step)": batch is not None,
+                   f"no packed form for {int(csr.num_nodes)} nodes, num_walks = {num_walks}, num_steps = {num_steps} "
+                   "(sampler.packed_rows_form: 32-bit key rows of a two-wave form, three bits a count beside the id)":
+                       packed_rows_form(csr.num_nodes, num_walks, num_steps, csr.indptr.dtype == torch.int64) is None}
+            if any(why.values()):
+                raise ValueError("StepBuffers(packed_half=True): " + "; ".join(k for k, v in why.items() if v))
         # a stage over 64-bit key rows (wide_keys=True at such a shape, nothing anywhere else): the columns pass of csrc/keycols64.hip
         self.wide = bool(wide_keys) and stage in _KEY_STAGES and bool(key_rows) and key_rows_form(int(num_walks), int(num_steps)) == 64
         self.half = _half_code(dtype, "StepBuffers", lambda: {
@@ -705,7 +721,8 @@ class StepBuffers:
         # packed rows: `_ids` takes the words, `_slot` the escape lists, `nesc` their lengths; nothing else of the buffers changes
         self.num_nodes = int(csr.num_nodes)
         fmt = packed_rows_form(self.num_nodes, self.M, self.m, csr.indptr.dtype == torch.int64)
-        why = {"key_rows=False": not key_rows, f"stage={stage!r}": stage is not None, "a 16-bit dtype": bool(self.half),
+        why = {"key_rows=False": not key_rows, f"stage={stage!r}": stage is not None,
+               "a 16-bit dtype (without packed_half=True)": bool(self.half) and not packed_half,
                "ptr=False": not self.ptr, "triplets=True": self.triplets, "batch= (many batches per step)": self.batch != self.B,
                f"no packed form for {self.num_nodes} nodes, num_walks = {self.M}, num_steps = {self.m} (sampler.packed_rows_form)": fmt is None}
         if packed_rows and any(why.values()):
@@ -1022,7 +1039,11 @@ def _buffered_step(csr, e, bufs, seed, out, fit=False):
     xz = _out_view(out if out is not None else bufs.out, dev, k, worst=S * bufs.Q, dtype=bufs.dtype)
     rows = dict(row_len=bufs.nsize, n_rows=n, row_stride=bufs.stride, ids=bufs._ids, payload=bufs._slot, own=own, partner=partner, S=S,
                 seg=bufs.seg, pair_block=PB, flags=flags)
-    if bufs.packed:     # one word per member and the escape lists: the same rows of xz
+    if bufs.packed and bufs.half:     # one word per member and the escape lists, 16-bit rows (StepBuffers(dtype=, packed_half=True))
+        with _timed("sjoin_fill_packed_half"):
+            check(L.subgacc_sjoin_fill_packed_half(ctypes.byref(_lib.join_desc(JOIN_ROWS, kind, **rows, **payload)), ptr(bufs.nesc),
+                                                   bufs.num_nodes, bufs.half, ptr(xz), st))
+    elif bufs.packed:     # one word per member and the escape lists: the same rows of xz
         with _timed("sjoin_fill"):
             check(L.subgacc_sjoin_fill_packed(ctypes.byref(_lib.join_desc(JOIN_ROWS, kind, out_xz=xz, **rows, **payload)), ptr(bufs.nesc),
                                               bufs.num_nodes, st))
