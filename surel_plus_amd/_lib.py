@@ -1,7 +1,8 @@
 """ctypes binding of libsubgacc_hip.so, derived from the declarations of include/subgacc.h (the C ABI), of include/subgacc_half.h
 (the join's rows in a 16-bit type), of include/subgacc_small.h (key rows for the small walk shapes), of include/subgacc_packed.h
 (the step's key rows as one word per member), of include/subgacc_wide.h (the columns of 64-bit key rows), of include/subgacc_half64.h
-(the 16-bit rows over 64-bit key rows) and of include/subgacc_packed_half.h (the packed rows joined in 16 bits) when this module is imported: an entry point is declared there and defined under csrc/, and
+(the 16-bit rows over 64-bit key rows), of include/subgacc_packed_half.h (the packed rows joined in 16 bits) and of
+include/subgacc_half_ids.h (the 16-bit rows with their segment ids) when this module is imported: an entry point is declared there and defined under csrc/, and
 nothing here names it.
 
 There is no CPU fallback: if the library is missing, or no gfx950 device is visible when a compute entry
@@ -145,6 +146,11 @@ PACKED_HALF_HEADER = os.path.join(os.path.dirname(HEADER), "subgacc_packed_half.
 PACKED_HALF_DECLS = parse_header(_header_text(PACKED_HALF_HEADER))
 _TYPES.update(bind_types(PACKED_HALF_DECLS))
 PACKED_HALF_SYMBOLS = tuple(PACKED_HALF_DECLS)
+# the eighth header: the 16-bit rows with the segment id of every row (csrc/sjoin_half.hip), the same library, the same descriptor
+HALF_IDS_HEADER = os.path.join(os.path.dirname(HEADER), "subgacc_half_ids.h")
+HALF_IDS_DECLS = parse_header(_header_text(HALF_IDS_HEADER))
+_TYPES.update(bind_types(HALF_IDS_DECLS))
+HALF_IDS_SYMBOLS = tuple(HALF_IDS_DECLS)
 HALF_F16, HALF_BF16 = (int(re.search(rf"^#define\s+SUBGACC_HALF_{n}\s+(\d+)", _HALF_TEXT, re.M).group(1)) for n in ("F16", "BF16"))
 
 
@@ -156,7 +162,7 @@ VERBOSE = os.environ.get("SUBGACC_QUIET", "0") != "1"
 def build(force=False):
     """hipcc-compile csrc/*.hip for gfx950 into surel_plus_amd/libsubgacc_hip.so (in-tree)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))]
-    srcs += [HEADER, HALF_HEADER, SMALL_HEADER, PACKED_HEADER, WIDE_HEADER, HALF64_HEADER, PACKED_HALF_HEADER]
+    srcs += [HEADER, HALF_HEADER, SMALL_HEADER, PACKED_HEADER, WIDE_HEADER, HALF64_HEADER, PACKED_HALF_HEADER, HALF_IDS_HEADER]
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
         subprocess.check_call(["make", "-s", "-C", CSRC, "-j4", "all"])

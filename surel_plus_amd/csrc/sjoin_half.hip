@@ -1,4 +1,5 @@
-// sjoin_half.hip -- the row form of the join written in a 16-bit type (gfx950): include/subgacc_half.h, subgacc_sjoin_fill_half.
+// sjoin_half.hip -- the row form of the join written in a 16-bit type (gfx950): include/subgacc_half.h, subgacc_sjoin_fill_half, and
+// include/subgacc_half_ids.h, subgacc_sjoin_fill_half_ids -- the same rows with the segment id of each.
 //
 // A caller that trains under autocast casts xz [R,2,k] to bf16 / fp16 in its first Linear: half of the bytes the f32 fill writes are
 // thrown away one kernel later, and the join is bound by its stores.  sjoin_half_kernel writes the rows in that type at once.
@@ -16,7 +17,7 @@
 // non-temporal, like every output of the join.
 // A workgroup has 128 lanes, or 256 for batches too small to fill the chip with 128 (half_threads); SPrefetch (sjoin.hpp) is written
 // for 256, so the prefetch of S is restated here for either size.
-#include "../../include/subgacc_half.h"
+#include "../../include/subgacc_half_ids.h"
 #include "sjoin_half.hpp"
 
 namespace subgacc {
@@ -67,58 +68,86 @@ struct HalfPrefetch {
     }
 };
 
+// One mirrored pair, by its workgroup of NT lanes: the body of both kernels below, as text.  IDS_S / IDS_T: the statement that follows the
+// store of a row of S / of T -- nothing in sjoin_half_kernel, the store of the row's segment id in sjoin_half_ids_kernel.  (A macro,
+// not a function with a bool parameter: inlined through a function -- by reference or by value, with or without __restrict__ -- every
+// instantiation of sjoin_half_kernel came out scheduled and register-allocated differently from the kernel this file had before the
+// ids form, tools/kernel_digest.py; as text it is instruction for instruction that kernel, profiles/small_step_isa.log.)
+#define SJ_HALF_PAIR(IDS_S, IDS_T)                                                                                                   \
+    extern __shared__ __align__(16) unsigned char lds_raw[];                                                                         \
+    const int L = a.max_len;                                                                                                         \
+    int32_t *idsT = (int32_t *)lds_raw;      /* [L] */                                                                               \
+    uint32_t *valT = (uint32_t *)(idsT + L); /* [L] the member's key, or its SFptr+1 */                                              \
+    uint32_t *parT = valT + L;               /* [L] the same of its partner in S (0 = absent) */                                     \
+                                                                                                                                     \
+    MirroredPair m;                                                                                                                  \
+    if (!mirrored_pair<true>(a, pb, m)) return;                                                                                      \
+    const int tid = threadIdx.x;                                                                                                     \
+    const int ns = m.ns, nt = m.nt;                                                                                                  \
+    const int64_t tb = m.tb;                                                                                                         \
+    const int32_t *data = (const int32_t *)a.data;                                                                                   \
+    HalfPrefetch<NT> s;                                                                                                              \
+    s.prefetch(a, m.sb, ns);                                                                                                         \
+    /* the segments' first output rows: ns and nt rows follow (the size pass's scan) */                                              \
+    const int64_t oS = a.seg[m.jS], oT = a.seg[m.jT];                                                                                \
+    HalfQuot q;                                                                                                                      \
+    q.fm = (float)a.key_M, q.rcp = 1.0f / q.fm, q.divide = a.key_M >= 4096;                                                          \
+    for (int r = tid; r < nt; r += NT) { /* T: ids, payload, no partner yet */                                                       \
+        idsT[r] = stream_load(&a.indices[tb + r]);                                                                                   \
+        valT[r] = (uint32_t)stream_load(&data[tb + r]);                                                                              \
+        parT[r] = 0;                                                                                                                 \
+    }                                                                                                                                \
+    __syncthreads();                                                                                                                 \
+    for (int r0 = 0; r0 < ns; r0 += NT) { /* S: search T once; a hit gives each row its partner's payload */                         \
+        const int r = r0 + tid;                                                                                                      \
+        if (r >= ns) break;                                                                                                          \
+        int32_t id, value;                                                                                                           \
+        s.get(a, m.sb, r0, r, id, value);                                                                                            \
+        int b;                                                                                                                       \
+        const bool hit = sorted_find(idsT, nt, id, true, b);                                                                         \
+        if (hit) parT[b] = (uint32_t)value; /* ids are distinct inside a row: one writer per word */                                 \
+        emit_half_row<K, TAB, T>(a, q, out, oS + r, (uint32_t)value, hit ? valT[b] : 0u);                                            \
+        IDS_S;                                                                                                                       \
+    }                                                                                                                                \
+    __syncthreads();                                                                                                                 \
+    for (int r = tid; r < nt; r += NT) {                                                                                             \
+        emit_half_row<K, TAB, T>(a, q, out, oT + r, valT[r], parT[r]);                                                               \
+        IDS_T;                                                                                                                       \
+    }
+
 template <int K, bool TAB, typename T, int NT>
 __global__ __launch_bounds__(NT) void sjoin_half_kernel(const JoinArgs a, int64_t pb, uint32_t *__restrict__ out) {
-    extern __shared__ __align__(16) unsigned char lds_raw[];
-    const int L = a.max_len;
-    int32_t *idsT = (int32_t *)lds_raw;               // [L]
-    uint32_t *valT = (uint32_t *)(idsT + L);          // [L] the member's key, or its SFptr+1
-    uint32_t *parT = valT + L;                        // [L] the same of its partner in S (0 = absent)
-
-    MirroredPair m;
-    if (!mirrored_pair<true>(a, pb, m)) return;
-    const int tid = threadIdx.x;
-    const int ns = m.ns, nt = m.nt;
-    const int64_t tb = m.tb;
-    const int32_t *data = (const int32_t *)a.data;
-    HalfPrefetch<NT> s;
-    s.prefetch(a, m.sb, ns);
-    const int64_t oS = a.seg[m.jS], oT = a.seg[m.jT];   // the segments' first output rows: ns and nt rows follow (the size pass's scan)
-    HalfQuot q;
-    q.fm = (float)a.key_M, q.rcp = 1.0f / q.fm, q.divide = a.key_M >= 4096;
-    for (int r = tid; r < nt; r += NT) {              // T: ids, payload, no partner yet
-        idsT[r] = stream_load(&a.indices[tb + r]);
-        valT[r] = (uint32_t)stream_load(&data[tb + r]);
-        parT[r] = 0;
-    }
-    __syncthreads();
-    for (int r0 = 0; r0 < ns; r0 += NT) {             // S: search T once; a hit gives each row its partner's payload
-        const int r = r0 + tid;
-        if (r >= ns) break;
-        int32_t id, value;
-        s.get(a, m.sb, r0, r, id, value);
-        int b;
-        const bool hit = sorted_find(idsT, nt, id, true, b);
-        if (hit) parT[b] = (uint32_t)value;           // ids are distinct inside a row: one writer per word
-        emit_half_row<K, TAB, T>(a, q, out, oS + r, (uint32_t)value, hit ? valT[b] : 0u);
-    }
-    __syncthreads();
-    for (int r = tid; r < nt; r += NT) emit_half_row<K, TAB, T>(a, q, out, oT + r, valT[r], parT[r]);
+    SJ_HALF_PAIR(, )
 }
 
+// ... and with the rows' segment ids (include/subgacc_half_ids.h): segid[row] = the row's segment, one more non-temporal store by the
+// lane that stores the row -- what emit_key_span of sjoin.hip writes beside the f32 rows
+template <int K, bool TAB, typename T, int NT>
+__global__ __launch_bounds__(NT) void sjoin_half_ids_kernel(const JoinArgs a, int64_t pb, uint32_t *__restrict__ out, int64_t *__restrict__ segid) {
+    SJ_HALF_PAIR(__builtin_nontemporal_store(m.jS, segid + oS + r), __builtin_nontemporal_store(m.jT, segid + oT + r))
+}
+#undef SJ_HALF_PAIR
+
+// (segid = NULL: sjoin_half_kernel, the rows alone; else sjoin_half_ids_kernel)
+template <int K, bool TAB, typename T, int NT>
+static int launch_half_one(int64_t grid, size_t lds, hipStream_t s, const JoinArgs &a, int64_t pb, uint32_t *out, int64_t *segid) {
+    if (segid) return launch(sjoin_half_ids_kernel<K, TAB, T, NT>, grid, NT, lds, s, a, pb, out, segid);
+    return launch(sjoin_half_kernel<K, TAB, T, NT>, grid, NT, lds, s, a, pb, out);
+}
 template <bool TAB, typename T, int NT>
-static int launch_half_k(int k, int64_t grid, size_t lds, hipStream_t s, const JoinArgs &a, int64_t pb, uint32_t *out) {
+static int launch_half_k(int k, int64_t grid, size_t lds, hipStream_t s, const JoinArgs &a, int64_t pb, uint32_t *out, int64_t *segid) {
     switch (k) {
-    case 2: return launch(sjoin_half_kernel<2, TAB, T, NT>, grid, NT, lds, s, a, pb, out);
-    case 3: return launch(sjoin_half_kernel<3, TAB, T, NT>, grid, NT, lds, s, a, pb, out);
-    case 4: return launch(sjoin_half_kernel<4, TAB, T, NT>, grid, NT, lds, s, a, pb, out);
-    default: return launch(sjoin_half_kernel<5, TAB, T, NT>, grid, NT, lds, s, a, pb, out);
+    case 2: return launch_half_one<2, TAB, T, NT>(grid, lds, s, a, pb, out, segid);
+    case 3: return launch_half_one<3, TAB, T, NT>(grid, lds, s, a, pb, out, segid);
+    case 4: return launch_half_one<4, TAB, T, NT>(grid, lds, s, a, pb, out, segid);
+    default: return launch_half_one<5, TAB, T, NT>(grid, lds, s, a, pb, out, segid);
     }
 }
 template <bool TAB, typename T>
-static int launch_half(int threads, int k, int64_t grid, size_t lds, hipStream_t s, const JoinArgs &a, int64_t pb, uint32_t *out) {
-    if (threads == 128) return launch_half_k<TAB, T, 128>(k, grid, lds, s, a, pb, out);
-    return launch_half_k<TAB, T, kPairThreads>(k, grid, lds, s, a, pb, out);
+static int launch_half(int threads, int k, int64_t grid, size_t lds, hipStream_t s, const JoinArgs &a, int64_t pb, uint32_t *out,
+                       int64_t *segid) {
+    if (threads == 128) return launch_half_k<TAB, T, 128>(k, grid, lds, s, a, pb, out, segid);
+    return launch_half_k<TAB, T, kPairThreads>(k, grid, lds, s, a, pb, out, segid);
 }
 
 // Lanes of a pair's workgroup: 128 -- twice the pairs with their row loads in flight per CU -- unless the batch is far below the
@@ -137,8 +166,9 @@ static int half_threads(int64_t pairs) {
 
 using namespace subgacc;
 
-extern "C" int subgacc_sjoin_fill_half(const subgacc_join_desc *d, int32_t out_dtype, void *out_rows, void *stream) {
-    const char *name = "sjoin_fill_half";
+// Both entry points: `ids` -- subgacc_sjoin_fill_half_ids -- asks for out_segid beside the rows
+static int fill_half(const char *name, const subgacc_join_desc *d, int32_t out_dtype, void *out_rows, bool ids, int64_t *out_segid,
+                     void *stream) {
     RowLayout layout;
     if (int rc = decode_desc(name, d, false, layout)) return rc;
     SG_REQUIRE(d->form == SUBGACC_JOIN_ROWS, SUBGACC_ERR_BADARG, "%s: writes the rows of the row form (form ROWS), not form %d", name,
@@ -179,6 +209,7 @@ extern "C" int subgacc_sjoin_fill_half(const subgacc_join_desc *d, int32_t out_d
                "%s: out_dtype = %d (SUBGACC_HALF_F16 = 1 or SUBGACC_HALF_BF16 = 2)", name, (int)out_dtype);
     SG_REQUIRE(out_rows || S == 0, SUBGACC_ERR_BADARG, "%s: out_rows = NULL with S = %lld segments", name, (long long)S);
     SG_REQUIRE(((uintptr_t)out_rows & 15) == 0, SUBGACC_ERR_BADARG, "%s: out_rows must be 16-byte aligned (rows leave as 16-byte words)", name);
+    SG_REQUIRE(!ids || out_segid || S == 0, SUBGACC_ERR_BADARG, "%s: out_segid = NULL with S = %lld segments", name, (long long)S);
     const size_t lds = half_lds(a.max_len);
     SG_REQUIRE(lds <= (size_t)kLdsBytes, SUBGACC_ERR_LDS, "%s: rows of %d members need %zu B of LDS", name, (int)a.max_len, lds);
     if (S == 0) return SUBGACC_OK;
@@ -191,7 +222,18 @@ extern "C" int subgacc_sjoin_fill_half(const subgacc_join_desc *d, int32_t out_d
     hipStream_t s = (hipStream_t)stream;
     uint32_t *out = (uint32_t *)out_rows;
     const bool bf = out_dtype == SUBGACC_HALF_BF16;
+    int64_t *segid = ids ? out_segid : nullptr;
     if (kind == SUBGACC_JOIN_SFPTR)
-        return bf ? launch_half<true, __hip_bfloat16>(threads, k, grid, lds, s, a, pb, out) : launch_half<true, __half>(threads, k, grid, lds, s, a, pb, out);
-    return bf ? launch_half<false, __hip_bfloat16>(threads, k, grid, lds, s, a, pb, out) : launch_half<false, __half>(threads, k, grid, lds, s, a, pb, out);
+        return bf ? launch_half<true, __hip_bfloat16>(threads, k, grid, lds, s, a, pb, out, segid)
+                  : launch_half<true, __half>(threads, k, grid, lds, s, a, pb, out, segid);
+    return bf ? launch_half<false, __hip_bfloat16>(threads, k, grid, lds, s, a, pb, out, segid)
+              : launch_half<false, __half>(threads, k, grid, lds, s, a, pb, out, segid);
+}
+
+extern "C" int subgacc_sjoin_fill_half(const subgacc_join_desc *d, int32_t out_dtype, void *out_rows, void *stream) {
+    return fill_half("sjoin_fill_half", d, out_dtype, out_rows, false, nullptr, stream);
+}
+
+extern "C" int subgacc_sjoin_fill_half_ids(const subgacc_join_desc *d, int32_t out_dtype, void *out_rows, int64_t *out_segid, void *stream) {
+    return fill_half("sjoin_fill_half_ids", d, out_dtype, out_rows, true, out_segid, stream);
 }

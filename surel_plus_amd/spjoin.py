@@ -128,12 +128,29 @@ def _half_store_refusals(x, wide_keys=False):
             "key_rows=False (strided rows of table slots)": bool(getattr(x, "payload_is_slot", False)) and not getattr(x, "keyrows", False)}
 
 
-def _half_shape_refused(num_walks, num_steps, wide_keys):
-    """a step's 16-bit rows exist over its key rows: the 32-bit ones (subgacc_sjoin_fill_half) and -- wide_keys=True -- the 64-bit ones of
-    sampler.key_rows_form == 64 (subgacc_sjoin_fill_half64); not at a shape without key rows"""
-    from .sampler import key_rows_form
+def _half_shape_refused(num_walks, num_steps, wide_keys, small_rows=False):
+    """a step's 16-bit rows exist over its key rows: the 32-bit ones (subgacc_sjoin_fill_half), -- wide_keys=True -- the 64-bit ones of
+    sampler.key_rows_form == 64 (subgacc_sjoin_fill_half64) and -- small_rows=True -- the 32-bit ones of a small shape
+    (sampler.small_rows_form); not at a shape without key rows"""
+    from .sampler import key_rows_form, small_rows_form
+    if small_rows and small_rows_form(int(num_walks), int(num_steps)):
+        return False
     form = key_rows_form(int(num_walks), int(num_steps))
     return form != 32 and not (wide_keys and form == 64)
+
+
+def _small_rows_wanted(who, small_rows, num_walks, num_steps, stage, refused):
+    """small_rows=True at a shape where it means something -- a small shape (sampler.small_rows_form) and the row form (stage=None:
+    the stages take the one-wave kernel by themselves) -- after a ValueError that names the keyword for the first entry of
+    `refused()` {what the call was given: bool} that holds, before any device work.  Anywhere else the keyword changes nothing."""
+    from .sampler import small_rows_form
+    if not small_rows or stage is not None or not small_rows_form(int(num_walks), int(num_steps)):
+        return False
+    for what, given in refused().items():
+        if given:
+            raise ValueError(f"{who}: small_rows=True (the row form over the 32-bit key rows of the one-wave kernel, num_walks = "
+                             f"{num_walks}, num_steps = {num_steps}) does not go with {what}")
+    return True
 
 
 def _fill_half(L, kind):
@@ -624,14 +641,29 @@ class StepBuffers:
     subgacc_sjoin_fill_half64 (include/subgacc_half64.h) instead of the f32 fill: nothing more is allocated or read back, root dedup,
     order=, rng="rand_r" and out= work as in the f32 step, and `self.wide` stays False (no stage, no columns pass).  Without the keyword
     the shape is refused as ever, and so are ptr=False, triplets=True, a stage, key_rows=False, batch= and a shape without key rows
-    with it."""
+    with it.
+    small_rows=True: the row form (stage=None) of a small shape (sampler.small_rows_form: the reference's mag, DBLP-coauthor and vessel
+    settings) over the 32-bit key rows of the one-wave kernel, as the stages of such a shape run already -- `self.small`, `keyrows`,
+    neither `table` nor `feat`: prologue (or a dedup prologue), work list, subgacc_walk_keyrows_small, size pass, the KEY32 join; no
+    LP unpack, nothing allocated or read back, (xz, indptr, segment ids) bit for bit those of the table form.  Pairs with pointers
+    and ptr=False, triplets=True, dedup_roots=True, order= / sort_roots, rng="rand_r", out=, and batch= for f32 rows with pointers.
+    dtype=torch.float16 / torch.bfloat16 goes with ptr=False and triplets=True here -- and only here: subgacc_sjoin_fill_half_ids
+    (include/subgacc_half_ids.h) writes the int64 ids beside the 16-bit rows.  Opt-in (profiles/small_step_bench.log has both routes).
+    ValueError naming the keyword for key_rows=False, packed_rows=True, packed_half=True and a 16-bit dtype with batch=; at any other
+    shape, and with a stage, the keyword changes nothing."""
 
     def __init__(self, csr, pairs, num_walks=200, num_steps=3, uniq_capacity=1 << 17, out=None, dedup_roots=False, rng="philox",
                  key_rows=True, sort_roots=True, batch=None, align_rows=True, order=None, ptr=True, triplets=False, stage=None,
-                 table_rows=2048, dtype=None, packed_rows=None, wide_keys=False, packed_half=False):
+                 table_rows=2048, small_rows=False, dtype=None, packed_rows=None, wide_keys=False, packed_half=False):
         from .sampler import FUSED_MAX_Q, as_rank, key_rows_form, packed_rows_form, small_rows_form
         self.packed, self._unpacked, self._unpacked_step = False, None, -1
-        if packed_half:     # opt-in: the packed hand-over under the 16-bit rows, refused before anything touches the device
+        # opt-in: the row form of a small shape over the key rows of the one-wave kernel, refused before anything touches the device
+        small_rows = _small_rows_wanted("StepBuffers", small_rows, num_walks, num_steps, stage, lambda: {
+            "key_rows=False (the one-wave kernel writes key rows)": not key_rows,
+            "packed_rows=True (no packed form at a small shape)": packed_rows is True,
+            "packed_half=True (no packed form at a small shape)": bool(packed_half),
+            f"dtype={dtype} with batch= (many batches per step)": batch is not None and dtype in (torch.float16, torch.bfloat16)})
+        if packed_half:    # opt-in: the packed hand-over under the 16-bit rows, refused before anything touches the device
             why = {f"dtype={dtype} (the packed rows are joined in 16 bits with dtype=torch.float16 / torch.bfloat16; the f32 step is packed "
                    "by itself)": dtype not in (torch.float16, torch.bfloat16),
                    "packed_rows=False": packed_rows is False, "ptr=False": not ptr, "triplets=True": bool(triplets),
@@ -644,9 +676,11 @@ class StepBuffers:
         # a stage over 64-bit key rows (wide_keys=True at such a shape, nothing anywhere else): the columns pass of csrc/keycols64.hip
         self.wide = bool(wide_keys) and stage in _KEY_STAGES and bool(key_rows) and key_rows_form(int(num_walks), int(num_steps)) == 64
         self.half = _half_code(dtype, "StepBuffers", lambda: {
-            "ptr=False (segment ids)": not ptr, "triplets=True": triplets, f"stage={stage!r}": stage is not None,
-            "key_rows=False (strided rows of table slots)": not key_rows,
-            f"num_walks = {num_walks}, num_steps = {num_steps} (64-bit keys, or no key rows)": _half_shape_refused(num_walks, num_steps, wide_keys),
+            # (small_rows: segment ids too -- subgacc_sjoin_fill_half_ids writes them beside the 16-bit rows)
+            "ptr=False (segment ids)": not ptr and not small_rows, "triplets=True": triplets and not small_rows,
+            f"stage={stage!r}": stage is not None, "key_rows=False (strided rows of table slots)": not key_rows,
+            f"num_walks = {num_walks}, num_steps = {num_steps} (64-bit keys, or no key rows)":
+                _half_shape_refused(num_walks, num_steps, wide_keys, small_rows),
             "batch= (many batches per step)": batch is not None})
         self.dtype = dtype if self.half else torch.float32
         # 16-bit rows over 64-bit key rows (wide_keys=True with a 16-bit dtype at such a shape): the step ends in subgacc_sjoin_fill_half64
@@ -699,8 +733,9 @@ class StepBuffers:
         self.ids = torch.empty(n * self.stride, dtype=torch.int32, device=dev)
         form = key_rows_form(self.M, self.m) if key_rows else 0
         # a stage over a small shape (sampler.small_rows_form): its 32-bit key rows come from subgacc_walk_keyrows_small, which reads a
-        # selecting work list; the row form (stage=None) of such a shape stays the table form on the general kernel
-        self.small = stage in _KEY_STAGES and bool(key_rows) and small_rows_form(self.M, self.m)
+        # selecting work list; the row form (stage=None) of such a shape stays the table form on the general kernel unless
+        # small_rows=True asks for the same rows under the row-form join
+        self.small = (stage in _KEY_STAGES and bool(key_rows) and small_rows_form(self.M, self.m)) or small_rows
         if self.small:
             form = 32
         self.keyrows = bool(form)                 # rows of LP keys: no table, no feature table
@@ -967,7 +1002,7 @@ def _buffered_step(csr, e, bufs, seed, out, fit=False):
                          f"these StepBuffers were made for [{B // PB}, 2, {PB}] pairs")
     e = e.contiguous()
     flags = bufs.status.view(torch.int32)[:4]
-    small = bool(getattr(bufs, "small", False))      # a stage over a small shape: subgacc_walk_keyrows_small writes the key rows
+    small = bool(getattr(bufs, "small", False))      # a small shape (a stage, or small_rows=True): subgacc_walk_keyrows_small writes the key rows
     cfg = make_cfg(csr, M, m, -1, seed, bufs.rng, records=(2 <= m <= 4) and not small,     # (only the fused-row kernel of 2..4 hops reads hop records)
                    row_pitch=bufs.stride if bufs.stride != bufs.Q else 0)
     rr = bufs.rng == "rand_r"
@@ -1047,6 +1082,10 @@ def _buffered_step(csr, e, bufs, seed, out, fit=False):
         with _timed("sjoin_fill"):
             check(L.subgacc_sjoin_fill_packed(ctypes.byref(_lib.join_desc(JOIN_ROWS, kind, out_xz=xz, **rows, **payload)), ptr(bufs.nesc),
                                               bufs.num_nodes, st))
+    elif bufs.half and bufs.segid is not None:      # 16-bit rows and their segment ids (a small shape: ptr=False, triplets)
+        with _timed("sjoin_fill_half_ids"):
+            check(L.subgacc_sjoin_fill_half_ids(ctypes.byref(_lib.join_desc(JOIN_ROWS, kind, **rows, **payload)), bufs.half, ptr(xz),
+                                                ptr(bufs.segid), st))
     elif bufs.half:       # 16-bit rows (StepBuffers(dtype=): key rows of 32 bits, or -- wide_keys=True -- of 64; segment pointers)
         with _timed("sjoin_fill_half"):
             check(_fill_half(L, kind)(ctypes.byref(_lib.join_desc(JOIN_ROWS, kind, **rows, **payload)), bufs.half, ptr(xz), st))
@@ -1058,8 +1097,38 @@ def _buffered_step(csr, e, bufs, seed, out, fit=False):
     return xz, (bufs.seg if bufs.ptr else _with_pointers(bufs.segid[: xz.shape[0]], bufs.seg)), sets
 
 
+def _small_call_refusals(kw, strided, dtype, lazy):
+    """what sample_and_gather / sample_and_hgather refuse of small_rows=True at a small shape (_small_rows_wanted), by what they were given"""
+    return {"key_rows=False (the one-wave kernel writes key rows)": not kw.get("key_rows", True),
+            "packed_rows=True (no packed form at a small shape)": kw.get("packed_rows") is True,
+            "packed_half=True (no packed form at a small shape)": bool(kw.get("packed_half")),
+            "strided=False (a packed copy of the step's rows)": strided is False,
+            "fused=False or a truncating bucket (the general kernel's)": kw.get("fused") is False or kw.get("bucket", -1) > 0,
+            f"dtype={dtype} with lazy=True": bool(lazy) and dtype in (torch.float16, torch.bfloat16)}
+
+
+def _small_rows_match(who, small_rows, buffers):
+    """buffers= of the row form run the route they were made for: the keyword of the call must say the same"""
+    if buffers is not None and getattr(buffers, "stage", None) is None and bool(small_rows) != bool(getattr(buffers, "small", False)):
+        raise ValueError(f"{who}: small_rows={bool(small_rows)} but buffers= were made with small_rows={bool(getattr(buffers, 'small', False))}: "
+                         "StepBuffers(..., small_rows=True) holds the key rows of the one-wave kernel, without it the table of the general one")
+
+
+def _small_step(csr, e, seed, out, lazy, **how):
+    """sample_and_gather / sample_and_hgather with small_rows=True and without buffers=: StepBuffers for this one call (as _step_counts
+    makes them for the stages), the buffered step, and -- unless lazy -- the sets resolved and (xz, ids) cut to the step's rows.
+    out=: as for StepBuffers, room for the worst case."""
+    bufs = StepBuffers(csr, e.shape[1], small_rows=True, **how)
+    xz, ind, sets = _buffered_step(csr, e, bufs, seed, out)
+    if lazy:
+        return xz, ind, sets
+    sets.resolve()
+    R = int(sets.extra[0])
+    return xz[:R], (ind if bufs.ptr else _with_pointers(ind[:R], bufs.seg)), sets
+
+
 def sample_and_gather(csr, edge, num_walks=200, num_steps=3, seed=111413, rng="philox", dedup_roots=False, out=None,
-                      lazy=False, strided=None, buffers=None, order=None, ptr=True, dtype=None, wide_keys=False, **kw):
+                      lazy=False, strided=None, buffers=None, order=None, ptr=True, small_rows=False, dtype=None, wide_keys=False, **kw):
     """The on-demand form of the path in one call: sample the endpoints of `edge` [2, B] (node ids), build their SpG
     rows, join -> (xz, indptr, sets), the same (xz, indptr) as `gather(edge, subg_matrix(G, arange(N)))` would give for sets
     drawn with the same RNG (Philox keys every walk by (seed, root id, walk, step), so a root's set does not depend on
@@ -1082,18 +1151,28 @@ def sample_and_gather(csr, edge, num_walks=200, num_steps=3, seed=111413, rng="p
     wide_keys=True (with a 16-bit dtype): a shape with 64-bit key rows (sampler.key_rows_form == 64: 4 hops, M = 128 .. 204 -- the
     paper's citation2 setting M = 200) is served too, by subgacc_sjoin_fill_half64 (include/subgacc_half64.h), buffered
     (StepBuffers(..., dtype=, wide_keys=True)) or not, with or without dedup_roots; the other refusals stand, and at a 32-bit shape
-    the keyword changes nothing."""
+    the keyword changes nothing.
+    small_rows=True: at a small shape (sampler.small_rows_form) the step of StepBuffers(..., small_rows=True) -- the one-wave kernel's
+    key rows under the row-form join, the same (xz, indptr); dtype= goes with ptr=False there.  With buffers=, those must have been made
+    with the keyword (and without it when the call has none); without buffers= a set is made for this one call, the sets are resolved
+    and (xz, ids) are the step's rows (lazy=True: the unresolved views of the buffered step; out=: room for the worst case, 2B * (M*m+1)
+    rows).  ValueError naming the keyword for key_rows=False, packed_rows=True, packed_half=True, strided=False, fused=False, a
+    truncating bucket and a 16-bit dtype with lazy=True; at any other shape the keyword changes nothing."""
     from .sampler import as_rank, key_rows_form
     from .spg import sample_spg
+    small_rows = _small_rows_wanted("sample_and_gather", small_rows, num_walks, num_steps, None, lambda: _small_call_refusals(kw, strided, dtype, lazy))
     half = _half_code(dtype, "sample_and_gather", lambda: {
-        "ptr=False (segment ids)": not ptr, "lazy=True": lazy, "key_rows=False (strided rows of table slots)": not kw.get("key_rows", True),
+        "ptr=False (segment ids)": not ptr and not small_rows, "lazy=True": lazy,
+        "key_rows=False (strided rows of table slots)": not kw.get("key_rows", True),
         "strided=False (a packed copy of the step's rows)": strided is False,
-        f"num_walks = {num_walks}, num_steps = {num_steps} (64-bit keys, or no key rows)": _half_shape_refused(num_walks, num_steps, wide_keys)})
+        f"num_walks = {num_walks}, num_steps = {num_steps} (64-bit keys, or no key rows)":
+            _half_shape_refused(num_walks, num_steps, wide_keys, small_rows)})
     half64 = bool(half) and key_rows_form(int(num_walks), int(num_steps)) == 64
     if buffers is not None and (half != getattr(buffers, "half", 0) or half64 != bool(getattr(buffers, "half64", False))):
         raise ValueError(f"sample_and_gather: dtype={dtype}{', wide_keys=True' if half64 else ''} but buffers= were made with "
                          f"dtype={getattr(buffers, 'dtype', None)}{', wide_keys=True' if getattr(buffers, 'half64', False) else ''}: "
                          "StepBuffers(..., dtype=) allocates `out` in the type the step writes")
+    _small_rows_match("sample_and_gather", small_rows, buffers)
     order = as_rank(csr, order)
     e = _as_rows(edge, csr.device)
     if buffers is None and e.dim() != 2:
@@ -1112,6 +1191,9 @@ def sample_and_gather(csr, edge, num_walks=200, num_steps=3, seed=111413, rng="p
         if order is not None and (buffers.order is None or order.rank is not buffers.order.rank):
             raise ValueError("buffers= walks in the order its StepBuffers were made with: pass order= to StepBuffers(...)")
         return _buffered_step(csr, e, buffers, seed, out)
+    if small_rows:      # the same step through buffers made for this one call
+        return _small_step(csr, e, seed, out, lazy, num_walks=num_walks, num_steps=num_steps, dedup_roots=dedup_roots, rng=rng, order=order,
+                           ptr=bool(ptr), dtype=dtype, sort_roots=kw.get("sort_roots", True))
     if dedup_roots:
         if rng != "philox":
             raise ValueError("dedup_roots=True needs rng='philox' (rand_r sets depend on the position in the stream)")
@@ -1147,7 +1229,7 @@ def _as_triplets(hedge, device, who):
 
 
 def sample_and_hgather(csr, hedge, num_walks=200, num_steps=3, seed=111413, rng="philox", dedup_roots=False, out=None, buffers=None,
-                       order=None, **kw):
+                       order=None, small_rows=False, dtype=None, **kw):
     """The on-demand form of hgather (train.py:48-72, the batches of main_horder.py / train.py:142-172) in one call: the three
     roles of `hedge` [3, B] (node ids u, v, w) are walked ONCE each -- 3B roots, not the 4B that two pair steps (u, w) and (v, w)
     would walk -- and joined as [U|w ; W|u ; V|w ; W|v] -> (xz, ids, sets): bit for bit the (xz, ids) of
@@ -1158,15 +1240,30 @@ def sample_and_hgather(csr, hedge, num_walks=200, num_steps=3, seed=111413, rng=
     buffers=StepBuffers(csr, B, ..., triplets=True): the allocation-free six-launch step (xz and ids are views of the buffers,
     their first ids.seg_pointers[-1] rows are the result; sets.prefetch() / sets.resolve() as for sample_and_gather).
     rng: "philox" only -- the reference never samples triplets in a rand_r stream, there is nothing to reproduce.
-    order=: as for sample_and_gather."""
+    order=: as for sample_and_gather.
+    small_rows=True: at a small shape (sampler.small_rows_form: DBLP-coauthor's M = 100, 2 hops) the step of
+    StepBuffers(..., triplets=True, small_rows=True), with buffers= made so or with a set made for this one call (resolved, (xz, ids)
+    cut to the step's rows); the same (xz, ids).  dtype=torch.float16 / torch.bfloat16: xz in that type, bit for bit xz.to(dtype) --
+    with small_rows=True at such a shape only (ValueError elsewhere: no other triplet step writes 16-bit rows), buffers= made with the
+    same dtype.  ValueError naming the keyword as for sample_and_gather; at any other shape it changes nothing."""
     from .sampler import as_rank
     from .spg import sample_spg
     if rng != "philox":
         raise ValueError("sample_and_hgather samples with rng='philox' (a rand_r set depends on its root's place in a stream the "
                          "reference never draws for triplets)")
+    small_rows = _small_rows_wanted("sample_and_hgather", small_rows, num_walks, num_steps, None, lambda: _small_call_refusals(kw, None, dtype, False))
+    half = _half_code(dtype, "sample_and_hgather", lambda: {
+        "triplets (16-bit rows with segment ids are those of small_rows=True at a small shape, sampler.small_rows_form)": not small_rows})
+    if buffers is not None and half != getattr(buffers, "half", 0):
+        raise ValueError(f"sample_and_hgather: dtype={dtype} but buffers= were made with dtype={getattr(buffers, 'dtype', None)}: "
+                         "StepBuffers(..., dtype=) allocates `out` in the type the step writes")
+    _small_rows_match("sample_and_hgather", small_rows, buffers)
     order = as_rank(csr, order)
     h = _as_triplets(hedge, csr.device, "sample_and_hgather")
     B = h.shape[1]
+    if small_rows and buffers is None:      # the same step through buffers made for this one call
+        return _small_step(csr, h, seed, out, False, num_walks=num_walks, num_steps=num_steps, dedup_roots=dedup_roots, order=order,
+                           triplets=True, dtype=dtype, sort_roots=kw.get("sort_roots", True))
     if buffers is not None:
         if not buffers.triplets or buffers.stage is not None or (dedup_roots and not buffers.dedup) or \
                 (num_walks, num_steps) != (buffers.M, buffers.m) or kw.get("uniq_capacity", buffers.capacity) != buffers.capacity or kw.get("fused") is False or kw.get("bucket", -1) > 0:
