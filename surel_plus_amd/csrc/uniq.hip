@@ -17,11 +17,7 @@ namespace subgacc {
 
 __global__ void uniq_reset_kernel(UniqTable t, int64_t cap) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < cap) {
-        t.keys[i] = kEmptyKey;
-        t.mintag[i] = ~0ull;
-        t.id[i] = -1;
-    }
+    if (i < cap) uniq_reset_slot(t, i);
 }
 
 // What an on-demand step (sample the endpoints of B pairs -> rows -> join) needs before its walk kernel, in ONE launch
@@ -30,16 +26,9 @@ __global__ void uniq_reset_kernel(UniqTable t, int64_t cap) {
 __global__ void step_prologue_kernel(UniqTable t, int64_t cap, int64_t *zero_words, int64_t n_zero, const int64_t *edge,
                                      int32_t *roots, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < cap) {        // cap = 0: no table (key rows)
-        t.keys[i] = kEmptyKey;
-        t.mintag[i] = ~0ull;
-        t.id[i] = -1;
-    }
+    if (i < cap) uniq_reset_slot(t, i);        // cap = 0: no table (key rows)
     if (i < n_zero) zero_words[i] = 0;
-    if (i < n) {
-        const int64_t v = edge[i];     // ids beyond int32 cannot be nodes of an int32 graph: out of range for the walk kernel
-        roots[i] = (v < 0 || v > 0x7FFFFFFFll) ? -1 : (int32_t)v;
-    }
+    if (i < n) roots[i] = narrow_root(edge[i]);
 }
 
 // The same prologue for a step that samples every DISTINCT endpoint once (Philox keys a walk by its root's id: a root's set does
@@ -397,8 +386,7 @@ extern "C" int subgacc_step_prologue(void *table, int64_t capacity, int64_t *zer
     if (!table) capacity = 0;
     SG_REQUIRE(n >= 0 && n_zero >= 0 && (n == 0 || (edge && roots)) && (n_zero == 0 || zero_words), SUBGACC_ERR_BADARG,
                "step_prologue: null argument");
-    int64_t span = capacity > n ? capacity : n;
-    if (n_zero > span) span = n_zero;
+    const int64_t span = prologue_span(capacity, n_zero, n);
     if (span == 0) return SUBGACC_OK;
     hipLaunchKernelGGL(step_prologue_kernel, dim3((unsigned)ceil_div(span, 256)), dim3(256), 0, (hipStream_t)stream,
                        table ? uniq_view(table, capacity) : UniqTable{nullptr, nullptr, nullptr, 0}, capacity, zero_words, n_zero,

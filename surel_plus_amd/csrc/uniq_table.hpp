@@ -27,6 +27,24 @@ __host__ __device__ inline UniqTable uniq_view(void *table, int64_t cap) {
     return t;
 }
 
+// What every step prologue does per thread, in one place (step_prologue_kernel of uniq.hip, step_prologue_star_kernel of
+// walk_prep.hip): slot i of the table back to empty (subgacc_uniq_reset), and an int64 node id narrowed to the int32 root the sampler
+// takes (force-cast like the reference's query, subg_acc.c:673) -- an id beyond int32 cannot be a node of an int32 graph: -1, out of
+// range for the walk kernel, which flags it.
+__device__ __forceinline__ void uniq_reset_slot(const UniqTable &t, int64_t i) {
+    t.keys[i] = kEmptyKey;
+    t.mintag[i] = ~0ull;
+    t.id[i] = -1;
+}
+
+__device__ __forceinline__ int32_t narrow_root(int64_t v) { return (v < 0 || v > 0x7FFFFFFFll) ? -1 : (int32_t)v; }
+
+// the threads of a prologue launch: one per table slot, status word and root, whichever are most
+inline int64_t prologue_span(int64_t capacity, int64_t n_zero, int64_t n) {
+    const int64_t span = capacity > n ? capacity : n;
+    return n_zero > span ? n_zero : span;
+}
+
 __device__ __forceinline__ uint64_t mix64(uint64_t x) {
     x ^= x >> 33;
     x *= 0xff51afd7ed558ccdULL;

@@ -1,8 +1,11 @@
 // walk_prep.hip -- what a walk launch is handed ready-made (gfx950): the key shift of a shape, the rand_r stream position of every
-// root (subgacc_rng_positions) and the packed hop records of a graph (subgacc_hop_records_*).  The walk kernels themselves:
+// root (subgacc_rng_positions), the packed hop records of a graph (subgacc_hop_records_*) and the roots of a step of one source
+// against K targets (subgacc_step_prologue_star, include/subgacc_star.h).  The walk kernels themselves:
 // walk.hip (general), walk_pipe.hip, walk_rows.hip, walk_small.hip.
 #include "common.hpp"
+#include "../../include/subgacc_star.h"
 #include "walk_common.hpp"
+#include "uniq_table.hpp"
 #include <stdlib.h>
 
 namespace subgacc {
@@ -44,9 +47,45 @@ __global__ void rng_positions_kernel(const int64_t *__restrict__ calls_excl, int
     sd[i] = lcg_jump(seed + (uint32_t)t, (uint32_t)(3ull * c));
 }
 
+// step_prologue_kernel (uniq.hip) for a step whose roots come as two arrays -- the heads every K segments share (the sources of an
+// evaluation batch, utils.py:93-95; u and v of the higher-order negatives, dataloader.py:265-275) and the tails (the candidates) --
+// in ONE launch: table reset, status words zeroed, roots[0 .. n_heads) = heads and roots[n_heads .. n_heads + n_tails) = tails,
+// narrowed as the plain prologue narrows.
+__global__ void step_prologue_star_kernel(UniqTable t, int64_t cap, int64_t *zero_words, int64_t n_zero, const int64_t *heads,
+                                          int64_t n_heads, const int64_t *tails, int64_t n_tails, int32_t *roots) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < cap) uniq_reset_slot(t, i);        // cap = 0: no table (key rows)
+    if (i < n_zero) zero_words[i] = 0;
+    if (i < n_heads + n_tails) roots[i] = narrow_root(i < n_heads ? heads[i] : tails[i - n_heads]);
+}
+
 }  // namespace subgacc
 
 using namespace subgacc;
+
+extern "C" int subgacc_step_prologue_star(void *table, int64_t capacity, int64_t *zero_words, int64_t n_zero, const int64_t *heads,
+                                          int64_t n_heads, const int64_t *tails, int64_t n_tails, int32_t *roots, void *stream) {
+    SG_REQUIRE(!table || (capacity > 0 && (capacity & (capacity - 1)) == 0 && capacity < (1ll << 31)), SUBGACC_ERR_BADARG,
+               "step_prologue_star: capacity must be a power of two below 2^31");
+    if (!table) capacity = 0;
+    SG_REQUIRE(n_heads >= 0 && n_tails >= 0 && n_zero >= 0, SUBGACC_ERR_BADARG,
+               "step_prologue_star: negative count (n_heads = %lld, n_tails = %lld, n_zero = %lld)", (long long)n_heads,
+               (long long)n_tails, (long long)n_zero);
+    SG_REQUIRE(n_heads < (1ll << 30) && n_tails < (1ll << 30) && n_heads + n_tails < (1ll << 30), SUBGACC_ERR_BADARG,
+               "step_prologue_star: n_heads + n_tails = %lld + %lld roots (must be below 2^30)", (long long)n_heads, (long long)n_tails);
+    const int64_t n = n_heads + n_tails;
+    SG_REQUIRE((n == 0 || roots) && (n_heads == 0 || heads) && (n_tails == 0 || tails) && (n_zero == 0 || zero_words),
+               SUBGACC_ERR_BADARG, "step_prologue_star: null argument");
+    SG_REQUIRE(n_zero < (1ll << 30), SUBGACC_ERR_BADARG, "step_prologue_star: n_zero = %lld status words (must be below 2^30)",
+               (long long)n_zero);
+    const int64_t span = prologue_span(capacity, n_zero, n);
+    if (span == 0) return SUBGACC_OK;
+    hipLaunchKernelGGL(step_prologue_star_kernel, dim3((unsigned)ceil_div(span, 256)), dim3(256), 0, (hipStream_t)stream,
+                       table ? uniq_view(table, capacity) : UniqTable{nullptr, nullptr, nullptr, 0}, capacity, zero_words, n_zero,
+                       heads, n_heads, tails, n_tails, roots);
+    SG_LAUNCH_CHECK();
+    return SUBGACC_OK;
+}
 
 extern "C" int subgacc_key_shift(int32_t num_walks, int32_t num_steps) {
     SG_REQUIRE(num_walks > 0 && num_steps > 0, SUBGACC_ERR_BADARG, "num_walks and num_steps must be positive");

@@ -650,12 +650,37 @@ class StepBuffers:
     dtype=torch.float16 / torch.bfloat16 goes with ptr=False and triplets=True here -- and only here: subgacc_sjoin_fill_half_ids
     (include/subgacc_half_ids.h) writes the int64 ids beside the 16-bit rows.  Opt-in (profiles/small_step_bench.log has both routes).
     ValueError naming the keyword for key_rows=False, packed_rows=True, packed_half=True and a 16-bit dtype with batch=; at any other
-    shape, and with a stage, the keyword changes nothing."""
+    shape, and with a stage, the keyword changes nothing.
+    star=K: the step of one source against K targets, the shape the reference evaluates with (utils.py:93-95; triplets: (u, v) kept,
+    w replaced, dataloader.py:265-275) -- sample_and_gather_star / sample_and_hgather_star and the stage calls of that name.  `pairs`
+    stays the number of joined pairs P*K (a multiple of K); the step walks every source ONCE: n = P + P*K rows (source j is row j,
+    target i row P + i) under S = 2*P*K segments, own = [j // K | P + i] and its mirror; triplets: n = 2P + P*K rows in the order u, v,
+    w under S = 4*P*K segments, own = [j // K | 2P + i | P + j // K | 2P + i] -- `own` / `partner`, constants of (P, K) built here
+    (_star_segments).  The step takes (heads, tails) = (source [P], targets [P*K]) or ([u.. | v..], w [P*K]) and begins with
+    subgacc_step_prologue_star (include/subgacc_star.h): the launch count of the plain step, nothing allocated.  Everything else is
+    the one-batch pair or triplet step: both row forms, dtype=, packed_rows=, packed_half=, wide_keys=, small_rows=, order= /
+    sort_roots, out=, stage="counts" / "counts_attn", each under its own rules; (xz, indptr or ids, flags) and (C, sizes, table) are
+    bit for bit those of the step over the expanded list (Philox keys a walk by its root's id).  ValueError naming `star` for K < 1,
+    pairs % K != 0, batch=, dedup_roots=True (the structural repeats are gone; a hash on top is not built), rng="rand_r" (a rand_r
+    set depends on its place in the stream: there is nothing to be identical to) and stage="index"."""
 
     def __init__(self, csr, pairs, num_walks=200, num_steps=3, uniq_capacity=1 << 17, out=None, dedup_roots=False, rng="philox",
                  key_rows=True, sort_roots=True, batch=None, align_rows=True, order=None, ptr=True, triplets=False, stage=None,
-                 table_rows=2048, small_rows=False, dtype=None, packed_rows=None, wide_keys=False, packed_half=False):
+                 table_rows=2048, small_rows=False, dtype=None, packed_rows=None, wide_keys=False, star=None, packed_half=False):
         from .sampler import FUSED_MAX_Q, as_rank, key_rows_form, packed_rows_form, small_rows_form
+        self.star = 0
+        if star is not None:    # one source against K targets: refused before anything touches the device
+            K = int(star)
+            why = {f"K = {K} (one target a source at least)": K < 1,
+                   f"pairs = {int(pairs)} (the joined pairs P*K: a multiple of K = {K})": K >= 1 and (int(pairs) < 0 or int(pairs) % K != 0),
+                   "batch= (one batch per step)": batch is not None,
+                   "dedup_roots=True (the repeated sources are walked once already; a hash on top is not built)": bool(dedup_roots),
+                   "rng='rand_r' (a rand_r set depends on its place in the stream: there is no expanded step to be identical to)":
+                       rng == "rand_r",
+                   "stage='index' (no index form for stars)": stage == "index"}
+            if any(why.values()):
+                raise ValueError(f"StepBuffers(star={star!r}) does not go with " + "; ".join(k for k, v in why.items() if v))
+            self.star = K
         self.packed, self._unpacked, self._unpacked_step = False, None, -1
         # opt-in: the row form of a small shape over the key rows of the one-wave kernel, refused before anything touches the device
         small_rows = _small_rows_wanted("StepBuffers", small_rows, num_walks, num_steps, stage, lambda: {
@@ -720,6 +745,9 @@ class StepBuffers:
                              "stream: there is nothing to reproduce)")
         # n roots = rows of the step, S segments of the join: pairs [u | v] -> 2B and 2B, triplets [u | v | w] -> 3B and 4B
         n, S = (3 * self.B, 4 * self.B) if self.triplets else (2 * self.B, 2 * self.B)
+        if self.star:       # every source stands once: P (triplets: 2P, u and v) + P*K rows under the same S segments
+            self.P = self.B // self.star
+            n = (2 if self.triplets else 1) * self.P + self.B
         self.n, self.S, self.Q, self.k = n, S, self.M * self.m + 1, self.m + 1
         if self.Q > FUSED_MAX_Q or self.m < 1:
             raise ValueError(f"StepBuffers: num_walks*num_steps+1 = {self.Q} exceeds what the fused-row walk kernel holds")
@@ -780,6 +808,8 @@ class StepBuffers:
             self.worklist = torch.empty(n, dtype=torch.int32, device=dev)
             self.dedup_ws = torch.zeros(L.subgacc_step_dedup_workspace_bytes(n), dtype=torch.uint8, device=dev)
             self.dedup_steps = 0
+        if self.star:       # the segment lists of the star: constants of (P, K)
+            self.own, self.partner = _star_segments(self.P, self.star, self.triplets, dev)
         if stage in _KEY_STAGES:  # counts, sizes, the sorted keys and their feature rows; no output rows, no segment ids (a size pass for "index" alone)
             T = self.T
             self.counts = self._counts_buffer(S, T, dev) if stage in _COUNT_STAGES else None
@@ -915,7 +945,8 @@ def _step_sets(csr, bufs, cfg, rr, step_id):
     # from them on demand (the member count of a deduplicated step, X / nnz) is refused once they hold a later batch
     sets._fresh = lambda: getattr(bufs, "step_id", 0) == step_id
     sets.status, sets._tail = bufs.status, bufs.tail[bufs.S: bufs.S + (6 if bufs.dedup else 5)]
-    sets._rows_are_members = not bufs.triplets       # (the rows of w are joined twice: the join's rows are not the members)
+    # (the rows of w are joined twice, the row of a star's source K times: the join's rows are not the members)
+    sets._rows_are_members = not bufs.triplets and not getattr(bufs, "star", 0)
     sets.walk_order = bufs.walk_order
     if bufs.stage in _KEY_STAGES:   # no row form ran (the index form's row count is its caller's to read): the members are counted on demand
         sets._rows_are_members, sets._table_rows = False, bufs.T
@@ -994,13 +1025,20 @@ def _buffered_step(csr, e, bufs, seed, out, fit=False):
     L, st, dev = lib(), stream_ptr(), csr.device
     B, M, m, k, n, S = bufs.B, bufs.M, bufs.m, bufs.k, bufs.n, bufs.S      # n roots (rows), S segments
     PB = bufs.batch              # pairs per mirrored block of the segment list
-    if bufs.triplets:
+    star = getattr(bufs, "star", 0)
+    if star:        # e = (heads, tails): the sources (triplets: [u.. | v..]) and the P*K targets of StepBuffers(star=K)
+        heads, tails = e if isinstance(e, tuple) and len(e) == 2 else (None, None)
+        if heads is None or heads.numel() != n - B or tails.numel() != B or heads.dtype != torch.int64 or tails.dtype != torch.int64:
+            raise ValueError(f"these StepBuffers were made for {bufs.P} " + ("pairs (u, v)" if bufs.triplets else "sources") +
+                             f" against [{bufs.P}, {star}] targets (star={star})")
+        heads, tails = heads.contiguous(), tails.contiguous()
+    elif bufs.triplets:
         if tuple(e.shape) != (3, B):
             raise ValueError(f"these StepBuffers were made for [3, {B}] triplets")
     elif tuple(e.shape) != ((2, B) if PB == B else (B // PB, 2, PB)):
         raise ValueError(f"these StepBuffers were made for [2, {B}] pairs" if PB == B else
                          f"these StepBuffers were made for [{B // PB}, 2, {PB}] pairs")
-    e = e.contiguous()
+    e = None if star else e.contiguous()
     flags = bufs.status.view(torch.int32)[:4]
     small = bool(getattr(bufs, "small", False))      # a small shape (a stage, or small_rows=True): subgacc_walk_keyrows_small writes the key rows
     cfg = make_cfg(csr, M, m, -1, seed, bufs.rng, records=(2 <= m <= 4) and not small,     # (only the fused-row kernel of 2..4 hops reads hop records)
@@ -1021,6 +1059,8 @@ def _buffered_step(csr, e, bufs, seed, out, fit=False):
             check(L.subgacc_step_prologue_dedup(*tab, ptr(bufs.status), 4, ptr(e), ptr(bufs.roots), ptr(bufs.own), ptr(bufs.partner),
                                                 ptr(bufs.worklist), ptr(bufs.nsize), n, ptr(bufs.dedup_ws), bufs.dedup_ws.numel(),
                                                 ptr(bufs.n_distinct), st))
+    elif star:          # the sources once, then the targets: one launch over the two arrays
+        check(L.subgacc_step_prologue_star(*tab, ptr(bufs.status), 4, ptr(heads), n - B, ptr(tails), B, ptr(bufs.roots), st))
     else:
         check(L.subgacc_step_prologue(*tab, ptr(bufs.status), 4, ptr(e), ptr(bufs.roots), n, st))
     # the work list the walk kernel runs over.  Root dedup: its first occurrences (no sort by id there: what that order buys is mostly
@@ -1047,7 +1087,7 @@ def _buffered_step(csr, e, bufs, seed, out, fit=False):
               "keys_packed" if bufs.packed else "keys_small" if small else "keys64" if bufs.key64 else "fused", ids=bufs._ids, payload=bufs._slot,
               nsize=bufs.nsize, rng=(bufs.rng_pos, bufs.rng_seed) if rr else (None, None), table=bufs.table,
               capacity=0 if kr else bufs.capacity, work=work, select=bufs.dedup, nesc=bufs.nesc if bufs.packed else None)
-    if bufs.dedup:
+    if bufs.dedup or star:      # (a star: the constant lists of its StepBuffers)
         own, partner = bufs.own, bufs.partner
     elif bufs.triplets:
         own, partner = _triplet_segments(B, dev), None
@@ -1288,15 +1328,18 @@ def sample_and_hgather(csr, hedge, num_walks=200, num_steps=3, seed=111413, rng=
 
 
 def _step_counts(who, csr, e, triplets, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers, stage="counts",
-                 wide_keys=False):
+                 wide_keys=False, star=0):
     """sample_and_counts / sample_and_hcounts: the step with stage="counts" through the caller's StepBuffers, or through a set made for
-    this one call (stage="counts_attn": sample_and_attn_counts, which checks the step itself once its kernel has run)"""
+    this one call (stage="counts_attn": sample_and_attn_counts, which checks the step itself once its kernel has run).  star=K: e =
+    (heads, tails) of the step of one source against K targets (StepBuffers(star=K))"""
     from .sampler import as_rank, key_rows_form
     order = as_rank(csr, order)
     wide = bool(wide_keys) and key_rows_form(int(num_walks), int(num_steps)) == 64     # (the keyword means nothing at any other shape)
+    pairs = e[1].numel() if star else e.shape[1]
     if buffers is not None:
-        if buffers.stage != stage or buffers.triplets != triplets:
-            raise ValueError(f"{who}: buffers= must be StepBuffers(..., stage='{stage}'" + (", triplets=True)" if triplets else ")"))
+        if buffers.stage != stage or buffers.triplets != triplets or getattr(buffers, "star", 0) != star or (star and buffers.B != pairs):
+            raise ValueError(f"{who}: buffers= must be StepBuffers(..., stage='{stage}'" + (", triplets=True" if triplets else "") +
+                             (f", star={star}) for {pairs} pairs" if star else ")"))
         if (dedup_roots and not buffers.dedup) or (num_walks, num_steps) != (buffers.M, buffers.m) or \
                 (table_rows is not None and int(table_rows) != buffers.T) or wide != bool(getattr(buffers, "wide", False)):
             raise ValueError(f"{who}: buffers= serves the step its StepBuffers were made for (num_walks, num_steps, table_rows; root "
@@ -1307,8 +1350,9 @@ def _step_counts(who, csr, e, triplets, num_walks, num_steps, seed, dedup_roots,
     fit = table_rows is None
     T = (COUNTS_MAX_TABLE_ROWS_WIDE if wide else COUNTS_MAX_TABLE_ROWS) if fit else int(table_rows)
     _counts_stage_shape(who, num_walks, num_steps, True, T, wide_keys)
-    bufs = (_FitStepBuffers if fit else StepBuffers)(csr, e.shape[1], num_walks=num_walks, num_steps=num_steps, dedup_roots=dedup_roots,
-                                                     order=order, triplets=triplets, stage=stage, table_rows=T, wide_keys=wide_keys)
+    bufs = (_FitStepBuffers if fit else StepBuffers)(csr, pairs, num_walks=num_walks, num_steps=num_steps, dedup_roots=dedup_roots,
+                                                     order=order, triplets=triplets, stage=stage, table_rows=T, wide_keys=wide_keys,
+                                                     star=star or None)
     C, sizes, table, sets = _buffered_step(csr, e, bufs, seed, None, fit=fit)
     if stage != "counts_attn":
         sets.resolve()
@@ -1436,13 +1480,17 @@ class _StepAttnJoin:
         return Dg
 
 
-def _step_attn(who, csr, edge, gate, bias, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers, wide_keys=False):
+def _step_attn(who, csr, edge, gate, bias, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers, wide_keys=False, star=0):
     """sample_and_attn_counts with gate(table, count) -- count: the number of distinct LP rows c, int64 [1] on the device -- and the
-    gate's bias (None: none) as an input of the autograd function -> (W, sizes, table, sets, count)"""
-    e = _as_rows(edge, csr.device)
-    if e.dim() != 2 or e.shape[0] != 2:
-        raise ValueError(f"{who}: edge must be [2, B], not {list(e.shape)}")
-    if e.shape[1] == 0 and buffers is None:     # an empty batch: no step, the zero row alone
+    gate's bias (None: none) as an input of the autograd function -> (W, sizes, table, sets, count).  star=K: edge = (heads, tails)
+    of _star_step_rows, the step of one source against K targets"""
+    if star:
+        e = edge
+    else:
+        e = _as_rows(edge, csr.device)
+        if e.dim() != 2 or e.shape[0] != 2:
+            raise ValueError(f"{who}: edge must be [2, B], not {list(e.shape)}")
+    if not star and e.shape[1] == 0 and buffers is None:     # an empty batch: no step, the zero row alone
         T = 2 if table_rows is None else int(table_rows)
         _counts_stage_shape(who, num_walks, num_steps, True, T, wide_keys)
         dev = csr.device
@@ -1451,7 +1499,7 @@ def _step_attn(who, csr, edge, gate, bias, num_walks, num_steps, seed, dedup_roo
         sets, count = None, torch.zeros(1, dtype=torch.int64, device=dev)
     else:
         join, sizes, table, sets = _step_counts(who, csr, e, False, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers,
-                                                stage="counts_attn", wide_keys=wide_keys)
+                                                stage="counts_attn", wide_keys=wide_keys, star=star)
         count = join.bufs.status[2:3]
     g = gate(table, count)
     if not (torch.is_tensor(g) and g.shape == (join.T,) and g.dtype == torch.float32 and g.device == table.device):
@@ -1499,7 +1547,13 @@ def sample_and_attn_stage(csr, edge, embed, gate_nn, value_nn=None, num_walks=20
     reference's is analytically.  Returns float32 [2, B, H''] (H without value_nn), empty segments as zero rows.  Keywords as
     sample_and_attn_counts; with buffers= the step's SampledSets are `buffers.sets` (`.resolve()` raises when the step had more distinct
     LP rows than table_rows - 1), and the backward must run before the buffers take their next step (RuntimeError otherwise)."""
-    name = "sample_and_attn_stage"
+    return _attn_stage("sample_and_attn_stage", csr, edge, embed, gate_nn, value_nn, num_walks, num_steps, seed, dedup_roots, order,
+                       table_rows, buffers, wide_keys)
+
+
+def _attn_stage(name, csr, edge, embed, gate_nn, value_nn, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers,
+                wide_keys=False, star=0):
+    """sample_and_attn_stage; star=K: sample_and_attn_stage_star with edge = (heads, tails) of _star_step_rows"""
     other = "sample_and_gather(csr, edge, ...) and the modules on xz"
     gate = _one_linear(gate_nn, "gate_nn", None, 1, name, other)
     H = gate.in_features
@@ -1520,12 +1574,183 @@ def sample_and_attn_stage(csr, edge, embed, gate_nn, value_nn=None, num_walks=20
         return (E - centre) @ gate.weight.view(-1)
 
     W, sizes, table, sets, _ = _step_attn(name, csr, edge, logits, gate.bias, num_walks, num_steps, seed, dedup_roots, order, table_rows,
-                                          buffers, wide_keys)
+                                          buffers, wide_keys, star)
     h = W @ box["E"]
     if val is not None:
         h = torch.nn.functional.linear(h, val.weight, val.bias)
     out = h * (sizes > 0).to(h.dtype)[:, None]
     return out.view(2, -1, out.shape[-1])
+
+
+# ------------------------------------------------------------------------------ the on-demand step for one source against K targets
+def _star_step_rows(who, csr, heads, targets, triplets):
+    """the arguments of a *_star call as the step takes them: (heads int64 [P] -- triplets: [2, P] --, tails int64 [P*K], P, K) on the
+    graph's device, checked on the host by _star_rows first"""
+    dev = csr.device
+    if triplets:
+        uv = _as_rows(heads, dev)
+        if uv.dim() != 2 or uv.shape[0] != 2:
+            raise ValueError(f"{who}: uv must be [2, P] pairs (u, v), not {list(uv.shape)}")
+        _, targets = _star_rows(uv[0], targets)
+        heads = uv.contiguous()
+    else:
+        source, targets = _star_rows(heads, targets)
+        heads = _as_rows(source, dev).contiguous()
+    P, K = int(targets.shape[0]), int(targets.shape[1])
+    return heads, _as_rows(targets, dev).reshape(-1).contiguous(), P, K
+
+
+def _star_buffers_match(who, buffers, P, K, triplets, num_walks, num_steps, order, ptr=None, dtype=None, wide_keys=False, small_rows=False):
+    """buffers= of a row-form *_star call: StepBuffers(csr, P*K, ..., star=K) of this call's geometry, shape and result"""
+    from .sampler import key_rows_form
+    if getattr(buffers, "star", 0) != K or buffers.B != P * K or buffers.triplets != triplets or buffers.stage is not None or \
+            (ptr is not None and bool(ptr) != buffers.ptr) or (num_walks, num_steps) != (buffers.M, buffers.m):
+        raise ValueError(f"{who}: buffers= were made for another geometry or result: this call takes StepBuffers(csr, {P * K}, num_walks="
+                         f"{num_walks}, num_steps={num_steps}, star={K}" + (", triplets=True)" if triplets else f", ptr={bool(ptr)})"))
+    half = _half_code(dtype, who, dict)
+    half64 = bool(half) and key_rows_form(int(num_walks), int(num_steps)) == 64 and bool(wide_keys)
+    if half != getattr(buffers, "half", 0) or (half and half64 != bool(getattr(buffers, "half64", False))):
+        raise ValueError(f"{who}: dtype={dtype} but buffers= were made with dtype={getattr(buffers, 'dtype', None)}: "
+                         "StepBuffers(..., dtype=) allocates `out` in the type the step writes")
+    _small_rows_match(who, _small_rows_wanted(who, small_rows, num_walks, num_steps, None, dict), buffers)
+    if order is not None and (buffers.order is None or order.rank is not buffers.order.rank):
+        raise ValueError("buffers= walks in the order its StepBuffers were made with: pass order= to StepBuffers(...)")
+
+
+def _star_step(csr, e, pairs, seed, out, lazy, **how):
+    """a row-form *_star call without buffers=: StepBuffers(star=K) for this one call, the buffered step, and -- unless lazy -- the sets
+    resolved and (xz, ids) cut to the step's rows (as _small_step)"""
+    bufs = StepBuffers(csr, pairs, out=out, **how)
+    xz, ind, sets = _buffered_step(csr, e, bufs, seed, None)
+    if lazy:
+        return xz, ind, sets
+    sets.resolve()
+    R = int(sets.extra[0])
+    return xz[:R], (ind if bufs.ptr else _with_pointers(ind[:R], bufs.seg)), sets
+
+
+def sample_and_gather_star(csr, source, targets, num_walks=200, num_steps=3, seed=111413, out=None, lazy=False, buffers=None, order=None,
+                           ptr=True, small_rows=False, dtype=None, wide_keys=False, packed_rows=None, packed_half=False, sort_roots=True):
+    """The on-demand step for the shape the reference evaluates with -- one source against K candidates (utils.py:93-95, joined batch
+    by batch in train.py:246-280) -- without the expanded edge tensor: source int [P], targets int [P, K] (NumPy or torch, checked as
+    gather_star checks them).  Returns bit for bit what
+        sample_and_gather(csr, stack([source.repeat_interleave(K), targets.reshape(-1)]), ...)
+    returns with the same seed -- xz, indptr (ptr=False: the segment ids), the status flags -- while the step walks P + P*K roots
+    instead of 2*P*K: every source is sampled ONCE and K segments point at its row (StepBuffers(star=K)).  No hash, no extra launch:
+    the shape itself says which roots are repeats, and Philox keys a walk by (seed, root id, walk, hop), so a set does not depend on
+    where or how often its root stands.  A node that is a target twice, or a source of two stars, is walked as often as it stands.
+    buffers=StepBuffers(csr, P*K, ..., star=K): the allocation-free step (six launches for the row form; lazy, views of the
+    buffers, sets.prefetch() / sets.resolve() as for sample_and_gather).  Without buffers= a set is made for this one call, the sets
+    are resolved and (xz, ids) are the step's rows (lazy=True: the unresolved views; out=: room for the worst case, 2*P*K * (M*m+1)
+    rows).  ptr=, dtype=, wide_keys=, small_rows=, packed_rows=, packed_half=, order= and sort_roots are StepBuffers' keywords under
+    StepBuffers' rules.  Philox only, and no root dedup on top.  P*K = 0: what the expanded call returns for [2, 0]."""
+    from .sampler import as_rank
+    who = "sample_and_gather_star"
+    heads, tails, P, K = _star_step_rows(who, csr, source, targets, False)
+    order = as_rank(csr, order)
+    if buffers is not None:
+        _star_buffers_match(who, buffers, P, K, False, num_walks, num_steps, order, ptr, dtype, wide_keys, small_rows)
+        return _buffered_step(csr, (heads, tails), buffers, seed, out)
+    if P * K == 0:
+        return sample_and_gather(csr, _no_pairs(csr), num_walks, num_steps, seed, out=out,
+                                 lazy=lazy, order=order, ptr=ptr, small_rows=small_rows, dtype=dtype, wide_keys=wide_keys)
+    return _star_step(csr, (heads, tails), P * K, seed, out, lazy, num_walks=num_walks, num_steps=num_steps, star=K, order=order,
+                      ptr=bool(ptr), small_rows=small_rows, dtype=dtype, wide_keys=wide_keys, packed_rows=packed_rows,
+                      packed_half=packed_half, sort_roots=sort_roots)
+
+
+def sample_and_hgather_star(csr, uv, w, num_walks=200, num_steps=3, seed=111413, out=None, buffers=None, order=None, small_rows=False,
+                            dtype=None, sort_roots=True):
+    """sample_and_gather_star for the higher-order model's evaluation: a triplet whose (u, v) is kept and whose w is replaced by K
+    candidates (dataloader.py:265-275, eval_model_horder, train.py:283-317).  uv int [2, P], w int [P, K].  Returns bit for bit what
+        sample_and_hgather(csr, stack([u.repeat_interleave(K), v.repeat_interleave(K), w.reshape(-1)]), ...)
+    returns -- (xz, ids with .seg_pointers, sets) -- while the step walks 2*P + P*K roots instead of 3*P*K.
+    buffers=StepBuffers(csr, P*K, ..., triplets=True, star=K); small_rows= / dtype= as for sample_and_hgather.  P*K = 0: what the
+    expanded call returns for [3, 0]."""
+    from .sampler import as_rank
+    who = "sample_and_hgather_star"
+    heads, tails, P, K = _star_step_rows(who, csr, uv, w, True)
+    order = as_rank(csr, order)
+    if buffers is not None:
+        _star_buffers_match(who, buffers, P, K, True, num_walks, num_steps, order, None, dtype, False, small_rows)
+        return _buffered_step(csr, (heads, tails), buffers, seed, out)
+    if P * K == 0:
+        return sample_and_hgather(csr, _no_pairs(csr, 3), num_walks, num_steps, seed, out=out,
+                                  order=order, small_rows=small_rows, dtype=dtype)
+    return _star_step(csr, (heads, tails), P * K, seed, out, False, num_walks=num_walks, num_steps=num_steps, star=K, order=order,
+                      triplets=True, small_rows=small_rows, dtype=dtype, sort_roots=sort_roots)
+
+
+def _star_counts(who, csr, heads, targets, triplets, num_walks, num_steps, seed, order, table_rows, buffers, wide_keys):
+    """sample_and_counts_star / sample_and_hcounts_star: _step_counts over (heads, tails); an empty star is the expanded call's"""
+    heads, tails, P, K = _star_step_rows(who, csr, heads, targets, triplets)
+    if P * K == 0 and buffers is None:
+        return (sample_and_hcounts if triplets else sample_and_counts)(csr, _no_pairs(csr, 3 if triplets else 2), num_walks, num_steps, seed, False, order, table_rows,
+                                                                      None, wide_keys)
+    return _step_counts(who, csr, (heads, tails), triplets, num_walks, num_steps, seed, False, order, table_rows, buffers,
+                        wide_keys=wide_keys, star=K)
+
+
+def sample_and_counts_star(csr, source, targets, num_walks=200, num_steps=3, seed=111413, order=None, table_rows=None, buffers=None,
+                           wide_keys=False):
+    """sample_and_counts for one source against K targets: source [P], targets [P, K] -> (C float32 [2*P*K, T], sizes int32 [2*P*K],
+    table, sets), bit for bit those of sample_and_counts over the expanded pairs (the step's distinct keys are the same set, so ranks
+    and columns are too), with P + P*K roots walked.  buffers=StepBuffers(csr, P*K, ..., stage="counts", table_rows=T, star=K)."""
+    return _star_counts("sample_and_counts_star", csr, source, targets, False, num_walks, num_steps, seed, order, table_rows, buffers,
+                        wide_keys)
+
+
+def sample_and_hcounts_star(csr, uv, w, num_walks=200, num_steps=3, seed=111413, order=None, table_rows=None, buffers=None,
+                            wide_keys=False):
+    """sample_and_hcounts for (u, v) kept and w replaced by K candidates: uv [2, P], w [P, K] -> (C float32 [4*P*K, T], sizes, table,
+    sets), bit for bit those of the expanded triplets, with 2*P + P*K roots walked.
+    buffers=StepBuffers(csr, P*K, ..., triplets=True, stage="counts", table_rows=T, star=K)."""
+    return _star_counts("sample_and_hcounts_star", csr, uv, w, True, num_walks, num_steps, seed, order, table_rows, buffers, wide_keys)
+
+
+def sample_and_mean_stage_star(csr, source, targets, embed, num_walks=200, num_steps=3, seed=111413, order=None, table_rows=None,
+                               buffers=None, wide_keys=False):
+    """sample_and_mean_stage over sample_and_counts_star: (C @ embed(table)) / sizes as float32 [2, P*K, H]"""
+    return _step_mean(*sample_and_counts_star(csr, source, targets, num_walks, num_steps, seed, order, table_rows, buffers, wide_keys),
+                      embed, 2)
+
+
+def sample_and_hmean_stage_star(csr, uv, w, embed, num_walks=200, num_steps=3, seed=111413, order=None, table_rows=None, buffers=None,
+                                wide_keys=False):
+    """sample_and_hmean_stage over sample_and_hcounts_star: float32 [4, P*K, H] in the order (xu, xwu, xv, xwv)"""
+    return _step_mean(*sample_and_hcounts_star(csr, uv, w, num_walks, num_steps, seed, order, table_rows, buffers, wide_keys), embed, 4)
+
+
+def _no_pairs(csr, rows=2):
+    """the expanded edge tensor of an EMPTY star (P*K = 0): the *_star calls answer it as the expanded call does"""
+    return torch.empty((rows, 0), dtype=torch.int64, device=csr.device)
+
+
+def sample_and_attn_counts_star(csr, source, targets, gate, num_walks=200, num_steps=3, seed=111413, order=None, table_rows=None,
+                                buffers=None, wide_keys=False):
+    """sample_and_attn_counts for one source against K targets -> (W float32 [2*P*K, T], sizes, table, sets), bit for bit those of the
+    expanded pairs; W is differentiable with respect to the gate's logits as there.
+    buffers=StepBuffers(csr, P*K, ..., stage="counts_attn", table_rows=T, star=K)."""
+    who = "sample_and_attn_counts_star"
+    heads, tails, P, K = _star_step_rows(who, csr, source, targets, False)
+    if P * K == 0 and buffers is None:
+        return sample_and_attn_counts(csr, _no_pairs(csr), gate, num_walks, num_steps, seed, False, order,
+                                      table_rows, None, wide_keys)
+    return _step_attn(who, csr, (heads, tails), lambda table, count: gate(table), None, num_walks, num_steps, seed, False, order,
+                      table_rows, buffers, wide_keys, star=K)[:4]
+
+
+def sample_and_attn_stage_star(csr, source, targets, embed, gate_nn, value_nn=None, num_walks=200, num_steps=3, seed=111413, order=None,
+                               table_rows=None, buffers=None, wide_keys=False):
+    """sample_and_attn_stage for one source against K targets: float32 [2, P*K, H''], the documented expression over
+    sample_and_attn_counts_star's (W, sizes, table), every parameter of embed, gate_nn and value_nn with its gradient."""
+    who = "sample_and_attn_stage_star"
+    heads, tails, P, K = _star_step_rows(who, csr, source, targets, False)
+    if P * K == 0 and buffers is None:
+        return sample_and_attn_stage(csr, _no_pairs(csr), embed, gate_nn, value_nn, num_walks, num_steps, seed,
+                                     False, order, table_rows, None, wide_keys)
+    return _attn_stage(who, csr, (heads, tails), embed, gate_nn, value_nn, num_walks, num_steps, seed, False, order, table_rows,
+                       buffers, wide_keys, star=K)
 
 
 def sample_and_gather_many(csr, edges, num_walks=200, num_steps=3, seed=111413, rng="philox", out=None, buffers=None, order=None,
@@ -1606,6 +1831,21 @@ def _triplet_segments(B, device):
                     torch.cuda.current_stream(hit.device).synchronize()
                 _ARANGE_SEGMENTS[key] = hit
     return hit
+
+
+def _star_segments(P, K, triplets=False, device=None):
+    """The segment lists (own, partner) of a step of P sources against K targets each (StepBuffers(star=K)): the lists of the expanded
+    batch [source.repeat_interleave(K) | targets.view(-1)] with every endpoint mapped to the row of its first occurrence -- source j
+    is row j, target i row P + i: own = [j // K | P + i] over 2*P*K segments, partner its mirror.  triplets: the rows are u, v, w --
+    P, P and P*K of them -- and the list is hgather's [U|w ; W|u ; V|w ; W|v] over 4*P*K segments, own = [j // K | 2P + i | P + j // K |
+    2P + i], partner None (mirrored: the kernels derive it).  Constants of (P, K)."""
+    i = torch.arange(int(P) * int(K), dtype=torch.int64, device=device)
+    src = torch.div(i, int(K), rounding_mode="floor")
+    if triplets:
+        w = 2 * int(P) + i
+        return torch.cat([src, w, int(P) + src, w]), None
+    tgt = int(P) + i
+    return torch.cat([src, tgt]), torch.cat([tgt, src])
 
 
 def _packed_rows(spg, form):
