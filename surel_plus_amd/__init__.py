@@ -13,7 +13,9 @@ from .spjoin import (attn_stage, bgather, counts_attn_stage, gather, gather_coun
                      float_attn_stage, float_lstm_stage, float_mean_stage, hinge_intervals, hinge_tables, mean_stage, pgather, sample_and_attn_counts, sample_and_attn_stage, sample_and_counts, sample_and_gather, sample_and_gather_many, sample_and_hcounts, sample_and_hgather, sample_and_index, sample_and_lstm_stage,
                      sample_and_hmean_stage, sample_and_mean_stage, sjoin, split_batches, StepBuffers,
                      sample_and_attn_counts_star, sample_and_attn_stage_star, sample_and_counts_star, sample_and_gather_star,
-                     sample_and_hcounts_star, sample_and_hgather_star, sample_and_hmean_stage_star, sample_and_mean_stage_star)
+                     sample_and_hcounts_star, sample_and_hgather_star, sample_and_hmean_stage_star, sample_and_mean_stage_star,
+                     sample_and_fused_hmean_stage, sample_and_fused_hmean_stage_star, sample_and_fused_mean_stage,
+                     sample_and_fused_mean_stage_star)
 from .subg_acc import batch_sampler, gset_sampler, walk_join, walk_sampler  # noqa: F401
 from .ppr import topk_ppr_matrix  # noqa: F401
 from .stepgraph import CapturedJoin, CapturedJoinPool, CapturedStep, CapturedStepPool  # noqa: F401

@@ -612,6 +612,15 @@ class StepBuffers:
     form, nor segment ids.  The buffers are those of "counts" without `counts`, plus `pairs` int32 [S * (M*m+1), 2] (the worst case; the
     first seg[-1] rows are a step's result) and the size pass's workspace.  Same refusals, and triplets=True (HONet has no LSTM
     aggregation, model_horder.py:56-57).
+    stage="mean" (with width=H): the step of sample_and_fused_mean_stage / sample_and_fused_hmean_stage and their *_star twins -- the
+    same launches up to the columns, then the caller's E = embed(table) float32 [table_rows, H] in torch and the mean first stage fused
+    into the count join (subgacc_sjoin_key_mean, include/subgacc_mean.h): the count matrix is never written.  The buffers are those of
+    "counts" WITHOUT `counts` -- the largest buffer of that set -- plus `mean` float32 [S, H], the stage's result.  width is required
+    here and a ValueError with any other stage; every refusal of "counts" applies, and small shapes, wide_keys=True, triplets,
+    dedup_roots, order= and star=K come under the rules of "counts".  Nothing is allocated or read back by the step (capturable), so
+    -- as `counts` -- `mean` is valid only once `sets.resolve()` has passed: a pair whose join raised a flag is left unwritten and
+    holds what an earlier step left there.  The backward joins the step's rows again, into a C of its own: it must run before the
+    buffers take their next step.
     dtype=torch.float16 / torch.bfloat16: `out` -- the largest buffer of the set -- is allocated in that type, half the bytes, and the
     step's join writes it through subgacc_sjoin_fill_half (sjoin(dtype=)); sample_and_gather(buffers=) must ask for the same dtype.
     The row form over 32-bit key rows with segment pointers: ValueError for ptr=False, triplets=True, a stage, key_rows=False, a shape
@@ -666,7 +675,8 @@ class StepBuffers:
 
     def __init__(self, csr, pairs, num_walks=200, num_steps=3, uniq_capacity=1 << 17, out=None, dedup_roots=False, rng="philox",
                  key_rows=True, sort_roots=True, batch=None, align_rows=True, order=None, ptr=True, triplets=False, stage=None,
-                 table_rows=2048, small_rows=False, dtype=None, packed_rows=None, wide_keys=False, star=None, packed_half=False):
+                 table_rows=2048, small_rows=False, dtype=None, packed_rows=None, wide_keys=False, star=None, width=None,
+                 packed_half=False):
         from .sampler import FUSED_MAX_Q, as_rank, key_rows_form, packed_rows_form, small_rows_form
         self.star = 0
         if star is not None:    # one source against K targets: refused before anything touches the device
@@ -712,7 +722,8 @@ class StepBuffers:
         self.half64 = bool(self.half) and key_rows_form(int(num_walks), int(num_steps)) == 64
         self.stage, self.T = stage, int(table_rows)
         if stage not in (None,) + _KEY_STAGES:
-            raise ValueError(f"StepBuffers: stage is None (the row form), 'counts', 'counts_attn' or 'index', not {stage!r}")
+            raise ValueError(f"StepBuffers: stage is None (the row form), 'counts', 'counts_attn', 'index' or 'mean', not {stage!r}")
+        self.width = _mean_width(stage, width)     # (refused before anything touches the device)
         if stage in _KEY_STAGES:  # refused before anything touches the device
             who = f"StepBuffers(stage='{stage}')"
             if stage == "index" and triplets:
@@ -813,6 +824,8 @@ class StepBuffers:
         if stage in _KEY_STAGES:  # counts, sizes, the sorted keys and their feature rows; no output rows, no segment ids (a size pass for "index" alone)
             T = self.T
             self.counts = self._counts_buffer(S, T, dev) if stage in _COUNT_STAGES else None
+            if stage == "mean":             # the stage's result; no C
+                self.mean = torch.empty((S, self.width), dtype=torch.float32, device=dev) if self.width else None
             if stage == "counts_attn":      # m_j and den_j of the softmax, for the backward
                 self.smax, self.sden = (None, None) if self.counts is None else \
                     (torch.empty(S, dtype=torch.float32, device=dev), torch.empty(S, dtype=torch.float32, device=dev))
@@ -886,10 +899,31 @@ class _FitStepBuffers(StepBuffers):
         return None
 
 
+MEAN_MAX_WIDTH = 1024              # subgacc_sjoin_key_mean: the features of a row of E
+# width= of the buffers a sample_and_fused_*mean_stage* call makes for itself (_step_counts): the width of embed(table) is known only
+# once the step has run, so they hold no `mean` (width 0) and the join writes a tensor of that call (_StepMeanJoin.forward)
+_WIDTH_OF_CALL = object()
+
+
+def _mean_width(stage, width):
+    """StepBuffers(stage="mean", width=H): H, the features of a row of the caller's E = embed(table) -- required there, refused with
+    any other stage (0: no `mean`)"""
+    if stage != "mean":
+        if width is not None:
+            raise ValueError(f"StepBuffers(width={width!r}) goes with stage='mean' alone (the width of `mean`), not stage={stage!r}")
+        return 0
+    if width is _WIDTH_OF_CALL:
+        return 0
+    if width is None or not 1 <= int(width) <= MEAN_MAX_WIDTH:
+        raise ValueError(f"StepBuffers(stage='mean') needs width=H, the features of a row of embed(table) (1 .. {MEAN_MAX_WIDTH}), "
+                         f"not width={width!r}: `mean` is float32 [S, H]")
+    return int(width)
+
+
 COUNTS_MAX_TABLE_ROWS = 16384      # subgacc_keyrows_columns sorts the distinct keys of a step in LDS
 COUNTS_MAX_TABLE_ROWS_WIDE = 8192  # ... subgacc_keyrows_columns64 sorts 64-bit keys in the same 128 KiB
 _COUNT_STAGES = ("counts", "counts_attn")       # the stages of a step that run over the columns of its LP keys: the count forms
-_KEY_STAGES = _COUNT_STAGES + ("index",)        # ... and the index form
+_KEY_STAGES = _COUNT_STAGES + ("index", "mean")     # ... the index form, and the mean first stage fused into the count join
 
 
 def _counts_stage_shape(who, num_walks, num_steps, key_rows, table_rows, wide_keys=False):
@@ -1096,6 +1130,9 @@ def _buffered_step(csr, e, bufs, seed, out, fit=False):
     if bufs.stage == "counts_attn":     # (C: the step's _StepAttnJoin -- the gate is the caller's, the kernel runs once it is there)
         T = _step_columns(bufs, flags, st, fit)[1]
         C, table = _StepAttnJoin(bufs, own, partner, T, step_id, flags), bufs.feat[:T]
+    elif bufs.stage == "mean":          # (C: the step's _StepMeanJoin -- E = embed(table) is the caller's, the kernel runs once it is there)
+        T = _step_columns(bufs, flags, st, fit)[1]
+        C, table = _StepMeanJoin(bufs, own, partner, T, step_id, flags), bufs.feat[:T]
     elif bufs.stage == "counts":
         C, table = _counts_tail(bufs, own, partner, flags, st, fit)
     elif bufs.stage == "index":
@@ -1352,9 +1389,9 @@ def _step_counts(who, csr, e, triplets, num_walks, num_steps, seed, dedup_roots,
     _counts_stage_shape(who, num_walks, num_steps, True, T, wide_keys)
     bufs = (_FitStepBuffers if fit else StepBuffers)(csr, pairs, num_walks=num_walks, num_steps=num_steps, dedup_roots=dedup_roots,
                                                      order=order, triplets=triplets, stage=stage, table_rows=T, wide_keys=wide_keys,
-                                                     star=star or None)
+                                                     star=star or None, width=_WIDTH_OF_CALL if stage == "mean" else None)
     C, sizes, table, sets = _buffered_step(csr, e, bufs, seed, None, fit=fit)
-    if stage != "counts_attn":
+    if stage not in ("counts_attn", "mean"):        # (those two check the step themselves once their kernel has run)
         sets.resolve()
     return C, sizes, table, sets
 
@@ -1719,6 +1756,146 @@ def sample_and_hmean_stage_star(csr, uv, w, embed, num_walks=200, num_steps=3, s
                                 wide_keys=False):
     """sample_and_hmean_stage over sample_and_hcounts_star: float32 [4, P*K, H] in the order (xu, xwu, xv, xwv)"""
     return _step_mean(*sample_and_hcounts_star(csr, uv, w, num_walks, num_steps, seed, order, table_rows, buffers, wide_keys), embed, 4)
+
+
+# ------------------------------------------------------------------------------ the mean first stage fused into the count join
+class _StepMeanJoin:
+    """the library calls of sample_and_fused_mean_stage over the key rows of ONE step of `bufs`: the descriptor of _counts_tail and the
+    step's stamp, as _StepAttnJoin.  forward: subgacc_sjoin_key_mean, no C.  backward: the step's rows are joined again by
+    subgacc_sjoin_key_counts into a C allocated for the backward alone, dE = C.t() @ (dOut / sizes) -- the gradient of the unfused
+    stage, deterministic, no new kernel.  With buffers= the rows live until the buffers take their next step: a kernel or backward
+    that comes later is refused, never answered from another batch."""
+
+    def __init__(self, bufs, own, partner, T, step_id, flags):
+        self.bufs, self.own, self.partner, self.T, self.step_id, self.flags = bufs, own, partner, int(T), step_id, flags
+        self.S, self.dev = bufs.S, bufs.sizes.device
+
+    def desc(self):
+        return _step_key_desc(self.bufs, JOIN_COUNTS, self.own, self.partner, self.T, self.flags)
+
+    def _require_fresh(self, what):
+        now = getattr(self.bufs, "step_id", 0)
+        if now != self.step_id:
+            raise RuntimeError(f"sample_and_fused_mean_stage: the {what} of step {self.step_id} of these StepBuffers ran after they took "
+                               f"step {now}: the rows it joins are gone (run a step's backward before the buffers' next step)")
+
+    def forward(self, E):
+        """E float32 [T, H], contiguous, detached -> out float32 [S, H]: `mean` of the caller's buffers, or a tensor of this call"""
+        b, H = self.bufs, int(E.shape[1])
+        out = b.mean.detach() if b.mean is not None else torch.empty((self.S, H), dtype=torch.float32, device=self.dev)
+        self._require_fresh("kernel")
+        with _timed("sjoin_key_mean"):
+            d = self.desc()
+            check(lib().subgacc_sjoin_key_mean(ctypes.byref(d), ptr(b.ukeys), ptr(b.status[2:3]), ptr(E), H, ptr(out), ptr(b.sizes),
+                                               stream_ptr()))
+        return out
+
+    def backward(self, dOut):
+        b = self.bufs
+        self._require_fresh("backward")
+        # zeros, not empty: a pair that raises a flag is left unwritten, and a buffered step reads no flag back before the product
+        C = torch.zeros((self.S, self.T), dtype=torch.float32, device=self.dev)
+        with _timed("sjoin_key_counts"):
+            d = self.desc()
+            check(lib().subgacc_sjoin_key_counts(ctypes.byref(d), ptr(b.ukeys), ptr(b.status[2:3]), ptr(C), None, stream_ptr()))
+        return C.t() @ (dOut / b.sizes.clamp(min=1).to(torch.float32)[:, None])
+
+
+class _FusedMean(torch.autograd.Function):
+    """out [S, H] of subgacc_sjoin_key_mean as a function of E = embed(table); backward: _StepMeanJoin.backward"""
+
+    @staticmethod
+    def forward(ctx, E, join):
+        ctx.join = join
+        return join.forward(E.detach().contiguous())
+
+    @staticmethod
+    def backward(ctx, dOut):
+        return ctx.join.backward(dOut.contiguous()), None
+
+
+def _fused_mean(who, csr, e, triplets, embed, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers, wide_keys, star=0):
+    """the four sample_and_fused_*mean_stage* calls: the step with stage="mean" (_step_counts), E = embed(table), the fused join.
+    star=K: e = (heads, tails) of _star_step_rows"""
+    join, sizes, table, sets = _step_counts(who, csr, e, triplets, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers,
+                                            stage="mean", wide_keys=wide_keys, star=star)
+    E, dev = embed(table), table.device
+    if not (torch.is_tensor(E) and E.ndim == 2 and E.shape[0] == join.T and E.dtype == torch.float32 and E.device == dev):
+        raise ValueError(f"{who}: embed(table) must be a float32 [{join.T}, H] tensor on {dev}, one row per row of table" +
+                         (f", not {E.dtype} {list(E.shape)} on {E.device}" if torch.is_tensor(E) else f", not {type(E).__name__}"))
+    H = int(E.shape[1])
+    want = join.bufs.width
+    if (want and H != want) or not 1 <= H <= MEAN_MAX_WIDTH:
+        raise ValueError(f"{who}: embed(table) has rows of {H} features, " +
+                         (f"buffers= were made with width={want}" if want else f"the fused join takes 1 .. {MEAN_MAX_WIDTH}"))
+    if torch.is_grad_enabled() and E.requires_grad:
+        out = _FusedMean.apply(E, join)
+    else:
+        out = join.forward(E.detach().contiguous())
+    if buffers is None:
+        sets.resolve()
+    return out.view(4 if triplets else 2, -1, H)
+
+
+def sample_and_fused_mean_stage(csr, edge, embed, num_walks=200, num_steps=3, seed=111413, dedup_roots=False, order=None, table_rows=None,
+                                buffers=None, wide_keys=False):
+    """sample_and_mean_stage without the count matrix: the reference's first model stage for mean aggregation (model.py:78-83) on the
+    on-demand step, (C @ E) / sizes with E = embed(table), where the join multiplies a pair's two count rows by E while they stand in
+    LDS (subgacc_sjoin_key_mean, include/subgacc_mean.h) -- neither C float32 [2B, T] nor the GEMM behind it exists in the forward.
+    The result is defined by one float32 chain per (segment, feature): acc = acc + float(c) * E[x, h] over the columns x with a count
+    c != 0 in ascending order, a separate multiply and add, then one division by max(size, 1) -- the same bits whatever the schedule, the
+    walk order (order=), root dedup, buffers and the star form; against sample_and_mean_stage (whose GEMM sums in another order) it
+    agrees to rounding, and bit for bit where every sum is exact.  `embed` is any row-wise module with float32 [T, H] output on the
+    graph's device, 1 <= H <= 1,024 (ValueError naming this call otherwise); every parameter receives a gradient: the backward joins
+    the step's rows again into a C of its own (subgacc_sjoin_key_counts) and returns dE = C.t() @ (dOut / sizes) -- under
+    torch.no_grad(), or when E needs no gradient, no C ever exists.  Returns float32 [2, B, H], empty segments as zero rows.
+    Keywords as sample_and_mean_stage; buffers=StepBuffers(csr, B, ..., stage="mean", table_rows=T, width=H): nothing is allocated or
+    read back (capturable), the result is a view of `buffers.mean`, the step is checked through `buffers.sets.resolve()`, and the
+    backward must run before the buffers take their next step (RuntimeError naming the step otherwise).  Without buffers the step is
+    checked before the result is returned; table_rows=None reads the number of distinct LP rows back once."""
+    who = "sample_and_fused_mean_stage"
+    e = _as_rows(edge, csr.device)
+    if e.dim() != 2 or e.shape[0] != 2:
+        raise ValueError(f"{who}: edge must be [2, B], not {list(e.shape)}")
+    return _fused_mean(who, csr, e, False, embed, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers, wide_keys)
+
+
+def sample_and_fused_hmean_stage(csr, hedge, embed, num_walks=200, num_steps=3, seed=111413, dedup_roots=False, order=None,
+                                 table_rows=None, buffers=None, wide_keys=False):
+    """sample_and_hmean_stage without the count matrix (HONet's first stage, model_horder.py:56-57): sample_and_fused_mean_stage for the
+    triplets `hedge` [3, B].  Returns float32 [4, B, H] in the order (xu, xwu, xv, xwv).
+    buffers=StepBuffers(csr, B, ..., triplets=True, stage="mean", table_rows=T, width=H)."""
+    who = "sample_and_fused_hmean_stage"
+    h = _as_triplets(hedge, csr.device, who)
+    return _fused_mean(who, csr, h, True, embed, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers, wide_keys)
+
+
+def _fused_mean_star(who, csr, heads, targets, triplets, embed, num_walks, num_steps, seed, order, table_rows, buffers, wide_keys):
+    """the two *_star calls: _fused_mean over (heads, tails); an empty star is the expanded call's"""
+    heads, tails, P, K = _star_step_rows(who, csr, heads, targets, triplets)
+    if P * K == 0 and buffers is None:
+        return _fused_mean(who, csr, _no_pairs(csr, 3 if triplets else 2), triplets, embed, num_walks, num_steps, seed, False, order,
+                           table_rows, None, wide_keys)
+    return _fused_mean(who, csr, (heads, tails), triplets, embed, num_walks, num_steps, seed, False, order, table_rows, buffers, wide_keys,
+                       star=K)
+
+
+def sample_and_fused_mean_stage_star(csr, source, targets, embed, num_walks=200, num_steps=3, seed=111413, order=None, table_rows=None,
+                                     buffers=None, wide_keys=False):
+    """sample_and_fused_mean_stage for one source against K targets (source [P], targets [P, K]): float32 [2, P*K, H], bit for bit the
+    call over the expanded pairs, with P + P*K roots walked -- the shape the reference evaluates with, where C would be written only to
+    be multiplied away.  buffers=StepBuffers(csr, P*K, ..., stage="mean", table_rows=T, width=H, star=K)."""
+    return _fused_mean_star("sample_and_fused_mean_stage_star", csr, source, targets, False, embed, num_walks, num_steps, seed, order,
+                            table_rows, buffers, wide_keys)
+
+
+def sample_and_fused_hmean_stage_star(csr, uv, w, embed, num_walks=200, num_steps=3, seed=111413, order=None, table_rows=None,
+                                      buffers=None, wide_keys=False):
+    """sample_and_fused_hmean_stage for (u, v) kept and w replaced by K candidates (uv [2, P], w [P, K]): float32 [4, P*K, H] in the
+    order (xu, xwu, xv, xwv), bit for bit the call over the expanded triplets.
+    buffers=StepBuffers(csr, P*K, ..., triplets=True, stage="mean", table_rows=T, width=H, star=K)."""
+    return _fused_mean_star("sample_and_fused_hmean_stage_star", csr, uv, w, True, embed, num_walks, num_steps, seed, order, table_rows,
+                            buffers, wide_keys)
 
 
 def _no_pairs(csr, rows=2):
