@@ -15,7 +15,7 @@ from .spjoin import (attn_stage, bgather, counts_attn_stage, gather, gather_coun
                      sample_and_attn_counts_star, sample_and_attn_stage_star, sample_and_counts_star, sample_and_gather_star,
                      sample_and_hcounts_star, sample_and_hgather_star, sample_and_hmean_stage_star, sample_and_mean_stage_star,
                      sample_and_fused_hmean_stage, sample_and_fused_hmean_stage_star, sample_and_fused_mean_stage,
-                     sample_and_fused_mean_stage_star)
+                     sample_and_fused_mean_stage_star, sample_and_fused_attn_stage, sample_and_fused_attn_stage_star)
 from .subg_acc import batch_sampler, gset_sampler, walk_join, walk_sampler  # noqa: F401
 from .ppr import topk_ppr_matrix  # noqa: F401
 from .stepgraph import CapturedJoin, CapturedJoinPool, CapturedStep, CapturedStepPool  # noqa: F401

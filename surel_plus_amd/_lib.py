@@ -3,7 +3,8 @@
 (the step's key rows as one word per member), of include/subgacc_wide.h (the columns of 64-bit key rows), of include/subgacc_half64.h
 (the 16-bit rows over 64-bit key rows), of include/subgacc_packed_half.h (the packed rows joined in 16 bits), of
 include/subgacc_half_ids.h (the 16-bit rows with their segment ids), of include/subgacc_star.h (the prologue of a step of one
-source against K targets) and of include/subgacc_mean.h (the mean first stage fused into the count join) when this module is imported: an entry point is declared there and defined under csrc/, and
+source against K targets), of include/subgacc_mean.h (the mean first stage fused into the count join) and of include/subgacc_attn.h
+(the attentional first stage fused into the attentional count join) when this module is imported: an entry point is declared there and defined under csrc/, and
 nothing here names it.
 
 There is no CPU fallback: if the library is missing, or no gfx950 device is visible when a compute entry
@@ -162,6 +163,12 @@ MEAN_HEADER = os.path.join(os.path.dirname(HEADER), "subgacc_mean.h")
 MEAN_DECLS = parse_header(_header_text(MEAN_HEADER))
 _TYPES.update(bind_types(MEAN_DECLS))
 MEAN_SYMBOLS = tuple(MEAN_DECLS)
+# the eleventh header: the LP encoder's attentional first stage fused into the attentional count join of a step
+# (csrc/sjoin_key_attn.hip), the same library
+ATTN_HEADER = os.path.join(os.path.dirname(HEADER), "subgacc_attn.h")
+ATTN_DECLS = parse_header(_header_text(ATTN_HEADER))
+_TYPES.update(bind_types(ATTN_DECLS))
+ATTN_SYMBOLS = tuple(ATTN_DECLS)
 HALF_F16, HALF_BF16 = (int(re.search(rf"^#define\s+SUBGACC_HALF_{n}\s+(\d+)", _HALF_TEXT, re.M).group(1)) for n in ("F16", "BF16"))
 
 
@@ -174,7 +181,7 @@ def build(force=False):
     """hipcc-compile csrc/*.hip for gfx950 into surel_plus_amd/libsubgacc_hip.so (in-tree)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp"))]
     srcs += [HEADER, HALF_HEADER, SMALL_HEADER, PACKED_HEADER, WIDE_HEADER, HALF64_HEADER, PACKED_HALF_HEADER, HALF_IDS_HEADER, STAR_HEADER,
-             MEAN_HEADER]
+             MEAN_HEADER, ATTN_HEADER]
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
         subprocess.check_call(["make", "-s", "-C", CSRC, "-j4", "all"])

@@ -1,7 +1,8 @@
 // sjoin_attn.hpp -- the count form with attentional aggregation (internal): ONE body for the packed SFptr store
 // (sjoin_counts_attn_kernel<BWD>, sjoin_forms.hip) and for the key rows of an on-demand step (sjoin_key_counts_attn_kernel<BWD>,
 // sjoin_keys.hip).  The two forms of the stage promise the same bits, and they get them from the same text: the kernels differ in where a
-// member's column comes from (TableColumns / KeyColumns, sjoin_cols.hpp) and in nothing else.
+// member's column comes from (TableColumns / KeyColumns, sjoin_cols.hpp) and in nothing else.  sjoin_key_attn_kernel
+// (sjoin_key_attn.hip) runs the forward of the same text up to its store, and multiplies the two rows by E there (Tail, below).
 //
 // Count form with attentional aggregation (model.py:59-62,78-81 for the LP encoder; include/subgacc.h: subgacc_sjoin_counts_attn).
 // Member t of segment j is the index pair (p_t, q_t) -- own column, partner column or 0 -- and its gate logit is l_t = g[p_t] + g[q_t]
@@ -33,8 +34,17 @@ static size_t counts_attn_lds(int64_t max_len, int64_t rows, int64_t dcap, bool 
     return 4 * ((size_t)max_len * 7 + (size_t)rows * 2 + (size_t)dcap * (bwd ? 6 : 2) + 8 + (size_t)key_words);
 }
 
-template <bool BWD, class Cols>
-__device__ __forceinline__ void counts_attn_body(const JoinArgs &a, int64_t pb, int32_t dcap, const CountsAttnArgs &c, Cols cols) {
+// What the forward does with a pair's two finished rows of W, accf[0 .. rows) and accf[rows .. 2 rows) in LDS (zero bits wherever a
+// column does not occur): StoreW, the default, stores them to out_w; a Tail with kFused (sjoin_key_attn.hip: the rows times
+// E = embed(table)) is called with them instead -- tail(accf, rows, cols, jS, jT), by every lane, behind the barrier -- and out_w
+// is never looked at.
+struct StoreW {
+    static constexpr bool kFused = false;
+};
+
+template <bool BWD, class Cols, class Tail = StoreW>
+__device__ __forceinline__ void counts_attn_body(const JoinArgs &a, int64_t pb, int32_t dcap, const CountsAttnArgs &c, Cols cols,
+                                                 Tail tail = Tail()) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     const int L = a.max_len, rows = (int)a.table_rows;
     int32_t *idsT = (int32_t *)lds_raw;                     // [L]
@@ -131,10 +141,14 @@ __device__ __forceinline__ void counts_attn_body(const JoinArgs &a, int64_t pb, 
             if (x == (blk ? c0 : 0)) stf[4 + blk] = den;
         }
         __syncthreads();
-        float *outS = c.out_w + jS * (int64_t)rows, *outT = c.out_w + jT * (int64_t)rows;
-        for (int x = tid; x < rows; x += kPairThreads) {
-            __builtin_nontemporal_store(accf[x], outS + x);
-            __builtin_nontemporal_store(accf[rows + x], outT + x);
+        if constexpr (Tail::kFused) {
+            tail(accf, rows, cols, jS, jT);
+        } else {
+            float *outS = c.out_w + jS * (int64_t)rows, *outT = c.out_w + jT * (int64_t)rows;
+            for (int x = tid; x < rows; x += kPairThreads) {
+                __builtin_nontemporal_store(accf[x], outS + x);
+                __builtin_nontemporal_store(accf[rows + x], outT + x);
+            }
         }
         if (tid == 0 && c.out_max) {
             c.out_max[jS] = m0, c.out_max[jT] = m1;

@@ -79,4 +79,21 @@ __device__ __forceinline__ int32_t ord_of(float f) {     // a float as an int of
 }
 __device__ __forceinline__ float float_of(int32_t o) { return __int_as_float(o >= 0 ? o : o ^ 0x7FFFFFFF); }
 
+// What every entry point over the key rows of a step refuses alike about its descriptor, in this order: subgacc_sjoin_key_counts, the
+// attentional pair and subgacc_sjoin_key_index (sjoin_keys.hip; rows_form: the index form, which has always looked at its form before
+// the options), subgacc_sjoin_key_mean (sjoin_mean.hip) and subgacc_sjoin_key_attn (sjoin_key_attn.hip)
+static int key_join_check(const char *name, const subgacc_join_desc *d, RowLayout &layout, bool rows_form = false) {
+    if (int rc = decode_desc(name, d, true, layout)) return rc;
+    SG_REQUIRE(!rows_form || d->form == SUBGACC_JOIN_ROWS, SUBGACC_ERR_BADARG,
+               "%s: writes the index pairs of the row form (form ROWS), not form %d", name, (int)d->form);
+    SG_REQUIRE(d->options == 0, SUBGACC_ERR_BADARG, "%s: takes no option (options = %d)", name, (int)d->options);
+    SG_REQUIRE(d->payload_kind == SUBGACC_JOIN_KEY32, SUBGACC_ERR_BADARG,
+               "%s: joins rows of 32-bit LP keys (KEY32), not payload kind %d", name, (int)d->payload_kind);
+    SG_REQUIRE(layout == RowLayout::Strided, SUBGACC_ERR_BADARG,
+               "%s: joins the strided key rows of a step (row_len and row_stride set, row_off NULL), not packed or headed rows", name);
+    SG_REQUIRE(d->table_rows >= 2 && d->table_rows < (1ll << 31), SUBGACC_ERR_BADARG,
+               "%s: table_rows = %lld (the absent column and at least one LP row: >= 2)", name, (long long)d->table_rows);
+    return SUBGACC_OK;
+}
+
 }  // namespace subgacc

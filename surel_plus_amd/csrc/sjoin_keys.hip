@@ -164,22 +164,7 @@ __global__ __launch_bounds__(kPairThreads) void sjoin_key_index_kernel(const Joi
 
 using namespace subgacc;
 
-// What the three entry points refuse alike about their descriptor, in this order (rows_form: subgacc_sjoin_key_index, which has always
-// looked at its form before the options)
-static int key_join_check(const char *name, const subgacc_join_desc *d, RowLayout &layout, bool rows_form = false) {
-    if (int rc = decode_desc(name, d, true, layout)) return rc;
-    SG_REQUIRE(!rows_form || d->form == SUBGACC_JOIN_ROWS, SUBGACC_ERR_BADARG,
-               "%s: writes the index pairs of the row form (form ROWS), not form %d", name, (int)d->form);
-    SG_REQUIRE(d->options == 0, SUBGACC_ERR_BADARG, "%s: takes no option (options = %d)", name, (int)d->options);
-    SG_REQUIRE(d->payload_kind == SUBGACC_JOIN_KEY32, SUBGACC_ERR_BADARG,
-               "%s: joins rows of 32-bit LP keys (KEY32), not payload kind %d", name, (int)d->payload_kind);
-    SG_REQUIRE(layout == RowLayout::Strided, SUBGACC_ERR_BADARG,
-               "%s: joins the strided key rows of a step (row_len and row_stride set, row_off NULL), not packed or headed rows", name);
-    SG_REQUIRE(d->table_rows >= 2 && d->table_rows < (1ll << 31), SUBGACC_ERR_BADARG,
-               "%s: table_rows = %lld (the absent column and at least one LP row: >= 2)", name, (long long)d->table_rows);
-    return SUBGACC_OK;
-}
-
+// (what the entry points refuse alike about their descriptor: key_join_check, sjoin_cols.hpp)
 extern "C" int subgacc_sjoin_key_counts(const subgacc_join_desc *d, const int32_t *ukeys, const int64_t *n_keys, float *out_counts,
                                         int32_t *out_len, void *stream) {
     const char *name = "sjoin_key_counts";

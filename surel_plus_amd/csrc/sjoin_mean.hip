@@ -143,24 +143,11 @@ __global__ __launch_bounds__(kPairThreads) void sjoin_key_mean_kernel(const Join
 
 using namespace subgacc;
 
-// What subgacc_sjoin_key_counts refuses about its descriptor, in its order (key_join_check of sjoin_keys.hip)
-static int key_mean_check(const char *name, const subgacc_join_desc *d, RowLayout &layout) {
-    if (int rc = decode_desc(name, d, true, layout)) return rc;
-    SG_REQUIRE(d->options == 0, SUBGACC_ERR_BADARG, "%s: takes no option (options = %d)", name, (int)d->options);
-    SG_REQUIRE(d->payload_kind == SUBGACC_JOIN_KEY32, SUBGACC_ERR_BADARG,
-               "%s: joins rows of 32-bit LP keys (KEY32), not payload kind %d", name, (int)d->payload_kind);
-    SG_REQUIRE(layout == RowLayout::Strided, SUBGACC_ERR_BADARG,
-               "%s: joins the strided key rows of a step (row_len and row_stride set, row_off NULL), not packed or headed rows", name);
-    SG_REQUIRE(d->table_rows >= 2 && d->table_rows < (1ll << 31), SUBGACC_ERR_BADARG,
-               "%s: table_rows = %lld (the absent column and at least one LP row: >= 2)", name, (long long)d->table_rows);
-    return SUBGACC_OK;
-}
-
 extern "C" int subgacc_sjoin_key_mean(const subgacc_join_desc *d, const int32_t *ukeys, const int64_t *n_keys, const float *e,
                                       int32_t width, float *out_mean, int32_t *out_len, void *stream) {
     const char *name = "sjoin_key_mean";
     RowLayout layout;
-    if (int rc = key_mean_check(name, d, layout)) return rc;
+    if (int rc = key_join_check(name, d, layout)) return rc;       // every refusal of subgacc_sjoin_key_counts, in its order
     SG_REQUIRE(ukeys && n_keys && e && out_mean, SUBGACC_ERR_BADARG, "%s: ukeys, n_keys, e and out_mean are required (a NULL one given)",
                name);
     SG_REQUIRE(width >= 1 && width <= kMeanMaxWidth, SUBGACC_ERR_BADARG, "%s: width = %d (the features of a row of e: 1 .. %d)", name,

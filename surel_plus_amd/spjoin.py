@@ -621,6 +621,14 @@ class StepBuffers:
     -- as `counts` -- `mean` is valid only once `sets.resolve()` has passed: a pair whose join raised a flag is left unwritten and
     holds what an earlier step left there.  The backward joins the step's rows again, into a C of its own: it must run before the
     buffers take their next step.
+    stage="attn" (with width=H): the step of sample_and_fused_attn_stage and its *_star twin -- the same launches up to the columns,
+    then the caller's E = embed(table) float32 [table_rows, H] and gate g in torch and the attentional first stage fused into the
+    attentional count join (subgacc_sjoin_key_attn, include/subgacc_attn.h): the softmax-weighted count matrix W is never written.
+    The buffers are those of "counts_attn" WITHOUT `counts` -- the largest buffer of that set -- plus `attn` float32 [S, H], the
+    aggregation W @ E; `smax` and `sden` stay.  width is required as for "mean"; every refusal of "counts_attn" applies, and small
+    shapes, wide_keys=True, dedup_roots, order= and star=K come under its rules.  Capturable; `attn` is valid only once
+    `sets.resolve()` has passed.  The backward joins the step's rows again, into a W of its own: it must run before the buffers
+    take their next step.
     dtype=torch.float16 / torch.bfloat16: `out` -- the largest buffer of the set -- is allocated in that type, half the bytes, and the
     step's join writes it through subgacc_sjoin_fill_half (sjoin(dtype=)); sample_and_gather(buffers=) must ask for the same dtype.
     The row form over 32-bit key rows with segment pointers: ValueError for ptr=False, triplets=True, a stage, key_rows=False, a shape
@@ -722,7 +730,7 @@ class StepBuffers:
         self.half64 = bool(self.half) and key_rows_form(int(num_walks), int(num_steps)) == 64
         self.stage, self.T = stage, int(table_rows)
         if stage not in (None,) + _KEY_STAGES:
-            raise ValueError(f"StepBuffers: stage is None (the row form), 'counts', 'counts_attn', 'index' or 'mean', not {stage!r}")
+            raise ValueError(f"StepBuffers: stage is None (the row form), 'counts', 'counts_attn', 'index', 'mean' or 'attn', not {stage!r}")
         self.width = _mean_width(stage, width)     # (refused before anything touches the device)
         if stage in _KEY_STAGES:  # refused before anything touches the device
             who = f"StepBuffers(stage='{stage}')"
@@ -829,6 +837,9 @@ class StepBuffers:
             if stage == "counts_attn":      # m_j and den_j of the softmax, for the backward
                 self.smax, self.sden = (None, None) if self.counts is None else \
                     (torch.empty(S, dtype=torch.float32, device=dev), torch.empty(S, dtype=torch.float32, device=dev))
+            if stage == "attn":             # the aggregation W @ E, m_j and den_j; no W
+                self.attn = torch.empty((S, self.width), dtype=torch.float32, device=dev) if self.width else None
+                self.smax, self.sden = torch.empty(S, dtype=torch.float32, device=dev), torch.empty(S, dtype=torch.float32, device=dev)
             self.sizes = torch.empty(S, dtype=torch.int32, device=dev)
             self.ukeys = torch.empty(T - 1, dtype=torch.int32, device=dev)
             self.feat = torch.empty((T, self.k), dtype=torch.float32, device=dev)
@@ -899,31 +910,35 @@ class _FitStepBuffers(StepBuffers):
         return None
 
 
-MEAN_MAX_WIDTH = 1024              # subgacc_sjoin_key_mean: the features of a row of E
-# width= of the buffers a sample_and_fused_*mean_stage* call makes for itself (_step_counts): the width of embed(table) is known only
-# once the step has run, so they hold no `mean` (width 0) and the join writes a tensor of that call (_StepMeanJoin.forward)
+MEAN_MAX_WIDTH = 1024              # subgacc_sjoin_key_mean and subgacc_sjoin_key_attn: the features of a row of E
+# width= of the buffers a sample_and_fused_*mean_stage* / sample_and_fused_attn_stage* call makes for itself (_step_counts): the width
+# of embed(table) is known only once the step has run, so they hold no `mean` / `attn` (width 0) and the join writes a tensor of that
+# call (_StepMeanJoin.forward, _StepFusedAttnJoin.fused)
 _WIDTH_OF_CALL = object()
+_WIDTH_STAGES = {"mean": "mean", "attn": "attn"}        # the stages that take width=H, and the buffer of that width
 
 
 def _mean_width(stage, width):
-    """StepBuffers(stage="mean", width=H): H, the features of a row of the caller's E = embed(table) -- required there, refused with
-    any other stage (0: no `mean`)"""
-    if stage != "mean":
+    """StepBuffers(stage="mean" / "attn", width=H): H, the features of a row of the caller's E = embed(table) -- required there, refused
+    with any other stage (0: no `mean` / `attn`)"""
+    if stage not in _WIDTH_STAGES:
         if width is not None:
-            raise ValueError(f"StepBuffers(width={width!r}) goes with stage='mean' alone (the width of `mean`), not stage={stage!r}")
+            raise ValueError(f"StepBuffers(width={width!r}) goes with stage='mean' or 'attn' alone (the width of `mean` / `attn`), "
+                             f"not stage={stage!r}")
         return 0
     if width is _WIDTH_OF_CALL:
         return 0
     if width is None or not 1 <= int(width) <= MEAN_MAX_WIDTH:
-        raise ValueError(f"StepBuffers(stage='mean') needs width=H, the features of a row of embed(table) (1 .. {MEAN_MAX_WIDTH}), "
-                         f"not width={width!r}: `mean` is float32 [S, H]")
+        raise ValueError(f"StepBuffers(stage='{stage}') needs width=H, the features of a row of embed(table) (1 .. {MEAN_MAX_WIDTH}), "
+                         f"not width={width!r}: `{_WIDTH_STAGES[stage]}` is float32 [S, H]")
     return int(width)
 
 
 COUNTS_MAX_TABLE_ROWS = 16384      # subgacc_keyrows_columns sorts the distinct keys of a step in LDS
 COUNTS_MAX_TABLE_ROWS_WIDE = 8192  # ... subgacc_keyrows_columns64 sorts 64-bit keys in the same 128 KiB
 _COUNT_STAGES = ("counts", "counts_attn")       # the stages of a step that run over the columns of its LP keys: the count forms
-_KEY_STAGES = _COUNT_STAGES + ("index", "mean")     # ... the index form, and the mean first stage fused into the count join
+# ... the index form, and the mean / attentional first stage fused into the count join
+_KEY_STAGES = _COUNT_STAGES + ("index", "mean", "attn")
 
 
 def _counts_stage_shape(who, num_walks, num_steps, key_rows, table_rows, wide_keys=False):
@@ -1133,6 +1148,9 @@ def _buffered_step(csr, e, bufs, seed, out, fit=False):
     elif bufs.stage == "mean":          # (C: the step's _StepMeanJoin -- E = embed(table) is the caller's, the kernel runs once it is there)
         T = _step_columns(bufs, flags, st, fit)[1]
         C, table = _StepMeanJoin(bufs, own, partner, T, step_id, flags), bufs.feat[:T]
+    elif bufs.stage == "attn":          # (C: the step's _StepFusedAttnJoin -- g and E = embed(table) are the caller's)
+        T = _step_columns(bufs, flags, st, fit)[1]
+        C, table = _StepFusedAttnJoin(bufs, own, partner, T, step_id, flags), bufs.feat[:T]
     elif bufs.stage == "counts":
         C, table = _counts_tail(bufs, own, partner, flags, st, fit)
     elif bufs.stage == "index":
@@ -1389,9 +1407,9 @@ def _step_counts(who, csr, e, triplets, num_walks, num_steps, seed, dedup_roots,
     _counts_stage_shape(who, num_walks, num_steps, True, T, wide_keys)
     bufs = (_FitStepBuffers if fit else StepBuffers)(csr, pairs, num_walks=num_walks, num_steps=num_steps, dedup_roots=dedup_roots,
                                                      order=order, triplets=triplets, stage=stage, table_rows=T, wide_keys=wide_keys,
-                                                     star=star or None, width=_WIDTH_OF_CALL if stage == "mean" else None)
+                                                     star=star or None, width=_WIDTH_OF_CALL if stage in _WIDTH_STAGES else None)
     C, sizes, table, sets = _buffered_step(csr, e, bufs, seed, None, fit=fit)
-    if stage not in ("counts_attn", "mean"):        # (those two check the step themselves once their kernel has run)
+    if stage not in ("counts_attn", "mean", "attn"):        # (those check the step themselves once their kernel has run)
         sets.resolve()
     return C, sizes, table, sets
 
@@ -1470,6 +1488,7 @@ class _StepAttnJoin:
     `bufs`: the descriptor of _counts_tail, the step's stamp.  The backward joins the step's rows again, and with buffers= those rows
     live until the buffers take their next step: a backward that comes later is refused, never answered from another batch.
     bufs = None: an empty batch, nothing is launched."""
+    who = "sample_and_attn_counts"
 
     def __init__(self, bufs, own, partner, T, step_id, flags, dev=None):
         self.bufs, self.own, self.partner, self.T, self.step_id, self.flags = bufs, own, partner, int(T), step_id, flags
@@ -1482,7 +1501,7 @@ class _StepAttnJoin:
     def _require_fresh(self, what):
         now = getattr(self.bufs, "step_id", 0)
         if now != self.step_id:
-            raise RuntimeError(f"sample_and_attn_counts: the {what} of step {self.step_id} of these StepBuffers ran after they took "
+            raise RuntimeError(f"{self.who}: the {what} of step {self.step_id} of these StepBuffers ran after they took "
                                f"step {now}: the rows it joins are gone (run a step's backward before the buffers' next step)")
 
     def forward(self, g, keep):
@@ -1896,6 +1915,152 @@ def sample_and_fused_hmean_stage_star(csr, uv, w, embed, num_walks=200, num_step
     buffers=StepBuffers(csr, P*K, ..., triplets=True, stage="mean", table_rows=T, width=H, star=K)."""
     return _fused_mean_star("sample_and_fused_hmean_stage_star", csr, uv, w, True, embed, num_walks, num_steps, seed, order, table_rows,
                             buffers, wide_keys)
+
+
+# --------------------------------------------------------------------- the attentional first stage fused into the attentional count join
+class _StepFusedAttnJoin(_StepAttnJoin):
+    """the library calls of sample_and_fused_attn_stage over the key rows of ONE step of `bufs` (stage="attn": no `counts`).  fused:
+    subgacc_sjoin_key_attn, A = W @ E without W.  The backward uses no new kernel: the step's rows are joined again by
+    subgacc_sjoin_key_counts_attn into a W allocated for the backward alone (rejoin), then _StepAttnJoin.backward.  The stale-step
+    rule is _StepAttnJoin's."""
+    who = "sample_and_fused_attn_stage"
+
+    def fused(self, g, E, keep):
+        """g float32 [T], E float32 [T, H], contiguous, detached -> (A float32 [S, H], m, den): `attn`, `smax`, `sden` of the caller's
+        buffers, or tensors of this call"""
+        b, H = self.bufs, int(E.shape[1])
+        A = b.attn.detach() if b.attn is not None else torch.empty((self.S, H), dtype=torch.float32, device=self.dev)
+        mx, den = (b.smax.detach(), b.sden.detach()) if keep else (None, None)
+        self._require_fresh("kernel")
+        with _timed("sjoin_key_attn"):
+            d = self.desc()
+            check(lib().subgacc_sjoin_key_attn(ctypes.byref(d), ptr(b.ukeys), ptr(b.status[2:3]), ptr(g), ptr(E), H, ptr(A), ptr(mx),
+                                               ptr(den), ptr(b.sizes), stream_ptr()))
+        return A, mx, den
+
+    def rejoin(self, g):
+        """W float32 [S, T] of the step, for the backward alone"""
+        b = self.bufs
+        self._require_fresh("backward")
+        # zeros, not empty: a pair that raises a flag is left unwritten, and a buffered step reads no flag back before the products
+        # (_StepAttnJoin.backward's reason)
+        W = torch.zeros((self.S, self.T), dtype=torch.float32, device=self.dev)
+        with _timed("sjoin_key_counts_attn"):
+            d = self.desc()
+            check(lib().subgacc_sjoin_key_counts_attn(ctypes.byref(d), ptr(b.ukeys), ptr(b.status[2:3]), ptr(g), ptr(W), None, None, None,
+                                                      stream_ptr()))
+        return W
+
+
+class _FusedAttn(torch.autograd.Function):
+    """A [S, H] of subgacc_sjoin_key_attn as a function of g, the gate bias (whose gradient is exactly zero: softmax drops a constant)
+    and E = embed(table); backward: W rejoined, dE = W.t() @ dA, dg = the rows of subgacc_sjoin_key_counts_attn_backward for
+    dW = dA @ E.t(), summed over the segments"""
+
+    @staticmethod
+    def forward(ctx, g, bg, E, join):
+        ctx.join = join
+        ctx.has_bg = bg is not None
+        g, E = g.detach().contiguous(), E.detach().contiguous()
+        A, mx, den = join.fused(g, E, True)
+        ctx.save_for_backward(g, E, mx, den)
+        return A
+
+    @staticmethod
+    def backward(ctx, dA):
+        g, E, mx, den = ctx.saved_tensors
+        dA = dA.contiguous()
+        W = ctx.join.rejoin(g)
+        dE = W.t() @ dA
+        Dg = ctx.join.backward(g, (dA @ E.t()).contiguous(), W, mx, den)
+        bg = torch.zeros((1,), dtype=dA.dtype, device=dA.device) if ctx.has_bg else None
+        return Dg.sum(0), bg, dE, None
+
+
+def _fused_attn_stage(name, csr, edge, embed, gate_nn, value_nn, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers,
+                      wide_keys=False, star=0):
+    """sample_and_fused_attn_stage; star=K: sample_and_fused_attn_stage_star with edge = (heads, tails) of _star_step_rows.
+    _attn_stage with the step of stage="attn" and subgacc_sjoin_key_attn in the place of W @ E"""
+    other = "sample_and_gather(csr, edge, ...) and the modules on xz"
+    gate = _one_linear(gate_nn, "gate_nn", None, 1, name, other)
+    H = gate.in_features
+    val = _one_linear(value_nn, "value_nn", H, None, name, other) if value_nn is not None else None
+    dev = csr.device
+    for mod in (gate, val, embed):
+        for prm in (mod.parameters() if mod is not None else ()):
+            if prm.device != dev or prm.dtype != torch.float32:
+                raise ValueError(f"{name}: embed, gate_nn and value_nn must hold float32 parameters on the graph's device ({dev})")
+    if star:
+        e = edge
+    else:
+        e = _as_rows(edge, dev)
+        if e.dim() != 2 or e.shape[0] != 2:
+            raise ValueError(f"{name}: edge must be [2, B], not {list(e.shape)}")
+        if e.shape[1] == 0 and buffers is None:      # an empty batch: no step and no W either way
+            return _attn_stage(name, csr, e, embed, gate_nn, value_nn, num_walks, num_steps, seed, dedup_roots, order, table_rows, None,
+                               wide_keys)
+    join, sizes, table, sets = _step_counts(name, csr, e, False, num_walks, num_steps, seed, dedup_roots, order, table_rows, buffers,
+                                            stage="attn", wide_keys=wide_keys, star=star)
+    count = join.bufs.status[2:3]
+    E = embed(table)
+    if not (torch.is_tensor(E) and E.ndim == 2 and E.shape[0] == join.T and E.shape[1] == H and E.dtype == torch.float32
+            and E.device == table.device):
+        raise ValueError(f"{name}: embed(table) must be a float32 [{join.T}, {H}] tensor on {table.device} (gate_nn takes rows of {H})" +
+                         (f", not {E.dtype} {list(E.shape)} on {E.device}" if torch.is_tensor(E) else f", not {type(E).__name__}"))
+    want = join.bufs.width
+    if (want and H != want) or not 1 <= H <= MEAN_MAX_WIDTH:
+        raise ValueError(f"{name}: embed(table) has rows of {H} features, " +
+                         (f"buffers= were made with width={want}" if want else f"the fused join takes 1 .. {MEAN_MAX_WIDTH}"))
+    live = (torch.arange(table.shape[0], device=dev) <= count).to(torch.float32)        # rows 0 .. c, from the step's count word
+    centre = (E.detach() * live[:, None]).sum(0) / (count + 1).to(torch.float32)
+    g = (E - centre) @ gate.weight.view(-1)
+    if torch.is_grad_enabled() and (g.requires_grad or E.requires_grad or (gate.bias is not None and gate.bias.requires_grad)):
+        h = _FusedAttn.apply(g, gate.bias, E, join)
+    else:
+        h = join.fused(g.detach().contiguous(), E.detach().contiguous(), False)[0]
+    if buffers is None:
+        sets.resolve()
+    if val is not None:
+        h = torch.nn.functional.linear(h, val.weight, val.bias)
+    out = h * (sizes > 0).to(h.dtype)[:, None]
+    return out.view(2, -1, out.shape[-1])
+
+
+def sample_and_fused_attn_stage(csr, edge, embed, gate_nn, value_nn=None, num_walks=200, num_steps=3, seed=111413, dedup_roots=False,
+                                order=None, table_rows=None, buffers=None, wide_keys=False):
+    """sample_and_attn_stage without the softmax-weighted count matrix: the reference's first model stage of the LP encoder for
+    --aggr attn (model.py:59-62,78-81) on the on-demand step,
+        E = embed(table),  g = (E - centre) wg,  out_j = nn(W[j] @ E) [n_j > 0]
+    with the same live-row centre, where the join multiplies a pair's two rows of W by E while they stand in LDS
+    (subgacc_sjoin_key_attn, include/subgacc_attn.h) -- neither W float32 [2B, T] nor the GEMM behind it exists in the forward.  The
+    aggregation is defined by one float32 chain per (segment, feature): acc = acc + W[j, r] * E[r, h] over the columns r whose W is not
+    zero, in ascending order, a separate multiply and add -- the same bits whatever the schedule, the walk order (order=), root dedup,
+    buffers and the star form; against sample_and_attn_stage (whose GEMM sums in another order) it agrees to rounding.  Modules as
+    for sample_and_attn_stage, embed's width H <= 1,024 (ValueError naming this call otherwise).  Every parameter of embed, gate_nn
+    and value_nn receives a gradient, the gate bias's exactly zero: the backward joins the step's rows again into a W of its own
+    (subgacc_sjoin_key_counts_attn) and returns dE = W.t() @ dA and dg from subgacc_sjoin_key_counts_attn_backward over
+    dW = dA @ E.t() -- under torch.no_grad(), or when nothing needs a gradient, no [2B, T] tensor ever exists.  Returns float32
+    [2, B, H''] (H without value_nn), empty segments as zero rows.  Keywords as sample_and_attn_stage;
+    buffers=StepBuffers(csr, B, ..., stage="attn", table_rows=T, width=H): nothing is allocated or read back by the forward under
+    no_grad (capturable), the aggregation is `buffers.attn`, the step is checked through `buffers.sets.resolve()`, and the backward
+    must run before the buffers take their next step (RuntimeError naming both steps otherwise).  Without buffers the step is
+    checked before the result is returned."""
+    return _fused_attn_stage("sample_and_fused_attn_stage", csr, edge, embed, gate_nn, value_nn, num_walks, num_steps, seed, dedup_roots,
+                             order, table_rows, buffers, wide_keys)
+
+
+def sample_and_fused_attn_stage_star(csr, source, targets, embed, gate_nn, value_nn=None, num_walks=200, num_steps=3, seed=111413,
+                                     order=None, table_rows=None, buffers=None, wide_keys=False):
+    """sample_and_fused_attn_stage for one source against K targets (source [P], targets [P, K]): float32 [2, P*K, H''], bit for bit the
+    call over the expanded pairs, with P + P*K roots walked -- the shape the reference evaluates with (forward only), where W would
+    be written only to be multiplied away.  buffers=StepBuffers(csr, P*K, ..., stage="attn", table_rows=T, width=H, star=K)."""
+    who = "sample_and_fused_attn_stage_star"
+    heads, tails, P, K = _star_step_rows(who, csr, source, targets, False)
+    if P * K == 0 and buffers is None:
+        return sample_and_fused_attn_stage(csr, _no_pairs(csr), embed, gate_nn, value_nn, num_walks, num_steps, seed, False, order,
+                                           table_rows, None, wide_keys)
+    return _fused_attn_stage(who, csr, (heads, tails), embed, gate_nn, value_nn, num_walks, num_steps, seed, False, order, table_rows,
+                             buffers, wide_keys, star=K)
 
 
 def _no_pairs(csr, rows=2):
